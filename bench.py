@@ -16,9 +16,17 @@ the host and nothing synchronises inside the timed region.
 Multi-GPU: environments are independent, so the batch is sharded (65536 per rank, weak scaling)
 with no data-path collective; RCCL only carries the max-over-ranks time and the step total.
 
-The JSON line also carries
-  roofline     -- algorithmic HBM bytes per launch / average kernel duration (HIP events on the
-                  launch stream, measured here) against the 8 TB/s HBM3E peak;
+A plain run sets up, warms up, times the --steps steps and prints the JSON line; its roofline
+divides the algorithmic bytes by the step time from HIP events over the timed steps.
+
+    --dump-outputs DIR  after the timed steps, what the last one handed its caller (observation,
+                        reward, terminated, truncated) as DIR/<name>.npy in float64 -- inputs are
+                        seeded, so two builds of the project can be compared output for output
+    --full              everything beyond the headline figure, each in runs of its own:
+  roofline     -- algorithmic HBM bytes per launch / kernel duration (launches issued back to back
+                  from C, HIP events on the launch stream) against the 8 TB/s HBM3E peak, the PMC
+                  traffic and fp64 issue figures, iteration and collapse statistics;
+  config       -- the cap-20 and tol-1e-5 variants, every other BASELINE configuration;
   cpu_baseline -- the NumPy/SciPy restatement of the reference algorithm (oracle/anm_oracle.py,
                   literal scipy.sparse + spsolve path) timed on one host core for a bounded sample.
 """
@@ -471,9 +479,17 @@ def parse_args(argv=None):
     ap.add_argument("--no-live-pmc", action="store_true", help="do not spawn the rocprofv3 counter passes (roofline.traffic then "
                     "carries the committed figure of an earlier run)")
     ap.add_argument("--headline-only", action="store_true",
-                    help="skip the secondary figures (cap-20, case30) so that a rocprofv3 trace of this command holds "
-                         "only launches of the headline configuration")
-    return ap.parse_args(argv)
+                    help="with --full: skip the secondary figures (cap-20, case30) so that a rocprofv3 trace of this "
+                         "command holds only launches of the headline configuration")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: the kernel timed from C, PMC passes, "
+                         "workload statistics, secondary figures, other configurations, the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned (obs, reward, terminated, truncated) as DIR/<name>.npy")
+    args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be at least 1: ms_per_step and --dump-outputs come from the timed steps")
+    return args
 
 
 def rank_info(environ=None):
@@ -609,6 +625,30 @@ def default_make_env(num_envs, device, args, env_offset, seed):
                        precision=args.precision, autoreset=True, env_offset=env_offset)  # fmt: skip
 
 
+DUMP_LIMIT_BYTES = 64 * 2**20
+
+
+def dump_outputs(directory, result, rank=0, world=1, limit=DUMP_LIMIT_BYTES):
+    """`env.step`'s return of the last timed step -- obs, reward, terminated, truncated -- as <directory>/<name>.npy in
+    float64 (flags as 0 / 1), this rank's shard (file names carry the rank when there are several).  Above `limit` bytes
+    in all, a fixed seeded sample of environments is written instead, with their indices as rows.npy."""
+    import numpy as np
+
+    obs, rew, term, trunc, _ = result
+    arrays = {"obs": obs, "reward": rew, "terminated": term, "truncated": trunc}
+    arrays = {k: v.detach().to("cpu", torch.float64).numpy() for k, v in arrays.items()}
+    n = len(arrays["reward"])
+    row_bytes = sum(a[0].nbytes if a.ndim > 1 else 8 for a in arrays.values())
+    if n * row_bytes > limit:
+        rows = np.sort(np.random.default_rng(0).choice(n, size=limit // (row_bytes + 8), replace=False))
+        arrays = {k: v[rows] for k, v in arrays.items()}
+        arrays["rows"] = rows.astype(np.float64)
+    os.makedirs(directory, exist_ok=True)
+    suffix = "" if world == 1 else "_rank%d" % rank
+    for name, a in arrays.items():
+        np.save(os.path.join(directory, name + suffix + ".npy"), np.ascontiguousarray(a))
+
+
 def main(argv=None, make_env=None, backend="nccl", device_type="cuda", script=None):
     """make_env / backend / device_type: the CPU tier's launcher test passes the host test double, "gloo" and "cpu";
     the benchmark itself never does (no flag selects them)."""
@@ -663,25 +703,28 @@ def main(argv=None, make_env=None, backend="nccl", device_type="cuda", script=No
     if gpu:
         ev0.record()  # torch's current stream == the stream every step kernel is launched on (_step_call)
     for i in range(args.steps):
-        env.step(pool[i % n_pool])
+        result = env.step(pool[i % n_pool])
     if gpu:
         ev1.record()
     comm.barrier()
     elapsed = time.perf_counter() - t0
     # HIP events over the timed region: kernel + launch gap
     step_events_s = ev0.elapsed_time(ev1) * 1e-3 / args.steps if gpu else elapsed / args.steps
+    if args.dump_outputs:  # before any further step overwrites the buffers the last one returned
+        dump_outputs(args.dump_outputs, result, rank, world)
     # statistics of the workload (outside the timed region)
-    for i in range(8):
-        env.step(pool[i % n_pool])
-        iters_sum += env.simulator.nr_iters.double().mean()
-        term_sum += env.terminated.double().mean()
+    if args.full:
+        for i in range(8):
+            env.step(pool[i % n_pool])
+            iters_sum += env.simulator.nr_iters.double().mean()
+            term_sum += env.terminated.double().mean()
     elapsed = comm.reduce([elapsed], "max")[0]                       # the slowest rank's clock
     total_steps = comm.reduce([float(E * args.steps)], "sum")[0]     # the units all ranks processed
 
     sim = env.simulator
     kernel_s = step_events_s
     n_launch = args.steps
-    if gpu:
+    if gpu and args.full:
         # cross-check: the same launch issued back to back from C (no Python between launches), HIP events
         # on the launch stream; one fixed action batch
         import ctypes as C
@@ -719,8 +762,9 @@ def main(argv=None, make_env=None, backend="nccl", device_type="cuda", script=No
     # ever exceed ~8 iterations) are then cut off early; on every sample tested the terminated flags
     # are identical to the reference's cap of 100, but that is an observation, not a proof, so the
     # headline `value` above keeps the reference's cap.
+    side = args.full and not args.headline_only
     alt = None
-    if rank == 0 and args.max_iter == 100 and not args.headline_only:
+    if rank == 0 and args.max_iter == 100 and side:
         sim.opts.max_iter = 20
         alt_elapsed = timed_steps(args.steps)
         alt = {"nr_max_iter": 20, "value_1gpu": E * args.steps / alt_elapsed, "ms_per_step": 1e3 * alt_elapsed / args.steps}
@@ -728,7 +772,7 @@ def main(argv=None, make_env=None, backend="nccl", device_type="cuda", script=No
 
     # the reference's own stop tolerance (simulator.py:529 passes 1e-5) as a second secondary figure
     alt_tol = None
-    if rank == 0 and args.tol != 1e-5 and not args.headline_only:
+    if rank == 0 and args.tol != 1e-5 and side:
         sim.opts.tol = 1e-5
         dt1 = timed_steps(args.steps)
         alt_tol = {"nr_tol": 1e-5, "nr_max_iter": args.max_iter, "value_1gpu": E * args.steps / dt1,
@@ -739,7 +783,7 @@ def main(argv=None, make_env=None, backend="nccl", device_type="cuda", script=No
     # measured by EVERY rank on its own GPU (north_star: "larger random radial networks at 1/2/4/8 GPUs") and reported
     # as sum of rates / slowest launch like the headline; the others (one-GPU configurations) by rank 0 of a 1-GPU run.
     other = None
-    if gpu and not args.headline_only:
+    if gpu and side:
         other = {}
         try:
             fig = case30_side_figure(dev)
@@ -764,30 +808,31 @@ def main(argv=None, make_env=None, backend="nccl", device_type="cuda", script=No
         traffic = None
         traffic_source = None
         valu = None
-        try:
-            pt = None
-            if gpu and world == 1 and not args.headline_only and not args.no_live_pmc:
-                pt = live_pmc(args)   # counters of THIS configuration on THIS box, collected by this run
-                if pt is not None:
-                    pt.update(num_envs=E, nr_max_iter=args.max_iter, precision=args.precision)
-                    src = ("live: rocprofv3 --kernel-trace --pmc passes (FETCH_SIZE / WRITE_SIZE / SQ_INSTS_VALU, one group per pass) "
-                           "spawned by this run around a %d-launch headline-only run of the same configuration; FETCH_SIZE %.2f MB x2 "
-                           "(gfx950 correction) + WRITE_SIZE %.2f MB" % (pt["launches_averaged"], pt["fetch_bytes_raw"] / 1e6, pt["write_bytes_raw"] / 1e6))
-            if pt is None:
-                pt = json.load(open(os.path.join(ROOT, "profiles", "pmc_traffic.json")))
-                src = "profiles/pmc_traffic.json (%s): PMC passes of an earlier run of this configuration, not of this run" % pt.get("source", "?")
-            if gpu and pt["num_envs"] == E and pt["nr_max_iter"] == args.max_iter and pt["precision"] == args.precision:
-                traffic = pt["hbm_bytes_per_launch"]
-                traffic_source = src
-                # what really bounds the kernel: fp64 VALU issue.  A wave64 fp64 instruction occupies its
-                # SIMD for 4 cycles, so the chip issues at most 256 CU x 4 SIMD x 2.4 GHz / 4 of them per s.
-                peak_issue = 256 * 4 * 2.4e9 / 4
-                valu = {"wave_instructions_per_launch": pt["valu_wave_insts_per_launch"],
-                        "achieved_per_s": pt["valu_wave_insts_per_launch"] / kernel_s, "peak_per_s": peak_issue,
-                        "frac": pt["valu_wave_insts_per_launch"] / kernel_s / peak_issue,
-                        "note": "chip-wide average; after ~9 iterations only waves holding a diverging solve run"}
-        except Exception:
-            pass
+        if args.full:
+            try:
+                pt = None
+                if gpu and world == 1 and side and not args.no_live_pmc:
+                    pt = live_pmc(args)   # counters of THIS configuration on THIS box, collected by this run
+                    if pt is not None:
+                        pt.update(num_envs=E, nr_max_iter=args.max_iter, precision=args.precision)
+                        src = ("live: rocprofv3 --kernel-trace --pmc passes (FETCH_SIZE / WRITE_SIZE / SQ_INSTS_VALU, one group per pass) "
+                               "spawned by this run around a %d-launch headline-only run of the same configuration; FETCH_SIZE %.2f MB x2 "
+                               "(gfx950 correction) + WRITE_SIZE %.2f MB" % (pt["launches_averaged"], pt["fetch_bytes_raw"] / 1e6, pt["write_bytes_raw"] / 1e6))
+                if pt is None:
+                    pt = json.load(open(os.path.join(ROOT, "profiles", "pmc_traffic.json")))
+                    src = "profiles/pmc_traffic.json (%s): PMC passes of an earlier run of this configuration, not of this run" % pt.get("source", "?")
+                if gpu and pt["num_envs"] == E and pt["nr_max_iter"] == args.max_iter and pt["precision"] == args.precision:
+                    traffic = pt["hbm_bytes_per_launch"]
+                    traffic_source = src
+                    # what really bounds the kernel: fp64 VALU issue.  A wave64 fp64 instruction occupies its
+                    # SIMD for 4 cycles, so the chip issues at most 256 CU x 4 SIMD x 2.4 GHz / 4 of them per s.
+                    peak_issue = 256 * 4 * 2.4e9 / 4
+                    valu = {"wave_instructions_per_launch": pt["valu_wave_insts_per_launch"],
+                            "achieved_per_s": pt["valu_wave_insts_per_launch"] / kernel_s, "peak_per_s": peak_issue,
+                            "frac": pt["valu_wave_insts_per_launch"] / kernel_s / peak_issue,
+                            "note": "chip-wide average; after ~9 iterations only waves holding a diverging solve run"}
+            except Exception:
+                pass
         out = {
             "metric": "env-steps/sec (whole node) at num_envs=%s, ANM6Easy; NR iters to 1e-6"
                       % ("65536" if (scaling == "weak" and E == 65536) else ("%d in total" % (E * world) if scaling == "strong" else "%d per GPU" % E)),
@@ -813,15 +858,16 @@ def main(argv=None, make_env=None, backend="nccl", device_type="cuda", script=No
                                       "solve spends in its own lane before a still-running one continues on a lane "
                                       "group of the same wavefront (-2: library default, -1: never)"},
                 "nr_tol": args.tol, "nr_max_iter": args.max_iter, "nr_start": "flat",
-                "mean_nr_iters": float(iters_sum.item() / 8), "collapsed_per_step": float(term_sum.item() / 8),
             },
             "roofline": {
                 "bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBPS, "unit": "GB/s",
                 "frac": achieved / HBM_PEAK_GBPS, "traffic": traffic, "traffic_source": traffic_source,
                 "kernel": "k_step_rows<double, false>" if args.precision == "f64" else "k_step_rows<float, false>",
                 "kernel_ms": kernel_s * 1e3, "launches_timed": n_launch,
-                "kernel_ms_source": "HIP events on the launch stream around %d launches issued back to back from C "
-                                    "(anm_time_step_launches), live in this run, rank 0's GPU" % n_launch,
+                "kernel_ms_source": ("HIP events on the launch stream around %d launches issued back to back from C "
+                                     "(anm_time_step_launches), live in this run, rank 0's GPU" % n_launch) if gpu and args.full else
+                                    ("HIP events on the launch stream over the %d timed steps (kernel + the caller's gap between "
+                                     "launches), rank 0's GPU; --full times launches issued back to back from C" % n_launch),
                 "step_ms_hip_events": step_events_s * 1e3, "steps_timed": args.steps,
                 "algorithmic_bytes_per_env_step": bytes_per, "valu_fp64_issue": valu,
                 "note": "fp64-ALU/latency-bound (Newton-Raphson in registers), not HBM-bound: see DESIGN.md",
@@ -829,20 +875,23 @@ def main(argv=None, make_env=None, backend="nccl", device_type="cuda", script=No
         }  # fmt: skip
         if not gpu:
             out["config"]["test_double"] = "host test double (CPU tier launcher test): not a measurement"
-        # secondary: algorithmic fp64 flops (per Newton iteration F ~ 8 nnz + 10 n, J ~ 16 nnz + 12 n,
-        # dense LU (2/3)(2n)^3 + 2(2n)^2, sincos n; ANM6: n = 5, nnz = 16 -> ~1.4 kflop, plus the final F)
-        n_, nnz_ = 5, 16
-        per_iter = (8 * nnz_ + 10 * n_) + (16 * nnz_ + 12 * n_) + (2.0 / 3.0) * (2 * n_) ** 3 + 2 * (2 * n_) ** 2 + n_
-        flops = per_iter * out["config"]["mean_nr_iters"] + (8 * nnz_ + 10 * n_)
-        out["roofline"]["fp64_flops"] = {"algorithmic_per_env_step": flops, "achieved_tflops": flops * E / kernel_s / 1e12,
-                                         "peak_tflops": 78.6, "frac": flops * E / kernel_s / 78.6e12}
+        if args.full:
+            out["config"]["mean_nr_iters"] = float(iters_sum.item() / 8)
+            out["config"]["collapsed_per_step"] = float(term_sum.item() / 8)
+            # secondary: algorithmic fp64 flops (per Newton iteration F ~ 8 nnz + 10 n, J ~ 16 nnz + 12 n,
+            # dense LU (2/3)(2n)^3 + 2(2n)^2, sincos n; ANM6: n = 5, nnz = 16 -> ~1.4 kflop, plus the final F)
+            n_, nnz_ = 5, 16
+            per_iter = (8 * nnz_ + 10 * n_) + (16 * nnz_ + 12 * n_) + (2.0 / 3.0) * (2 * n_) ** 3 + 2 * (2 * n_) ** 2 + n_
+            flops = per_iter * out["config"]["mean_nr_iters"] + (8 * nnz_ + 10 * n_)
+            out["roofline"]["fp64_flops"] = {"algorithmic_per_env_step": flops, "achieved_tflops": flops * E / kernel_s / 1e12,
+                                             "peak_tflops": 78.6, "frac": flops * E / kernel_s / 78.6e12}
         if alt is not None:
             out["config"]["alt_iteration_cap"] = alt
         if alt_tol is not None:
             out["config"]["alt_reference_tol"] = alt_tol
         if other is not None:
             out["config"]["other_workloads"] = other
-        if gpu and world == 1 and not args.no_cpu_baseline:
+        if gpu and world == 1 and args.full and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(args.cpu_budget)
         print(json.dumps(out), flush=True)
     comm.close()

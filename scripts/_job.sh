@@ -1,4 +1,6 @@
 cd $GRAFT_REPO_ROOT
-python bench.py > gpurun_out/bench.json 2> gpurun_out/bench.err
-tail -c 300 gpurun_out/bench.json
+out=${1:?usage: bash scripts/_job.sh <output directory>}
+mkdir -p "$out"
+python bench.py --full > "$out"/bench.json 2> "$out"/bench.err
+tail -c 300 "$out"/bench.json
 python -c "import __graft_entry__ as g; g.smoke()" 2>&1 | tail -2

@@ -128,7 +128,9 @@ def test_more_gpus_asked_than_visible_exits_with_one_line_before_spawning():
     res = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "64", "--steps", "1", "--warmup", "0"],
                          capture_output=True, text=True, env=env, timeout=280)
     assert res.returncode != 0 and res.stdout.strip() == ""
-    err = [ln for ln in res.stderr.splitlines() if ln.strip()]
+    # (libdrm's notice that its device-name table is not installed comes from the driver stack when torch counts the
+    # devices, not from bench.py)
+    err = [ln for ln in res.stderr.splitlines() if ln.strip() and not ln.endswith("amdgpu.ids: No such file or directory")]
     assert len(err) == 1 and "--gpus 64 but only" in err[0] and "nothing started" in err[0], res.stderr[-2000:]
 
 
@@ -147,3 +149,11 @@ def test_a_missing_peer_does_not_hang_the_rendezvous():
     assert "did not complete within 4 s" in res.stderr and "a peer rank is missing" in res.stderr, res.stderr[-2000:]
     assert not [ln for ln in res.stdout.splitlines() if ln.startswith("{")]
     assert time.time() - t0 < 200
+
+
+def test_at_least_one_timed_step():
+    """ms_per_step and the outputs of --dump-outputs come from the timed steps: --steps 0 is refused at parse time"""
+    assert bench.parse_args(["--steps", "1"]).steps == 1
+    for argv in (["--steps", "0"], ["--steps", "0", "--dump-outputs", "out"], ["--steps", "-3"]):
+        with pytest.raises(SystemExit):
+            bench.parse_args(argv)

@@ -2,6 +2,8 @@
 Python host layer, against the golden vectors recorded from the reference.  This is what keeps
 the kernel logic, the constant packing and the host code honest when no GPU is present; the GPU
 tier (test_gpu_parity.py) repeats the same checks through the hipcc-built library."""
+import os
+
 import numpy as np
 import pytest
 import torch
@@ -10,9 +12,30 @@ from gym_anm_amd.envs import ANM6EasyVec
 from gym_anm_amd.model import NetworkModel
 
 import parity_common as pc
+from conftest import GOLDEN
 from hostsim_backend import hostsim_backend
 
 NETS = pc.golden_nets()
+REFERENCE_RUNS = os.path.join(GOLDEN, "reference_runs.npz")
+_RECORDING = None  # oracle/make_golden_reference_runs.py puts a dict here: the reference's side then runs live into it
+
+
+def _reference_side(key, run):
+    """The reference's side of a differential test: what `run()` returned on the reference (an array, or a dict of
+    arrays), as oracle/make_golden_reference_runs.py recorded it in tests/golden/reference_runs.npz."""
+    if _RECORDING is not None:
+        import ref_harness
+
+        ref_harness.load_reference()
+        out = run()
+        _RECORDING.update({key + "/" + k: np.asarray(v) for k, v in out.items()} if isinstance(out, dict) else {key: np.asarray(out)})
+        return out
+    with np.load(REFERENCE_RUNS) as z:
+        if key in z.files:
+            return z[key]
+        out = {k[len(key) + 1:]: z[k] for k in z.files if k.startswith(key + "/")}
+    assert out, "no recorded run %s in %s" % (key, REFERENCE_RUNS)
+    return out
 
 
 def _backend(net):
@@ -208,15 +231,19 @@ def _reference_available():
         return False
 
 
-@pytest.mark.skipif(not _reference_available(), reason="reference checkout not present (GPU box)")
+def _plain(x):
+    """`x` with NumPy scalars turned into Python ones (its repr is then a literal)"""
+    if isinstance(x, (list, tuple)):
+        return type(x)(_plain(y) for y in x)
+    return x.item() if isinstance(x, np.generic) else x
+
+
 def test_observation_spaces_of_random_lists_equal_the_reference():
     """Differential test of the observation-spec compiler's host side (anm_env.py:193-233, 497-521): 60 random
     list-form observations (random quantities, 'all' or random ids, every unit) on ANM6 -- same expanded
-    obs_values and bit-identical Box bounds as the reference's ANMEnv.  Dev container only."""
-    import ref_harness
+    obs_values and bit-identical Box bounds as the reference's ANMEnv (recorded: tests/golden/reference_runs.npz)."""
+    import ast
 
-    ref_harness.load_reference()
-    from gym_anm.envs import ANMEnv
     import numpy.testing as npt
     from gym_anm_amd import networks
     from gym_anm_amd.envs.anm_env import BatchedANMEnv
@@ -227,6 +254,7 @@ def test_observation_spaces_of_random_lists_equal_the_reference():
            "branch": [(0, 1), (1, 2), (1, 3), (2, 4), (2, 5)]}
     rng = np.random.default_rng(3)
     keys = [k for k in STATE_VARIABLES if k != "aux"]
+    specs = []
     for case in range(60):
         spec = []
         for key in rng.choice(keys, size=rng.integers(1, 6), replace=False):
@@ -239,37 +267,74 @@ def test_observation_spaces_of_random_lists_equal_the_reference():
                 pick = sorted(rng.choice(len(pool), size=rng.integers(1, len(pool) + 1), replace=False))
                 nodes = [pool[i] for i in pick]
             spec.append((str(key), nodes, str(unit)))
-        ref = ANMEnv(net, [tuple(s) for s in spec], 0, 0.25, 0.995, 100, None, (None, None), None)
+        specs.append(spec)
+
+    def reference():
+        """per case: obs_values (as literals, one after the other, `n` per case) and the Box bounds (`m` per case)"""
+        from gym_anm.envs import ANMEnv
+
+        out = {"obs_values": [], "n": [], "m": [], "low": [], "high": []}
+        for spec in specs:
+            ref = ANMEnv(net, [tuple(s) for s in spec], 0, 0.25, 0.995, 100, None, (None, None), None)
+            out["obs_values"] += [repr(_plain(v)) for v in ref.obs_values]
+            out["n"].append(len(ref.obs_values))
+            out["m"].append(len(ref.observation_space.low))
+            out["low"].append(np.asarray(ref.observation_space.low, dtype=np.float64))
+            out["high"].append(np.asarray(ref.observation_space.high, dtype=np.float64))
+        return {"obs_values": np.array(out["obs_values"]), "n": np.array(out["n"]), "m": np.array(out["m"]), "low": np.concatenate(out["low"]),
+                "high": np.concatenate(out["high"])}
+
+    rec = _reference_side("observation_spaces_of_random_lists", reference)
+    start, box = np.concatenate(([0], np.cumsum(rec["n"]))), np.concatenate(([0], np.cumsum(rec["m"])))
+    for case, spec in enumerate(specs):
+        sl, bx = slice(start[case], start[case + 1]), slice(box[case], box[case + 1])
         env = BatchedANMEnv(net, [tuple(s) for s in spec], 0, 0.25, 0.995, 100, num_envs=2, **_KW(net))
-        assert env.obs_values == ref.obs_values, (case, spec)
-        npt.assert_array_equal(env.observation_space.low, ref.observation_space.low, err_msg=str(spec))
-        npt.assert_array_equal(env.observation_space.high, ref.observation_space.high, err_msg=str(spec))
+        assert env.obs_values == [ast.literal_eval(v) for v in rec["obs_values"][sl].tolist()], (case, spec)
+        npt.assert_array_equal(env.observation_space.low, rec["low"][bx], err_msg=str(spec))
+        npt.assert_array_equal(env.observation_space.high, rec["high"][bx], err_msg=str(spec))
 
 
-@pytest.mark.skipif(not _reference_available(), reason="reference checkout not present (GPU box)")
 @pytest.mark.parametrize("seed", [1, 3, 4])
 def test_list_observation_episode_equals_the_live_reference(seed):
     """ANM6Easy's dynamics with a LIST observation (the committed golden episodes use "state"): the reference's
     environment and the batched one (one environment, host double), same seed and actions, 150 steps with resets --
-    observations, rewards and terminations step by step.  Dev container only."""
+    observations, rewards and terminations step by step (the reference's episode: tests/golden/reference_runs.npz)."""
     import numpy.testing as npt
-    import ref_harness
 
-    ref_harness.load_reference()
-    from gym_anm.envs import ANM6Easy
-    from gym_anm.envs.anm6_env.anm6 import ANM6
     from gym_anm_amd import networks
     from gym_anm_amd.envs.anm6 import ANM6Vec, anm6easy_series, random_date
 
     observation = [("bus_v_magn", "all", "pu"), ("branch_s", [(1, 2), (2, 4)], "MVA"), ("des_soc", "all", "MWh"),
                    ("dev_q", [2, 4, 6], "MVAr"), ("bus_v_ang", [3, 5], "degree"), ("gen_p_max", "all", "MW"), ("aux", "all")]
 
-    class RefTask(ANM6Easy):
-        def __init__(self):
-            ANM6.__init__(self, observation, 1, 0.25, 0.995, 100, np.array([[0, 95]]), (1, 100))
-            from gym_anm.envs.anm6_env.anm6_easy import _get_gen_time_series, _get_load_time_series
+    def reference():
+        """obs after reset(seed); per step: action, obs, reward, terminated, and the obs after the reset that follows a
+        termination (NaN where there was none)"""
+        from gym_anm.envs import ANM6Easy
+        from gym_anm.envs.anm6_env.anm6 import ANM6
 
-            self.P_loads, self.P_maxs = _get_load_time_series(), _get_gen_time_series()
+        class RefTask(ANM6Easy):
+            def __init__(self):
+                ANM6.__init__(self, observation, 1, 0.25, 0.995, 100, np.array([[0, 95]]), (1, 100))
+                from gym_anm.envs.anm6_env.anm6_easy import _get_gen_time_series, _get_load_time_series
+
+                self.P_loads, self.P_maxs = _get_load_time_series(), _get_gen_time_series()
+
+        ref = RefTask()
+        o_ref, _ = ref.reset(seed=seed)
+        out = {"obs0": o_ref, "actions": [], "obs": [], "reward": [], "terminated": [], "reset_obs": []}
+        rng = np.random.default_rng(50 + seed)
+        for t in range(150):
+            a = rng.uniform(ref.action_space.low, ref.action_space.high)
+            if t % 3:
+                a[2:] *= 0.3
+            o_ref, r_ref, term_ref, _, _ = ref.step(a)
+            out["actions"].append(a)
+            out["obs"].append(o_ref)
+            out["reward"].append(r_ref)
+            out["terminated"].append(float(bool(term_ref)))
+            out["reset_obs"].append(ref.reset()[0] if term_ref else np.full(len(o_ref), np.nan))
+        return {k: np.array(v, dtype=np.float64) for k, v in out.items()}
 
     class Task(ANM6EasyVec):
         def __init__(self, **kw):
@@ -277,29 +342,24 @@ def test_list_observation_episode_equals_the_live_reference(seed):
             ANM6Vec.__init__(self, observation, 1, 0.25, 0.995, 100, aux_bounds=np.array([[0, 95]]), costs_clipping=(1, 100),
                              series=anm6easy_series(), **kw)
 
-    ref = RefTask()
+    rec = _reference_side("list_observation_episode_%d" % seed, reference)
     env = Task(num_envs=1, seed=seed, **_KW(networks.anm6_network()))
-    o_ref, _ = ref.reset(seed=seed)
     o, _ = env.reset(seed=seed)
     random_date(env.np_random, 2020)  # ANM6.reset draws the rendering date from np_random (anm6.py:138): the batched
-    npt.assert_allclose(o[0].cpu().numpy(), o_ref, rtol=0, atol=1e-9)  # class leaves that to its NumPy-facing wrapper
-    rng = np.random.default_rng(50 + seed)
+    npt.assert_allclose(o[0].cpu().numpy(), rec["obs0"], rtol=0, atol=1e-9)  # class leaves that to its NumPy-facing wrapper
     n_term = 0
     for t in range(150):
-        a = rng.uniform(ref.action_space.low, ref.action_space.high)
-        if t % 3:
-            a[2:] *= 0.3
-        o_ref, r_ref, term_ref, _, _ = ref.step(a)
+        a = rec["actions"][t]
+        o_ref, r_ref, term_ref = rec["obs"][t], rec["reward"][t], bool(rec["terminated"][t])
         o, r, term, _, _ = env.step(torch.as_tensor(a[None, :]))
         assert bool(term[0]) == bool(term_ref), t
         npt.assert_allclose(o[0].cpu().numpy(), o_ref, rtol=0, atol=1e-7, err_msg="step %d" % t)
         npt.assert_allclose(float(r[0]), r_ref, rtol=1e-9, atol=1e-8)
         if term_ref:
             n_term += 1
-            o_ref, _ = ref.reset()
             o, _ = env.reset()
             random_date(env.np_random, 2020)
-            npt.assert_allclose(o[0].cpu().numpy(), o_ref, rtol=0, atol=1e-9)
+            npt.assert_allclose(o[0].cpu().numpy(), rec["reset_obs"][t], rtol=0, atol=1e-9)
 
 
 def _simple_env_classes(kw):
@@ -350,18 +410,14 @@ def test_reference_example_simple_env_runs_unmodified():
     assert env.state.shape == (5,) and env.timestep == 10
 
 
-@pytest.mark.skipif(not _reference_available(), reason="reference checkout not present (GPU box)")
 def test_reference_example_simple_env_equals_the_live_reference():
-    """... and it walks the same trajectory as the reference's class under the same global NumPy seed."""
+    """... and it walks the same trajectory as the reference's class under the same global NumPy seed (the reference's
+    trajectory: tests/golden/reference_runs.npz)."""
     import numpy.testing as npt
-    import ref_harness
-
-    ref_harness.load_reference()
-    from gym_anm import ANMEnv as Ref
 
     make, Ours, extra = _simple_env_classes(_KW)
-    traj = []
-    for base, ex in ((Ref, {}), (Ours, extra)):
+
+    def run(base, ex):
         env = make(base, ex)()
         np.random.seed(11)
         o, _ = env.reset()
@@ -369,20 +425,23 @@ def test_reference_example_simple_env_equals_the_live_reference():
         for t in range(40):
             o, r, term, _, _ = env.step(env.action_space.sample())
             rows.append(np.concatenate((o, [r, float(term)])))
-        traj.append(np.array(rows))
-    npt.assert_allclose(traj[1], traj[0], rtol=1e-9, atol=1e-9)
+        return np.array(rows)
+
+    def reference():
+        from gym_anm import ANMEnv as Ref
+
+        return run(Ref, {})
+
+    npt.assert_allclose(run(Ours, extra), _reference_side("simple_env", reference), rtol=1e-9, atol=1e-9)
 
 
-@pytest.mark.skipif(not _reference_available(), reason="reference checkout not present (GPU box)")
 def test_reference_example_custom_anm6_equals_the_live_reference():
     """`class CustomANM6Environment(ANM6)` of examples/custom_anm6.py (random loads and generation potentials within
     their limits, time-of-day aux variable), body unchanged, on `gym_anm.envs.ANM6` and on this package's `ANM6`:
-    same trajectory under the same global NumPy seed (random agent from a seeded generator)."""
+    same trajectory under the same global NumPy seed (random agent from a seeded generator; the reference's
+    trajectory: tests/golden/reference_runs.npz)."""
     import numpy.testing as npt
-    import ref_harness
 
-    ref_harness.load_reference()
-    from gym_anm.envs import ANM6 as Ref
     from gym_anm_amd import networks
     from gym_anm_amd.envs import ANM6 as Ours
 
@@ -404,8 +463,7 @@ def test_reference_example_custom_anm6_equals_the_live_reference():
 
         return CustomANM6Environment
 
-    traj = []
-    for base, ex in ((Ref, {}), (Ours, _KW(networks.anm6_network()))):
+    def run(base, ex):
         env = make(base, ex)()
         np.random.seed(3)
         o, _ = env.reset()
@@ -419,21 +477,24 @@ def test_reference_example_custom_anm6_equals_the_live_reference():
             if term:
                 o, _ = env.reset()
                 rows.append(np.concatenate((o, [0.0, 0.0])))
-        traj.append(np.array(rows))
+        return np.array(rows)
+
+    def reference():
+        from gym_anm.envs import ANM6 as Ref
+
+        return run(Ref, {})
+
+    traj = [_reference_side("custom_anm6", reference), run(Ours, _KW(networks.anm6_network()))]
     assert traj[0].shape == traj[1].shape
     npt.assert_allclose(traj[1], traj[0], rtol=1e-9, atol=1e-7)
 
 
-@pytest.mark.skipif(not _reference_available(), reason="reference checkout not present (GPU box)")
 def test_new_env_template_with_callable_observation_and_own_bounds_equals_the_live_reference():
     """examples/new_env_template.py filled in with the optional pieces: a CALLABLE observation (anm_env.py:511-514)
     and an overridden observation_bounds() (anm_env.py:193-233) on the 3-bus loop -- the reference's ANMEnv and this
-    package's, same global NumPy seed."""
+    package's, same global NumPy seed (the reference's trajectory: tests/golden/reference_runs.npz)."""
     import numpy.testing as npt
-    import ref_harness
 
-    ref_harness.load_reference()
-    from gym_anm import ANMEnv as Ref
     from gym_anm_amd import ANMEnv as Ours
     from gym_anm_amd import networks
     from gym_anm_amd.spaces import Box
@@ -459,10 +520,7 @@ def test_new_env_template_with_callable_observation_and_own_bounds_equals_the_li
 
         return CustomEnvironment
 
-    import gymnasium  # the harness's stand-in in the dev container
-
-    traj = []
-    for base, ex, box in ((Ref, {}, gymnasium.spaces.Box), (Ours, _KW(net), Box)):
+    def run(base, ex, box):
         env = make(base, ex, box)()
         np.random.seed(21)
         o, _ = env.reset()
@@ -475,7 +533,16 @@ def test_new_env_template_with_callable_observation_and_own_bounds_equals_the_li
             rows.append(np.concatenate((o, [r, float(term)])))
             if term:
                 break
-        traj.append(np.array(rows))
+        return np.array(rows)
+
+    def reference():
+        import gymnasium  # the reference harness's stand-in
+
+        from gym_anm import ANMEnv as Ref
+
+        return run(Ref, {}, gymnasium.spaces.Box)
+
+    traj = [_reference_side("new_env_template", reference), run(Ours, _KW(net), Box)]
     assert traj[0].shape == traj[1].shape and len(traj[0]) > 5
     npt.assert_allclose(traj[1], traj[0], rtol=1e-9, atol=1e-8)
 
@@ -571,18 +638,15 @@ def test_single_environment_simulator_state_follows_the_steps():
         assert abs(float(env.simulator.devices[6].soc[0]) * 100.0 - o[14]) < 1e-9
 
 
-@pytest.mark.skipif(not _reference_available(), reason="reference checkout not present (GPU box)")
 @pytest.mark.parametrize("kind,n_bus,seed,n_chords", [("mesh", 5, 51, 2), ("radial", 8, 52, 0), ("mesh", 9, 53, 3)])
 def test_random_task_on_a_random_network_equals_the_live_reference(kind, n_bus, seed, n_chords):
     """A task nobody wrote down: random network (several loads, generators, storage units), "state" observation,
     K = 1, exogenous variables drawn from NumPy's global stream within the devices' limits, random agent --
     the reference's ANMEnv and this package's, 60 steps with resets, same trajectory (state layout, device
-    ordering, SoC bookkeeping of several storage units, clipping, terminal handling)."""
+    ordering, SoC bookkeeping of several storage units, clipping, terminal handling; the reference's side:
+    tests/golden/reference_runs.npz)."""
     import numpy.testing as npt
-    import ref_harness
 
-    ref_harness.load_reference()
-    from gym_anm import ANMEnv as Ref
     from gym_anm_amd import ANMEnv as Ours
     from gym_anm_amd import networks
 
@@ -614,11 +678,11 @@ def test_random_task_on_a_random_network_equals_the_live_reference(kind, n_bus, 
 
         return Task
 
-    traj, spaces_ = [], []
-    for base, ex in ((Ref, {}), (Ours, _KW(net))):
+    def run(base, ex):
         env = make(base, ex)()
-        spaces_.append((env.state_N, list(env.state_values), np.asarray(env.observation_space.low), np.asarray(env.observation_space.high),
-                        np.asarray(env.action_space.low), np.asarray(env.action_space.high)))
+        out = {"state_N": env.state_N, "state_values": [repr(v) for v in env.state_values],
+               "obs_low": np.asarray(env.observation_space.low), "obs_high": np.asarray(env.observation_space.high),
+               "act_low": np.asarray(env.action_space.low), "act_high": np.asarray(env.action_space.high)}
         np.random.seed(100 + seed)
         o, _ = env.reset()
         rng = np.random.default_rng(seed)
@@ -630,65 +694,102 @@ def test_random_task_on_a_random_network_equals_the_live_reference(kind, n_bus, 
             if term:
                 o, _ = env.reset()
                 rows.append(np.concatenate((o, [0.0, 0.0])))
-        traj.append(np.array(rows))
-    assert traj[0].shape == traj[1].shape
-    npt.assert_allclose(traj[1], traj[0], rtol=1e-9, atol=1e-7)
-    assert spaces_[0][0] == spaces_[1][0] and spaces_[0][1] == spaces_[1][1]          # state_N, state_values
-    for a, b in zip(spaces_[0][2:], spaces_[1][2:]):                                      # observation and action boxes
-        npt.assert_array_equal(a, b)
+        out["traj"] = np.array(rows)
+        return out
+
+    def reference():
+        from gym_anm import ANMEnv as Ref
+
+        return run(Ref, {})
+
+    ref, ours = _reference_side("random_task_%s%d_s%d" % (kind, n_bus, seed), reference), run(Ours, _KW(net))
+    assert ref["traj"].shape == ours["traj"].shape
+    npt.assert_allclose(ours["traj"], ref["traj"], rtol=1e-9, atol=1e-7)
+    assert int(ref["state_N"]) == ours["state_N"] and list(ref["state_values"]) == ours["state_values"]   # state layout
+    for k in ("obs_low", "obs_high", "act_low", "act_high"):                                              # observation and action boxes
+        npt.assert_array_equal(ref[k], ours[k])
 
 
-@pytest.mark.skipif(not _reference_available(), reason="reference checkout not present (GPU box)")
 @pytest.mark.parametrize("kind,n_bus,seed,n_chords", [("mesh", 6, 61, 2), ("radial", 10, 62, 0)])
 def test_the_whole_state_dictionary_equals_the_live_reference(kind, n_bus, seed, n_chords):
     """`Simulator.transition(...)` with the reference's dict arguments on a random network with mixed base voltages,
     then EVERY entry of `simulator.state[quantity][unit][id]` (simulator.py:551-636: all quantities, all units,
-    kV / kA conversions per bus) against the reference's dictionary."""
-    import numpy.testing as npt
-    import ref_harness
+    kV / kA conversions per bus) against the reference's dictionary (recorded: tests/golden/reference_runs.npz)."""
+    import ast
 
-    ref_harness.load_reference()
-    from gym_anm.simulator import Simulator
+    import numpy.testing as npt
+
     from gym_anm_amd import networks
     from gym_anm_amd.simulator import BatchedSimulator
 
     net = networks.synthetic_meshed_network(n_bus, seed, n_chords) if kind == "mesh" else networks.synthetic_radial_network(n_bus, seed)
     net = dict(net, bus=np.array(net["bus"], dtype=float).copy())
     net["bus"][1:, 2] = [33.0 if i % 2 else 11.0 for i in range(1, n_bus)]       # mixed base voltages
-    ref = Simulator(net, 0.25, 100)
     sim = BatchedSimulator(net, 0.25, 100, num_envs=2, **_KW(net))
     m = sim.model
-    rng = np.random.default_rng(seed)
     b = m.baseMVA
     loads = [m.dev_ids[k] for k in m.load_idx]
     gens = [m.dev_ids[k] for k in m.gen_idx]
     setp = [m.dev_ids[k] for k in m.setp_idx]
+
+    def trials():
+        rng = np.random.default_rng(seed)
+        for trial in range(6):
+            P_load = {i: float(rng.uniform(0.6 * m.dev_p_min[m.dev_ids.index(i)] * b, 0.0)) for i in loads}
+            P_pot = {i: float(rng.uniform(0.0, m.dev_p_max[m.dev_ids.index(i)] * b)) for i in gens}
+            P_set = {i: float(rng.uniform(0.3 * m.dev_p_min[m.dev_ids.index(i)] * b, 0.3 * m.dev_p_max[m.dev_ids.index(i)] * b)) for i in setp}
+            Q_set = {i: float(rng.uniform(0.3 * m.dev_q_min[m.dev_ids.index(i)] * b, 0.3 * m.dev_q_max[m.dev_ids.index(i)] * b)) for i in setp}
+            soc = rng.uniform(0.2, 0.8, m.N_des) * np.array([m.dev_soc_max[k] for k in m.des_idx])
+            yield P_load, P_pot, P_set, Q_set, soc
+
+    def reference():
+        """per trial: converged, reward, e_loss, penalty; the state dictionary's (quantity, unit) pairs, and its entries as
+        (trial, quantity, unit, repr(id)) -> value"""
+        from gym_anm.simulator import Simulator
+
+        ref = Simulator(net, 0.25, 100)
+        out = {"head": [], "units": [], "names": [], "values": []}
+        for trial, (P_load, P_pot, P_set, Q_set, soc) in enumerate(trials()):
+            for j, k in enumerate(m.des_idx):
+                ref.devices[m.dev_ids[k]].soc = float(soc[j])
+            _, r_ref, e_ref, p_ref, conv_ref = ref.transition(P_load, P_pot, P_set, Q_set)
+            out["head"].append([float(bool(conv_ref)), r_ref, e_ref, p_ref])
+            for key, per_unit in ref.state.items():
+                for unit, per_id in per_unit.items():
+                    if trial == 0:
+                        out["units"].append([key, unit])
+                    for i, v in per_id.items():
+                        out["names"].append([str(trial), key, unit, repr(tuple(map(int, i)) if isinstance(i, tuple) else int(i))])
+                        out["values"].append(v)
+        return {k: np.array(v) for k, v in out.items()}
+
+    rec = _reference_side("state_dictionary_%s%d_s%d" % (kind, n_bus, seed), reference)
+    recorded = [{} for _ in range(6)]
+    for d in recorded:
+        for key, unit in rec["units"].tolist():
+            d.setdefault(key, {})[unit] = {}
+    for (trial, key, unit, i), v in zip(rec["names"].tolist(), rec["values"].tolist()):
+        recorded[int(trial)].setdefault(key, {}).setdefault(unit, {})[ast.literal_eval(i)] = v
     n_checked = 0
-    for trial in range(6):
-        P_load = {i: float(rng.uniform(0.6 * m.dev_p_min[m.dev_ids.index(i)] * b, 0.0)) for i in loads}
-        P_pot = {i: float(rng.uniform(0.0, m.dev_p_max[m.dev_ids.index(i)] * b)) for i in gens}
-        P_set = {i: float(rng.uniform(0.3 * m.dev_p_min[m.dev_ids.index(i)] * b, 0.3 * m.dev_p_max[m.dev_ids.index(i)] * b)) for i in setp}
-        Q_set = {i: float(rng.uniform(0.3 * m.dev_q_min[m.dev_ids.index(i)] * b, 0.3 * m.dev_q_max[m.dev_ids.index(i)] * b)) for i in setp}
-        soc = rng.uniform(0.2, 0.8, m.N_des) * np.array([m.dev_soc_max[k] for k in m.des_idx])
-        for j, k in enumerate(m.des_idx):
-            ref.devices[m.dev_ids[k]].soc = float(soc[j])
+    for trial, (P_load, P_pot, P_set, Q_set, soc) in enumerate(trials()):
+        conv_ref, r_ref, e_ref, p_ref = rec["head"][trial]
+        ref_state = recorded[trial]
         sim.soc[:] = torch.as_tensor(soc)
-        _, r_ref, e_ref, p_ref, conv_ref = ref.transition(P_load, P_pot, P_set, Q_set)
         st, r, e, p, conv = sim.transition(P_load, P_pot, P_set, Q_set)
         assert bool(conv[0]) == bool(conv_ref)
         if not conv_ref:
             continue
         npt.assert_allclose([float(r[0]), float(e[0]), float(p[0])], [r_ref, e_ref, p_ref], rtol=1e-9, atol=1e-9)
-        assert set(st.keys()) == set(ref.state.keys())
-        for key in ref.state:
+        assert set(st.keys()) == set(ref_state.keys())
+        for key in ref_state:
             ours = st[key]
-            assert set(ours.keys()) == set(ref.state[key].keys()), key
-            for unit, per_id in ref.state[key].items():
+            assert set(ours.keys()) == set(ref_state[key].keys()), key
+            for unit, per_id in ref_state[key].items():
                 assert list(ours[unit].keys()) == list(per_id.keys()), (key, unit)
                 for i, v in per_id.items():
                     atol = 1e-9
                     if key.endswith("_ang"):  # the angle of a small phasor is ill-conditioned: 1e-9 on the phasor itself
-                        mag = abs(ref.state[key.replace("_ang", "_magn")]["pu"][i])
+                        mag = abs(ref_state[key.replace("_ang", "_magn")]["pu"][i])
                         if mag < 1e-9:   # a bus nothing is injected at: the angle of rounding noise
                             continue
                         atol = min(1e-4, 1e-9 / mag) * (180.0 / np.pi if unit == "degree" else 1.0)
@@ -697,14 +798,10 @@ def test_the_whole_state_dictionary_equals_the_live_reference(kind, n_bus, seed,
     assert n_checked > 500
 
 
-@pytest.mark.skipif(not _reference_available(), reason="reference checkout not present (GPU box)")
 def test_bad_observation_specs_fail_like_the_live_reference():
     """Observation arguments the reference refuses (anm_env.py:497-545, 193-233): same exception class at
-    construction, or -- where the reference only fails later, in reset() -- a failure at the same stage."""
-    import ref_harness
-
-    ref_harness.load_reference()
-    from gym_anm import ANMEnv as Ref
+    construction, or -- where the reference only fails later, in reset() -- a failure at the same stage (the
+    reference's outcomes: tests/golden/reference_runs.npz)."""
     from gym_anm_amd import ANMEnv as Ours
     from gym_anm_amd import networks
 
@@ -741,10 +838,15 @@ def test_bad_observation_specs_fail_like_the_live_reference():
             env.reset()
         except Exception as e:  # noqa: BLE001
             return "reset", type(e).__name__
-        return "ok", None
+        return "ok", ""
 
-    for obs in bad:
-        r, o = outcome(Ref, obs, {}), outcome(Ours, obs, extra)
+    def reference():
+        from gym_anm import ANMEnv as Ref
+
+        return np.array([outcome(Ref, obs, {}) for obs in bad])
+
+    for obs, r in zip(bad, _reference_side("bad_observation_specs", reference).tolist()):
+        o = outcome(Ours, obs, extra)
         assert r[0] != "ok", obs
         assert o[0] == r[0], (obs, r, o)
         if r[1] not in ("KeyError", "TypeError", "IndexError", "ValueError", "AttributeError"):   # the reference's own classes

@@ -3,8 +3,10 @@
 * known answers of the reference's own tests, restated as data
   (tests/simulator/test_simulator_basics.py:35-46, 69-174; test_network_checks.py; test_bus.py;
   test_branch.py; test_devices.py spec errors);
-* when the reference is importable (dev container), a direct cross-check of every constant against
-  the reference's Simulator objects for several networks (bit-exact)."""
+* every constant against what the reference's Simulator objects hold for several networks and for 400
+  mutated ones (bit-exact), recorded in tests/golden/reference_constants.npz by oracle/make_golden_constants.py."""
+import os
+
 import numpy as np
 import numpy.testing as npt
 import pytest
@@ -12,6 +14,8 @@ import pytest
 from gym_anm_amd import errors as E
 from gym_anm_amd import networks
 from gym_anm_amd.model import NetworkModel
+
+from conftest import GOLDEN
 
 _N = None
 
@@ -168,71 +172,87 @@ def test_defaults_and_flex_constants():
     assert m.dev_p_max[1] == np.inf and m.dev_p_min[1] == 0.0 and m.dev_q_min[1] == -np.inf
 
 
-def _reference_available():
-    try:
-        import ref_harness
-
-        return ref_harness.reference_available()
-    except Exception:
-        return False
+def _reference_constants():
+    """tests/golden/reference_constants.npz (oracle/make_golden_constants.py): what the reference's Simulator made of
+    the stock networks and of the mutated ones"""
+    with np.load(os.path.join(GOLDEN, "reference_constants.npz")) as z:
+        return {k: z[k] for k in z.files}
 
 
-def _assert_same_constants(m, ref):
-    from gym_anm.simulator.components import Generator, StorageUnit
+def _recorded(z, case):
+    """the fields of one stock network `case` of `_reference_constants()`"""
+    r = {k[len(case) + 1:]: v for k, v in z.items() if k.startswith(case + "/")}
+    assert r, "no case %s in reference_constants.npz" % case
+    return r
+
+
+def _recorded_mutations(z):
+    """(the exception class each of the 400 mutated networks raised in the reference, "" where it was accepted; the
+    fields of every accepted network, in order)"""
+    lens = {k[len("mutations/"):-len("_len")]: v for k, v in z.items() if k.startswith("mutations/") and k.endswith("_len")}
+    n = {len(v) for v in lens.values()}
+    assert len(n) == 1, "packed fields of different network counts: %r" % n
+    ends = {k: np.concatenate(([0], np.cumsum(v))) for k, v in lens.items()}
+    accepted = [{k: z["mutations/" + k][e[j]:e[j + 1]] for k, e in ends.items()} for j in range(n.pop())]
+    return z["mutations/exception"].tolist(), accepted
+
+
+def _assert_same_constants(m, r):
+    """`m` against the reference's recorded constants `r` (`_recorded`)"""
+    import ast
 
     def eq(x, y):  # bit-equal, NaN == NaN (what a degenerate but accepted spec yields on both sides)
         return x == y or (x != x and y != y)
 
-    npt.assert_array_equal(m.Y_bus, ref.Y_bus.toarray())
-    assert m.bus_ids == list(ref.buses.keys()) and m.dev_ids == list(ref.devices.keys())
-    assert m.branch_ids == list(ref.branches.keys())
-    for k, d in enumerate(ref.devices.values()):
-        for a, b in ((m.dev_p_min[k], d.p_min), (m.dev_p_max[k], d.p_max), (m.dev_q_min[k], d.q_min), (m.dev_q_max[k], d.q_max)):
+    npt.assert_array_equal(m.Y_bus, r["Y_bus"])
+    assert m.bus_ids == r["bus_ids"].tolist() and m.dev_ids == r["dev_ids"].tolist()
+    assert m.branch_ids == [tuple(b) for b in r["branch_ids"].tolist()]
+    for k, kind in enumerate(r["dev_kind"].tolist()):
+        for a, b in ((m.dev_p_min[k], r["dev_p_min"][k]), (m.dev_p_max[k], r["dev_p_max"][k]), (m.dev_q_min[k], r["dev_q_min"][k]),
+                     (m.dev_q_max[k], r["dev_q_max"][k])):
             assert eq(a, b)
-        if isinstance(d, (Generator, StorageUnit)):
-            assert eq(m.dev_tau[k, 0], d.tau_1) and eq(m.dev_tau[k, 1], d.tau_2)
-            assert eq(m.dev_rho[k, 0], d.rho_1) and eq(m.dev_rho[k, 1], d.rho_2)
-        if isinstance(d, StorageUnit):
-            assert eq(m.dev_tau[k, 2], d.tau_3) and eq(m.dev_tau[k, 3], d.tau_4)
-            assert eq(m.dev_rho[k, 2], d.rho_3) and eq(m.dev_rho[k, 3], d.rho_4)
-            assert (m.dev_soc_min[k], m.dev_soc_max[k], m.dev_eff[k]) == (d.soc_min, d.soc_max, d.eff)
-    for k, b in enumerate(ref.branches.values()):
-        assert m.br_series[k] == b.series and m.br_shunt[k] == b.shunt and m.br_tap[k] == b.tap and m.br_rate[k] == b.rate
-    # nested bounds dictionaries
-    rb, mb = ref.state_bounds, m.state_bounds()
+        if kind in (1, 2):  # generator, storage unit
+            assert eq(m.dev_tau[k, 0], r["tau"][k, 0]) and eq(m.dev_tau[k, 1], r["tau"][k, 1])
+            assert eq(m.dev_rho[k, 0], r["rho"][k, 0]) and eq(m.dev_rho[k, 1], r["rho"][k, 1])
+        if kind == 2:  # storage unit
+            assert eq(m.dev_tau[k, 2], r["tau"][k, 2]) and eq(m.dev_tau[k, 3], r["tau"][k, 3])
+            assert eq(m.dev_rho[k, 2], r["rho"][k, 2]) and eq(m.dev_rho[k, 3], r["rho"][k, 3])
+            assert (m.dev_soc_min[k], m.dev_soc_max[k], m.dev_eff[k]) == tuple(r["soc"][k])
+    for k in range(len(r["br_rate"])):
+        assert (m.br_series[k] == r["br_series"][k] and m.br_shunt[k] == r["br_shunt"][k] and m.br_tap[k] == r["br_tap"][k]
+                and m.br_rate[k] == r["br_rate"][k])
+    # nested bounds dictionaries (the reference's state_bounds, recorded flat in its own order)
+    rb = {q: {} for q in r["sb_quantities"].tolist()}
+    for q, i in r["sb_ids"].tolist():
+        rb[q][ast.literal_eval(i)] = {}
+    for (q, i, unit), (lo, hi) in zip(r["sb_units"].tolist(), r["sb_lohi"].tolist()):
+        rb[q][ast.literal_eval(i)][unit] = (lo, hi)
+    mb = m.state_bounds()
     assert set(rb) == set(mb)
     for q in rb:
         assert list(rb[q].keys()) == list(mb[q].keys()), q
         for i in rb[q]:
             for unit, (lo, hi) in rb[q][i].items():
                 assert eq(mb[q][i][unit][0], lo) and eq(mb[q][i][unit][1], hi), (q, i, unit)
-    P_gen, Q_gen, P_des, Q_des = ref.get_action_space()
     lo, hi = m.action_bounds()
-    ref_lo = [v[0] for x in (P_gen, Q_gen, P_des, Q_des) for _, v in sorted(x.items())]
-    ref_hi = [v[1] for x in (P_gen, Q_gen, P_des, Q_des) for _, v in sorted(x.items())]
-    npt.assert_array_equal(lo, ref_lo)
-    npt.assert_array_equal(hi, ref_hi)
+    npt.assert_array_equal(lo, r["act_lo"])
+    npt.assert_array_equal(hi, r["act_hi"])
 
 
-@pytest.mark.skipif(not _reference_available(), reason="reference checkout not present (GPU box)")
-@pytest.mark.parametrize("which", ["anm6", "basics", "3bus_tx", "case30", "2bus"])
-def test_constants_bit_identical_to_reference(which):
-    import ref_harness
-
-    ref_harness.load_reference()
-    from gym_anm.simulator import Simulator
-    from gym_anm.simulator.components import Generator, StorageUnit
-
-    net = {
+def stock_networks():
+    return {
         "anm6": networks.anm6_network(),
         "basics": basics_network(),
         "3bus_tx": networks.three_bus_loop_network(1.0437, 23.1),
         "case30": networks.synthetic_radial_network(30, 0),
         "2bus": networks.two_bus_network(),
-    }[which]
-    ref = Simulator(net, 0.25, 100)
-    m = NetworkModel(net, 0.25, 100, require_solvable=False)
-    _assert_same_constants(m, ref)
+    }
+
+
+@pytest.mark.parametrize("which", ["anm6", "basics", "3bus_tx", "case30", "2bus"])
+def test_constants_bit_identical_to_reference(which):
+    m = NetworkModel(stock_networks()[which], 0.25, 100, require_solvable=False)
+    _assert_same_constants(m, _recorded(_reference_constants(), which))
 
 
 BUILTIN_CRASHES = ("TypeError", "KeyError", "IndexError", "ValueError", "AttributeError", "ZeroDivisionError", "UnboundLocalError")
@@ -264,25 +284,19 @@ def _mutations(rng, n):
         yield net
 
 
-@pytest.mark.skipif(not _reference_available(), reason="reference checkout not present (GPU box)")
 def test_front_end_agrees_with_the_reference_on_mutated_networks():
     """Differential test of the network-dict front end: 400 random single-field mutations of a
-    valid network go through the reference's Simulator and through NetworkModel; both must accept or both must
-    raise, with the same exception class (check_network.py:7-64, components/*.py); accepted networks give
-    bit-identical Y_bus, device limits, tau / rho, storage constants, branch constants, state bounds and action box."""
-    import ref_harness
-
-    ref_harness.load_reference()
-    from gym_anm.simulator import Simulator
-
+    valid network, against what the reference's Simulator made of each (tests/golden/reference_constants.npz,
+    oracle/make_golden_constants.py); both must accept or both must raise, with the same exception class
+    (check_network.py:7-64, components/*.py); accepted networks give bit-identical Y_bus, device limits, tau / rho,
+    storage constants, branch constants, state bounds and action box."""
+    ref_excs, ref_accepted = _recorded_mutations(_reference_constants())
+    assert len(ref_excs) == 400 and ref_excs.count("") == len(ref_accepted), "stale reference_constants.npz"
     rng = np.random.default_rng(12)
     n_ok = n_err = 0
-    for net in _mutations(rng, 400):
-        ref_exc = got_exc = None
-        try:
-            ref = Simulator(net, 0.25, 100)
-        except Exception as ex:  # noqa: BLE001
-            ref_exc = type(ex).__name__
+    for i, net in enumerate(_mutations(rng, 400)):
+        ref_exc, got_exc = ref_excs[i] or None, None
+        ref = ref_accepted[ref_excs[:i].count("")] if ref_exc is None else None   # the reference's constants of this network
         try:
             m = NetworkModel(net, 0.25, 100, require_solvable=False)
         except Exception as ex:  # noqa: BLE001

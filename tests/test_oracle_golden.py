@@ -7,7 +7,6 @@ Sources of truth, in order:
    tests/simulator/test_devices.py:74-97, 269-295, 456-492, 523-562 (device maps).
 """
 import os
-import sys
 
 import numpy as np
 import numpy.testing as npt
@@ -258,29 +257,27 @@ def test_known_reward():
     npt.assert_allclose(pen, lamb * dt * (0.2 + 30 / base), rtol=1e-12)
 
 
-def _reference_available():
-    try:
-        import ref_harness
+def _random_net_case(fixture, kind, n_bus, seed, n_chords):
+    """(network, recorded reference outputs) of one case of oracle/make_golden_random_nets.py"""
+    net = networks.synthetic_meshed_network(n_bus, seed, n_chords) if kind == "mesh" else networks.synthetic_radial_network(n_bus, seed)
+    prefix = "%s%d_s%d/" % (kind, n_bus, seed)
+    with np.load(os.path.join(GOLDEN, fixture)) as z:
+        g = {k[len(prefix):]: z[k] for k in z.files if k.startswith(prefix)}
+    assert g, "no case %s in %s" % (prefix, fixture)
+    return net, g
 
-        return ref_harness.reference_available()
-    except Exception:
-        return False
 
-
-@pytest.mark.skipif(not _reference_available(), reason="reference checkout not present (GPU box)")
 @pytest.mark.parametrize("kind,n_bus,seed,n_chords", [("mesh", 4, 31, 1), ("mesh", 7, 32, 2), ("mesh", 11, 33, 4), ("mesh", 16, 34, 3),
                                                       ("radial", 9, 35, 0), ("radial", 18, 36, 0), ("mesh", 30, 37, 6)])
 def test_oracle_against_the_live_reference_on_random_networks(kind, n_bus, seed, n_chords):
-    """Beyond the committed golden vectors: the oracle and the UNMODIFIED reference, run side by side on random
-    networks nobody recorded (loops, line charging, a phase shifter; feeders) -- same flags and iteration counts,
-    electrical state, SoC and reward to 1e-9.  Dev container only (the reference does not travel)."""
-    sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "oracle"))
-    import make_golden as MG
-
-    net = networks.synthetic_meshed_network(n_bus, seed, n_chords) if kind == "mesh" else networks.synthetic_radial_network(n_bus, seed)
-    P_load, P_pot, P_set, Q_set, soc0 = MG.random_inputs(net, 0.25, 100, 24, seed, wild_frac=0.15)
-    g = MG.run_transitions(net, 0.25, 100, P_load, P_pot, P_set, Q_set, soc0)
+    """Beyond the golden vectors of the stock networks: the oracle against the UNMODIFIED reference on random networks
+    (loops, line charging, a phase shifter; feeders), recorded by oracle/make_golden_random_nets.py
+    (tests/golden/random_nets_transitions.npz) -- same flags and iteration counts, electrical state, SoC and reward to
+    1e-9."""
+    net, g = _random_net_case("random_nets_transitions.npz", kind, n_bus, seed, n_chords)
+    P_load, P_pot, P_set, Q_set, soc0 = g["P_load"], g["P_pot"], g["P_set"], g["Q_set"], g["soc0"]
     n = O.parse_network(net, 0.25, 100)
+    npt.assert_array_equal(n.Y, g["Y_bus"])
     n_conv = 0
     for m in range(len(g["n_iter"])):
         out = O.transition(n, P_load[m], P_pot[m], P_set[m], Q_set[m], soc0[m], sparse=(m % 2 == 0))
@@ -297,16 +294,12 @@ def test_oracle_against_the_live_reference_on_random_networks(kind, n_bus, seed,
     assert n_conv >= 12
 
 
-@pytest.mark.skipif(not _reference_available(), reason="reference checkout not present (GPU box)")
 @pytest.mark.parametrize("kind,n_bus,seed,n_chords", [("mesh", 6, 41, 2), ("radial", 12, 42, 0), ("mesh", 20, 43, 5)])
 def test_oracle_reset_against_the_live_reference_on_random_networks(kind, n_bus, seed, n_chords):
-    """Simulator.reset(init_state) (simulator.py:225-293: SoC pre-set, one transition, SoC overwrite) -- oracle and
-    live reference side by side on random networks and initial states, infeasible ones included."""
-    sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "oracle"))
-    import make_golden as MG
-
-    net = networks.synthetic_meshed_network(n_bus, seed, n_chords) if kind == "mesh" else networks.synthetic_radial_network(n_bus, seed)
-    g = MG.run_resets(net, 0.25, 100, 24, seed)
+    """Simulator.reset(init_state) (simulator.py:225-293: SoC pre-set, one transition, SoC overwrite) -- the oracle
+    against the reference's recorded resets on random networks and initial states, infeasible ones included
+    (oracle/make_golden_random_nets.py: tests/golden/random_nets_resets.npz)."""
+    net, g = _random_net_case("random_nets_resets.npz", kind, n_bus, seed, n_chords)
     n = O.parse_network(net, 0.25, 100)
     n_conv = 0
     for m in range(len(g["n_iter"])):
