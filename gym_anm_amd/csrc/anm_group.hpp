@@ -24,11 +24,10 @@
 #include "anm_device.hpp"
 
 #if defined(__HIPCC__)
-#ifndef ANM_LDSX_FETCH
-#define ANM_LDSX_FETCH 3   // child slots a parent lane fetches from LDS before folding them (LDS hand-overs)
-#endif
 namespace anm {
 namespace group {
+
+constexpr int LDSX_FETCH = 3;   // child slots a parent lane fetches from LDS before folding them (LDS hand-overs)
 
 // llvm CmpInst predicate codes taken by __builtin_amdgcn_{fcmp,uicmp,sicmp}: they return the compare as a
 // 64-bit lane mask in scalar registers (no bool -> ballot round trip)
@@ -46,9 +45,6 @@ enum : int { FCMP_UNO = 8, FCMP_UGT = 10, ICMP_EQ = 32, ICMP_NE = 33, ICMP_SLT =
 // Every lane of the wavefront must be executing at a hand-over.
 // ---------------------------------------------------------------------------------------------
 __device__ __forceinline__ double bperm(double x, int src4) {
-#ifdef ANM_GROUP_FAKE_XFER  // timing experiment only (wrong results): what the trips cost without the hand-overs
-  return x + double(src4) * 1e-300;
-#endif
   const int lo = __builtin_amdgcn_ds_bpermute(src4, __double2loint(x));
   const int hi = __builtin_amdgcn_ds_bpermute(src4, __double2hiint(x));
   return __hiloint2double(hi, lo);
@@ -332,21 +328,12 @@ constexpr int hyb_slot_base(int h) {
 // through LDS -- a lane PUBLISHES what its parent (or its children) will need in its own slot, the consumer reads
 // the slot of the lane it needs -- instead of ds_bpermute: a pair of doubles is one 16-byte write / read instead of
 // four bpermutes, and the 5 child slots x 6 values of a bushy level cost 15 reads instead of 60 bpermutes.
-#ifndef ANM_GROUP_MERGED_REGIONS
-#define ANM_GROUP_MERGED_REGIONS 1
-#endif
-#ifndef ANM_HYB_LIGHT_ALL
-#define ANM_HYB_LIGHT_ALL 1
-#endif
-#ifndef ANM_LDSX_BS_ALL
-#define ANM_LDSX_BS_ALL 1
-#endif
 // Padding lanes never publish; their slots hold the neutral values (zeroed here, V = 1).
 // MERGED = false: the loop as it stood before the instruction-count cuts of round 6 (one region per fold, predicated child
 // sums, no copies): 21 registers fewer -- what the radial kernel with per-group classes needs on a tree with a DPP plan to keep
 // three wavefronts per SIMD.
-template <class T, class JT, int EARLY_EXIT_TRIPS = 0, bool LDSX = false, int FETCH = ANM_LDSX_FETCH, bool WFREE = true, bool VPOLY = !LDSX,
-          bool MERGED = (ANM_GROUP_MERGED_REGIONS != 0), bool REDUCE_ALWAYS = false>
+template <class T, class JT, int EARLY_EXIT_TRIPS = 0, bool LDSX = false, int FETCH = LDSX_FETCH, bool WFREE = true, bool VPOLY = !LDSX,
+          bool MERGED = true>
 __device__ __forceinline__ void newton_groups(const LaneView<T>& V, bool gvalid, double& vm, double& cs, double& sn,
                                               double bus_p, double bus_q, int& it, unsigned& tb, unsigned& tn,
                                               double tol, int max_iter, double* xl = nullptr) {
@@ -354,11 +341,10 @@ __device__ __forceinline__ void newton_groups(const LaneView<T>& V, bool gvalid,
   static_assert(!LDSX || T::T_DPP == 0, "LDS hand-overs are the alternative to ds_bpermute, not to DPP moves");
   [[maybe_unused]] const int wl = threadIdx.x & 63;
   [[maybe_unused]] const int pl = X.psrc4 >> 2;                       // lane of the parent (or a padding lane)
-  // LDS variant, back substitution without regions (ANM_LDSX_BS_ALL): every lane recomputes its step at every level -- from
-  // its own level on its parent's step is final, so it recomputes the same value -- and a bus that hangs off the slack reads
-  // a step of zero: the W slot of a padding lane (its admittances are zero), 64 slots behind the V slots.
-  constexpr bool BS_ALL = LDSX && ANM_LDSX_BS_ALL != 0;
-  [[maybe_unused]] const int plb = (BS_ALL && V.depth == 0) ? 64 + pl : pl;
+  // LDS variant, back substitution without regions: every lane recomputes its step at every level -- from its own level on
+  // its parent's step is final, so it recomputes the same value -- and a bus that hangs off the slack reads a step of zero:
+  // the W slot of a padding lane (its admittances are zero), 64 slots behind the V slots.
+  [[maybe_unused]] const int plb = V.depth == 0 ? 64 + pl : pl;
   [[maybe_unused]] int cl[T::T_MAXCH > 0 ? T::T_MAXCH : 1];           // lanes of the children (or a padding lane)
   static_for<0, T::T_MAXCH>([&](auto Cc) { cl[Cc] = X.csrc4[Cc] >> 2; });
   // LDS hand-overs: what a lane publishes sits TOGETHER in its slot -- (re, im) pairs and the six values a parent folds
@@ -411,14 +397,13 @@ __device__ __forceinline__ void newton_groups(const LaneView<T>& V, bool gvalid,
     unsigned long long runm = __builtin_amdgcn_uicmp(gvalid ? 1u : 0u, 0u, ICMP_NE);
     const unsigned glo = unsigned(gmask & busm), ghi = unsigned((gmask & busm) >> 32);   // bus lanes of my group
     tb = 0u; tn = 0u;
-    [[maybe_unused]] const unsigned fbus1 = isbus ? 1u : 0u, fbus3 = isbus ? 3u : 0u;
     it -= gvalid ? 1 : 0;        // the first trip only evaluates: its `it += running` is undone here
     // What a lane publishes for its parent (Schur complement, reduced right-hand side) and its Newton step:
     // a bus lane rewrites them at its own level of every trip before anybody reads them; a padding lane never
     // does, so these zeros are the neutral values the hand-overs rely on.
     Blk<JT> Sc = Blk<JT>{JT(0), JT(0), JT(0), JT(0)};
     JT Lr0 = JT(0), Lr1 = JT(0), d0 = JT(0), d1 = JT(0);
-    constexpr bool ROOT_STEP_IN_PIVOT = !LDSX && !(LDSX && T::T_HYB != 0) && T::T_LP_NW > 0 && MERGED;
+    constexpr bool ROOT_STEP_IN_PIVOT = !LDSX && T::T_LP_NW > 0 && MERGED;
     constexpr bool WSUM_FREE = WFREE && !LDSX && MERGED && T::T_MAXCH > 0 && child_moves_land_on_parents_or_zero<T>();
     constexpr bool WSUM_ONE = WSUM_FREE && child_moves_write_the_same_lanes<T>();
     [[maybe_unused]] double wr[T::T_MAXCH > 0 ? T::T_MAXCH : 1] = {0.0}, wi[T::T_MAXCH > 0 ? T::T_MAXCH : 1] = {0.0};
@@ -477,26 +462,8 @@ __device__ __forceinline__ void newton_groups(const LaneView<T>& V, bool gvalid,
       const double fr = sr - bus_p, fi = si - bus_q;
       // group-wide stop test: "||F||inf > tol" and "F has a NaN" are all the reference's loop and flags need.
       // A group that has stopped keeps evaluating the same frozen iterate, so what the last trip computed
-      // is also each group's final verdict: nothing but `runm` and `it` is carried over.
-#ifndef ANM_GROUP_FLAG_OR
-#define ANM_GROUP_FLAG_OR 0   // (measured, same box: headline kernel 74.7 us without, 79.2 us with -- the butterfly sits on the exit chain)
-#endif
-      constexpr bool FLAG_OR = ANM_GROUP_FLAG_OR != 0 && !LDSX && MERGED && T::T_DPP != 0 && (T::GRP == 8 || T::GRP == 16);
-      if constexpr (FLAG_OR) {
-        // the two verdicts as bits of one word per bus lane (1: above the tolerance or NaN, 2: NaN; a padding lane: 0), OR-ed
-        // over the group by a butterfly of DPP-operand v_or_b32 (quad swaps, half-row mirror, row mirror for 16 lanes): every
-        // lane then holds its group's verdict, and "keeps iterating" is the one comparison  verdict == 1
-        const bool bad = !(fmax(fabs(fr), fabs(fi)) <= tol), nan = !(fr == fr) || !(fi == fi);
-        unsigned f = bad ? fbus1 : 0u;
-        f = nan ? fbus3 : f;
-        f |= unsigned(__builtin_amdgcn_update_dpp(0, int(f), 0xB1, 0xF, 0xF, true));    // quad_perm [1,0,3,2]
-        f |= unsigned(__builtin_amdgcn_update_dpp(0, int(f), 0x4E, 0xF, 0xF, true));    // quad_perm [2,3,0,1]
-        f |= unsigned(__builtin_amdgcn_update_dpp(0, int(f), 0x141, 0xF, 0xF, true));   // row_half_mirror
-        if constexpr (T::GRP == 16) f |= unsigned(__builtin_amdgcn_update_dpp(0, int(f), 0x140, 0xF, 0xF, true));   // row_mirror
-        tb = f & 1u; tn = f & 2u;
-        it += __builtin_amdgcn_inverse_ballot_w64(runm) ? 1 : 0;   // the update applied in the previous trip
-        runm &= __builtin_amdgcn_uicmp(f, 1u, ICMP_EQ) & __builtin_amdgcn_sicmp(it, max_iter, ICMP_SLT);
-      } else {
+      // is also each group's final verdict: nothing but `runm` and `it` is carried over.  (The verdict OR-ed over the group
+      // by a butterfly of DPP-operand v_or_b32 instead: headline kernel 74.7 -> 79.2 us, same box -- it sits on the exit chain.)
       const unsigned long long badm = __builtin_amdgcn_fcmp(fmax(fabs(fr), fabs(fi)), tol, FCMP_UGT);
       const unsigned long long nanm = __builtin_amdgcn_fcmp(fr, fi, FCMP_UNO);
       tb = (unsigned(badm) & glo) | (unsigned(badm >> 32) & ghi);
@@ -504,7 +471,6 @@ __device__ __forceinline__ void newton_groups(const LaneView<T>& V, bool gvalid,
       it += __builtin_amdgcn_inverse_ballot_w64(runm) ? 1 : 0;   // the update applied in the previous trip
       runm &= __builtin_amdgcn_uicmp(tb, 0u, ICMP_NE) & ~__builtin_amdgcn_uicmp(tn, 0u, ICMP_NE) &
               __builtin_amdgcn_sicmp(it, max_iter, ICMP_SLT);   // NaN > tol is false, like the reference
-      }
       // The loop is left at the END of the trip: the scalar chain compare -> masks -> branch then overlaps the
       // elimination instead of stalling the wavefront in front of it every trip (what counts for the ~94 trips
       // of a diverging solve); the price is one idle elimination when the last group stops (its update is
@@ -529,36 +495,24 @@ __device__ __forceinline__ void newton_groups(const LaneView<T>& V, bool gvalid,
       // children published (registers Sc / Lr of the child lanes; 0 on padding lanes), inverts its pivot
       // and publishes its own
       if constexpr (HYB) {
-        static_for<0, T::T_MAXH + 1>([&](auto H) {
+        // (`height` captured first, by value: the register assignment the compiler makes follows the closure's layout, and this
+        // one gives the code that was measured)
+        static_for<0, T::T_MAXH + 1>([&, height](auto H) {
           constexpr int h = H;
           if constexpr (h > 0) {
             constexpr int NL = T::T_NLH[h];
             // light children of height h - 1 (published at the end of the previous level), folded by every bus that has some --
-            // whatever its own height: all NL slots fetched together, then folded
-            if constexpr (NL > 0) {
-              // (ANM_HYB_LIGHT_ALL: every lane reads and folds -- a lane without such a child reads a padding lane's slot, zeros,
-              // also after its own pivot: no region around the reads)
-              if (ANM_HYB_LIGHT_ALL != 0 || height >= h) {
-#ifndef ANM_HYB_FETCH
-#define ANM_HYB_FETCH 1   // light-child slots fetched together before they are folded (2: 170 registers, the third wavefront per SIMD lost)
-#endif
-                static_for<0, (NL + ANM_HYB_FETCH - 1) / ANM_HYB_FETCH>([&](auto R) {
-                  constexpr int Q0 = R * ANM_HYB_FETCH;
-                  constexpr int NF = (NL - Q0) < ANM_HYB_FETCH ? (NL - Q0) : ANM_HYB_FETCH;
-                  double2 qv[NF][3];
-                  static_for<0, NF>([&](auto Q) {
-                    constexpr int q = hyb_slot_base<T>(h) + Q0 + Q;
-                    const int cq = 3 * int(__builtin_amdgcn_ubfe(lqp[q / 4], 8u * (q % 4), 8u));
-                    qv[Q][0] = xS[cq]; qv[Q][1] = xS[cq + 1]; qv[Q][2] = xS[cq + 2];
-                  });
-                  __builtin_amdgcn_s_waitcnt(0xC07F);   // lgkmcnt(0): ONE wait for the round's reads (else one per 16-byte unit)
-                  static_for<0, NF>([&](auto Q) {
-                    Dg.a -= JT(qv[Q][0].x); Dg.b -= JT(qv[Q][0].y); Dg.c -= JT(qv[Q][1].x); Dg.d -= JT(qv[Q][1].y);
-                    r0 -= JT(qv[Q][2].x); r1 -= JT(qv[Q][2].y);
-                  });
-                });
-              }
-            }
+            // whatever its own height -- one slot at a time (two fetched together: 170 registers, the third wavefront per SIMD
+            // lost).  Every lane reads and folds: a lane without such a child reads a padding lane's slot, zeros, also after its
+            // own pivot -- no region around the reads.
+            static_for<0, NL>([&](auto Q) {
+              constexpr int q = hyb_slot_base<T>(h) + Q;
+              const int cq = 3 * int(__builtin_amdgcn_ubfe(lqp[q / 4], 8u * (q % 4), 8u));
+              const double2 q0 = xS[cq], q1 = xS[cq + 1], q2 = xS[cq + 2];
+              __builtin_amdgcn_s_waitcnt(0xC07F);   // lgkmcnt(0): ONE wait for the slot's three reads (else one per 16-byte unit)
+              Dg.a -= JT(q0.x); Dg.b -= JT(q0.y); Dg.c -= JT(q1.x); Dg.d -= JT(q1.y);
+              r0 -= JT(q2.x); r1 -= JT(q2.y);
+            });
             // the heavy child's publication: registers of the next lane (every lane executes the moves; only the buses of
             // this height, whose next lane IS their child of height h - 1, use what arrives)
             constexpr int SHL1 = 0x101;   // row_shl:1 -- lane i reads lane i + 1 of its 16-lane row
@@ -591,7 +545,7 @@ __device__ __forceinline__ void newton_groups(const LaneView<T>& V, bool gvalid,
         // folds now: the 6-bus feeder's only kind) and the pivot -- and one per child class a HIGHER bus folds early.  Each
         // region the compiler opens is a save / restore pair of the exec mask (+ a skip branch for a long one): issue
         // slots like any other for a wavefront that iterates alone on its SIMD.  Same operations on every bus, in the
-        // same order: bit-identical to the one-region-per-fold form (ANM_GROUP_MERGED_REGIONS=0).
+        // same order: bit-identical to the one-region-per-fold form (MERGED = false).
         // Level 0 has nothing to fold, so its pivot needs no region either when it writes to a copy (Di) and no leaf hangs
         // off the slack: every lane computes it, a bus of a greater height (and a padding lane) on an unfinished block --
         // what that publishes is rewritten at the bus's own level before its parent reads it, a padding lane's is read by nobody.
@@ -741,7 +695,7 @@ __device__ __forceinline__ void newton_groups(const LaneView<T>& V, bool gvalid,
         JT p0 = JT(0), p1 = JT(0);
         if constexpr (dd > 0) {
           if constexpr (LDSX) {
-            const double2 dp = xV[BS_ALL ? plb : pl];
+            const double2 dp = xV[plb];
             p0 = JT(dp.x); p1 = JT(dp.y);
           } else {
             p0 = X.from_parent(d0, JT(0));
@@ -749,7 +703,7 @@ __device__ __forceinline__ void newton_groups(const LaneView<T>& V, bool gvalid,
           }
         }
         if constexpr (!(ROOT_STEP_IN_PIVOT && dd == 0))
-        if (BS_ALL || depth == dd) {
+        if (LDSX || depth == dd) {
           JT a0 = r0, a1 = r1;
           if constexpr (dd > 0) {
             a0 = fm(-Jbp.b, p1, fm(-Jbp.a, p0, a0));
@@ -770,20 +724,14 @@ __device__ __forceinline__ void newton_groups(const LaneView<T>& V, bool gvalid,
       const bool upd = __builtin_amdgcn_inverse_ballot_w64(updm);
       const double dth = double(d0);
       const unsigned long long bigm = __builtin_amdgcn_fcmp(fabs(dth), 0.78, FCMP_UGT) & updm;  // NaN counts
-#ifndef ANM_GROUP_POLY_UNMASKED
-#define ANM_GROUP_POLY_UNMASKED 1
-#endif
-      if constexpr (ANM_GROUP_POLY_UNMASKED != 0 && VPOLY) {
+      if constexpr (VPOLY) {
         // (VPOLY: the register hand-over variant = the continuation of the thread family's diverging solves, where a trip's
         // instruction COUNT is its duration, and the LDS variant where the caller's register budget has room for the
         // coefficients in vector registers (the radial kernel without per-group classes: 163 of 168): the short path evaluates the polynomials on every lane -- a lane that does not update
         // computes on whatever its dth holds and drops the result -- so that the wave-uniform branch is the only control
         // flow in front of them, and the rotation stands once behind both paths)
         double sd_, cd_;
-        // (REDUCE_ALWAYS: no short path -- the range reduction of a small step returns the step itself and quadrant 0, the
-        // same bits; for a launch that lasts as long as its slowest wavefront, whose trips reduce anyway, the test and the
-        // branch in front of the short path are four instructions of every trip)
-        if (!REDUCE_ALWAYS && bigm == 0ull) {
+        if (bigm == 0ull) {
           sincos_kernel<true>(dth, 0, sd_, cd_);
         } else {
           sincos_medium<true>(dth, sd_, cd_);
@@ -807,7 +755,7 @@ __device__ __forceinline__ void newton_groups(const LaneView<T>& V, bool gvalid,
       if (bigm == 0ull) {
         if (upd) {
           double sd_, cd_;
-          // (one-instruction Horner steps with the coefficients in vector registers -- see horner() -- where there is room: the
+          // (one-instruction Horner steps with the coefficients in vector registers -- see sincos_kernel -- where there is room: the
           // LDS-hand-over variant, which serves the radial kernel's larger trees, sits at its 168-register budget for three
           // wavefronts per SIMD and keeps the compiler's own form)
           sincos_kernel<!LDSX>(dth, 0, sd_, cd_);
@@ -843,7 +791,7 @@ __device__ __forceinline__ void newton_groups(const LaneView<T>& V, bool gvalid,
 // `lds`: >= NG * Slot<T>::SIZE doubles, private to this wavefront; every lane of the wave must call.
 // WFREE = false: the predicate-free child sums (four to eight loop-carried registers) left out -- the straggler launch, whose
 // budget is two wavefronts per SIMD.
-template <class T, class JT, bool WFREE = true, bool REDUCE_ALWAYS = false>
+template <class T, class JT, bool WFREE = true>
 __device__ __forceinline__ void continue_in_groups(cptr_t C, EnvWork<T>& w, PFState<T>& st, bool mine, double tol, int max_iter,
                                    double* lds) {
   typedef Slot<T> S;
@@ -882,7 +830,7 @@ __device__ __forceinline__ void continue_in_groups(cptr_t C, EnvWork<T>& w, PFSt
     }
     ANM_WAVE_SYNC();
     unsigned tb, tn;
-    newton_groups<T, JT, 0, false, ANM_LDSX_FETCH, WFREE, true, (ANM_GROUP_MERGED_REGIONS != 0), REDUCE_ALWAYS>(V, gvalid, vm, cs, sn, bus_p, bus_q, it, tb, tn, tol, max_iter);
+    newton_groups<T, JT, 0, false, LDSX_FETCH, WFREE>(V, gvalid, vm, cs, sn, bus_p, bus_q, it, tb, tn, tol, max_iter);
 
     // ---- results back to the owner lanes
     if (isbus) {

@@ -315,16 +315,9 @@ __global__ __launch_bounds__(64, ANM_RADIAL_WAVES) void k_radial(Dims d, const i
   const int S = d.SDIM + K;
   // The constants of this lane's device (limits, the static part of the projection: SD_SIZE doubles), asked for NOW: their
   // address depends on the lane alone, and the ~35 loads the device maps would otherwise issue inside their type branches --
-  // after the inputs have arrived -- are a second trip to memory on every wavefront's critical path.  (ANM_RADIAL_PREFETCH=0:
-  // tuning switch, the loads where they are used.)
-#ifndef ANM_RADIAL_VPOLY
-#define ANM_RADIAL_VPOLY 1   // the update's polynomials as in the thread family's lane-group loop (group::newton_groups: VPOLY)
-#endif
-#ifndef ANM_RADIAL_PREFETCH
-#define ANM_RADIAL_PREFETCH 1
-#endif
-  double sdr[ANM_RADIAL_PREFETCH ? SD_SIZE : 1];
-  if constexpr (ANM_RADIAL_PREFETCH != 0) {
+  // after the inputs have arrived -- are a second trip to memory on every wavefront's critical path.
+  double sdr[SD_SIZE];
+  {
     cptr_t row = C + d.off_dev + (l < d.ND ? l : d.ND - 1) * SD_SIZE;
     static_for<0, SD_SIZE>([&](auto Kk) { sdr[Kk] = row[Kk]; });
   }
@@ -443,8 +436,7 @@ __global__ __launch_bounds__(64, ANM_RADIAL_WAVES) void k_radial(Dims d, const i
       }
     }
   };
-  if constexpr (ANM_RADIAL_PREFETCH != 0) device_maps(sdr);
-  else device_maps(C + d.off_dev + l * SD_SIZE);
+  device_maps(sdr);
   sh[A_S0][t] = dev_p;
   sh[A_S1][t] = dev_q;
   ANM_GROUP_SYNC();
@@ -500,10 +492,10 @@ __global__ __launch_bounds__(64, ANM_RADIAL_WAVES) void k_radial(Dims d, const i
     // (trees without a DPP plan hand over through the LDS arrays the table-driven loop would use)
     static_assert(A_N >= 10, "group::newton_groups<.., LDSX> takes 640 doubles");
     // (per-environment parameters cost this kernel nine registers: two child slots per fetch round instead of three keep
-    // it at three wavefronts per SIMD)
-    group::newton_groups<TT, JT, 10, TT::T_DPP == 0, PG ? 2 : ANM_LDSX_FETCH, true, ANM_RADIAL_VPOLY != 0 && !PG,
-                         (ANM_GROUP_MERGED_REGIONS != 0) && !(PG && TT::T_DPP != 0)>(V, env_ok && !skip, gvm, gcs, gsn, gp, gq, git, tb, tn,
-                                                                            so.tol, so.max_iter, &sh[0][0]);
+    // it at three wavefronts per SIMD; without them, the update's polynomials as in the thread family's lane-group loop:
+    // group::newton_groups, VPOLY)
+    group::newton_groups<TT, JT, 10, TT::T_DPP == 0, PG ? 2 : group::LDSX_FETCH, true, !PG, !(PG && TT::T_DPP != 0)>(
+        V, env_ok && !skip, gvm, gcs, gsn, gp, gq, git, tb, tn, so.tol, so.max_iter, &sh[0][0]);
     int back_lane;   // the lane that plays bus l + 1
     if constexpr (TT::T_LP_NW > 0) back_lane = int(V.pk[TT::T_LP_NW - 1]);
     else back_lane = isbus ? TT::T_POS[l + 1] : l;
