@@ -10,6 +10,8 @@
 // (thread family) or per-lane tables (lane groups).
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
+#include <array>
 #include <cstdio>
 #include <cstring>
 #include <new>
@@ -193,6 +195,20 @@ __global__ void k_sample_init_state(int64_t n, int nd, int nload, int ngen, int 
     }
 }
 
+// The parameter tables of one kernel family: class 0 (the network the model was created from) on the host where the
+// family's packer writes it, classes 1.. (anm_model_set_classes: same topology, other numbers), and the device buffer
+// that holds all of them back to back, class k at k * h0.size() doubles
+struct Tables {
+  std::vector<double>& h0;      // h_const (Layout<Topo>) | plan.hd | mplan.hd
+  const char* copy_what;        // error texts: of an upload, of the reallocation for more classes
+  const char* alloc_what;
+  bool ok = false;              // the family can serve this model
+  int off_obs_lo = 0, off_obs_hi = 0;   // where the observation bounds [SDIM + K] sit in a class's table
+  std::vector<std::vector<double>> extra;
+  int* dev_int = nullptr;       // lane-group families: the int tables of the plan (the topology: one copy for all classes)
+  double* dev = nullptr;
+};
+
 }  // namespace
 
 struct anm_model {
@@ -201,18 +217,19 @@ struct anm_model {
   radial::View view{};          // anm_model_bind_view: the launches serve a sub-batch of a larger, padded batch
   bool has_view = false;
   int view_waves = 0;   // k_step_view variant: 0 = by batch size; 1 | 2 (ANM_VIEW_WAVES, read at anm_model_create: tuning, tests)
-  bool tpe_ok = false;          // the network has the topology this library was compiled for
-  bool radial_ok = false;       // the network is a tree that fits one wavefront
+  // the shape of the network, from the first family that took it: the compiled topology, else the radial plan, else the
+  // general one (where two families have it they agree: all three derive it from the same description)
+  anm_dims dims{};              // (action_dim = 2 n_set: the devices with set-points are the generators and the storage units)
+  FullOffsets full{};           // rows of the `full` dump
+  std::vector<double> h_const;  // constants of the compiled topology (Layout<Topo>)
   radial::Plan plan;            // per-lane tables of the lane-group kernel
-  bool mesh_ok = false;         // the general lane-group kernel can take the network
-  mesh::Plan mplan;
+  mesh::Plan mplan;             // ... of the general lane-group kernel
   mesh::Launch mlaunch{2, 1, true, 0, 0};
-  int* d_mi = nullptr;
-  double* d_md = nullptr;
-  std::vector<std::vector<double>> x_md;      // general lane-group tables of each extra class
-  int* d_ri = nullptr;
-  double* d_rd = nullptr;
-  double* d_const = nullptr;    // device constant buffer (Layout<Topo>)
+  // .ok: the network has the topology this library was compiled for | is a tree that fits one wavefront | is one the
+  // general lane-group kernel can take
+  Tables t_thread{h_const, "hipMemcpy(constants)", "hipMalloc(class constants)"};
+  Tables t_radial{plan.hd, "hipMemcpy(radial tables)", "hipMalloc(class tables)"};
+  Tables t_mesh{mplan.hd, "hipMemcpy(mesh tables)", "hipMalloc(class tables)"};
   double* d_series = nullptr;   // device exogenous series [NEXO][period]
   int period = 0;
   int K = 0;
@@ -224,10 +241,6 @@ struct anm_model {
   short obs_cls_off[FC_COUNT] = {0};
   int32_t* d_obs_index = nullptr;            // [2][n_obs]: compact-layout indices, identity-layout indices
   double* d_obs_tab = nullptr;               // [3][n_obs]: scale, low, high
-  std::vector<double> h_const;
-  // parameter classes 1.. (class 0 is the network the model was created from): same topology, other numbers
-  std::vector<std::vector<double>> x_const;   // thread-per-environment constants of each extra class
-  std::vector<std::vector<double>> x_hd;      // lane-group tables of each extra class
   const int32_t* d_env_class = nullptr;       // caller's device array [num_envs] (anm_model_bind_env_classes)
   bool class_per_env = false;                 // the classes do not come in aligned blocks of 64 environments
   uint8_t* d_state_same = nullptr;            // caller's device array [num_envs] (anm_model_bind_state_same)
@@ -237,55 +250,117 @@ struct anm_model {
   double* d_samp = nullptr;                   // [n_dev][6] sampler table (anm_sample_init_state_f64)
   int s_nd = 0, s_nload = 0, s_ngen = 0, s_ndes = 0;
   std::vector<cplx> ybus;
+
+  std::array<Tables*, 3> tables() { return {&t_thread, &t_radial, &t_mesh}; }
+  int n_classes() const { return 1 + int(std::max(std::max(t_thread.extra.size(), t_radial.extra.size()), t_mesh.extra.size())); }
 };
 
+// FullState<Topo> is full_offsets() at the counts of Topo, and the compiled topology counts action and state rows like
+// the lane-group plans (build_plan): whichever family fills the shape of a model, it is the same shape
+static_assert(full_offsets_match<Topo>());
+static_assert(Dims<Topo>::ADIM == 2 * Topo::NSET && Topo::SDIM == 2 * Topo::ND + Topo::NDES + Topo::NGEN);
 
 namespace {
 
+// (const_doubles: Layout<Topo>::TOTAL | the plan's n_double)
+void set_shape(anm_model* m, int NB, int ND, int NBR, int NLOAD, int NGEN, int NDES, int SDIM, int const_doubles) {
+  m->full = full_offsets(NB, ND, NDES, NGEN, NBR);
+  m->dims = anm_dims{NB, ND, NBR, NLOAD, NGEN, NDES, 2 * (NGEN + NDES), SDIM, m->full.base[FC_COUNT], const_doubles};
+}
+
+// device copies of a lane-group plan: its int tables and room for the doubles of class 0
+bool alloc_plan(Tables& t, const std::vector<int>& hi) {
+  return hipMalloc(&t.dev_int, hi.size() * sizeof(int)) == hipSuccess && hipMalloc(&t.dev, t.h0.size() * sizeof(double)) == hipSuccess &&
+         hipMemcpy(t.dev_int, hi.data(), hi.size() * sizeof(int), hipMemcpyHostToDevice) == hipSuccess;
+}
+
+int upload(Tables& t) {
+  if (!t.ok) return 0;
+  const size_t n = t.h0.size();
+  hipError_t e = hipMemcpy(t.dev, t.h0.data(), n * sizeof(double), hipMemcpyHostToDevice);
+  for (size_t k = 0; k < t.extra.size() && e == hipSuccess; ++k)
+    e = hipMemcpy(t.dev + (k + 1) * n, t.extra[k].data(), n * sizeof(double), hipMemcpyHostToDevice);
+  return e == hipSuccess ? 0 : fail_hip(e, t.copy_what);
+}
+
 int upload_const(anm_model* m) {
-  hipError_t e = hipSuccess;
-  if (m->tpe_ok) {
-    const size_t n = m->h_const.size();
-    e = hipMemcpy(m->d_const, m->h_const.data(), n * sizeof(double), hipMemcpyHostToDevice);
-    for (size_t k = 0; k < m->x_const.size() && e == hipSuccess; ++k)
-      e = hipMemcpy(m->d_const + (k + 1) * n, m->x_const[k].data(), n * sizeof(double), hipMemcpyHostToDevice);
-    if (e != hipSuccess) return fail_hip(e, "hipMemcpy(constants)");
-  }
-  if (m->radial_ok) {
-    const size_t n = m->plan.hd.size();
-    e = hipMemcpy(m->d_rd, m->plan.hd.data(), n * sizeof(double), hipMemcpyHostToDevice);
-    for (size_t k = 0; k < m->x_hd.size() && e == hipSuccess; ++k)
-      e = hipMemcpy(m->d_rd + (k + 1) * n, m->x_hd[k].data(), n * sizeof(double), hipMemcpyHostToDevice);
-    if (e != hipSuccess) return fail_hip(e, "hipMemcpy(radial tables)");
-  }
-  if (m->mesh_ok) {
-    const size_t n = m->mplan.hd.size();
-    e = hipMemcpy(m->d_md, m->mplan.hd.data(), n * sizeof(double), hipMemcpyHostToDevice);
-    for (size_t k = 0; k < m->x_md.size() && e == hipSuccess; ++k)
-      e = hipMemcpy(m->d_md + (k + 1) * n, m->x_md[k].data(), n * sizeof(double), hipMemcpyHostToDevice);
-    if (e != hipSuccess) return fail_hip(e, "hipMemcpy(mesh tables)");
-  }
+  for (Tables* t : m->tables())
+    if (int rc = upload(*t)) return rc;
   return 0;
 }
 
-ClassSel class_sel(const anm_model* m, bool radial) {
-  if (!m->d_env_class) return ClassSel{m->d_zero, 0, 0, 0};
-  return ClassSel{m->d_env_class, radial ? int(m->plan.hd.size()) : int(m->h_const.size()), 1, m->class_per_env ? 1 : 0};
+// the device buffer for n_classes consecutive copies (the old one stays when there is no room for the new)
+int reallocate(Tables& t, int n_classes) {
+  if (!t.ok) return 0;
+  double* p = nullptr;
+  hipError_t e = hipMalloc(&p, size_t(n_classes) * t.h0.size() * sizeof(double));
+  if (e != hipSuccess) return fail_hip(e, t.alloc_what);
+  hipFree(t.dev);
+  t.dev = p;
+  return 0;
 }
 
-template <bool WG, int SW = 2, bool TL = !WG>
-void launch_mesh_as(anm_model* m, int precision, unsigned grid, unsigned threads, size_t lds, hipStream_t s, const radial::IO& io,
-                    SolverOpts so, int64_t n, const ClassSel& cs) {
-  const mesh::Dims& d = m->mplan.d;
-  if (cs.per_group) {
-    if (precision == ANM_SOLVE_F32)
-      hipLaunchKernelGGL((mesh::k_mesh<float, true, WG, SW, TL>), dim3(grid), dim3(threads), lds, s, d, m->d_mi, m->d_md, io, so, n, cs);
-    else
-      hipLaunchKernelGGL((mesh::k_mesh<double, true, WG, SW, TL>), dim3(grid), dim3(threads), lds, s, d, m->d_mi, m->d_md, io, so, n, cs);
-  } else if (precision == ANM_SOLVE_F32)
-    hipLaunchKernelGGL((mesh::k_mesh<float, false, WG, SW, TL>), dim3(grid), dim3(threads), lds, s, d, m->d_mi, m->d_md, io, so, n, cs);
-  else
-    hipLaunchKernelGGL((mesh::k_mesh<double, false, WG, SW, TL>), dim3(grid), dim3(threads), lds, s, d, m->d_mi, m->d_md, io, so, n, cs);
+void set_obs_bounds(Tables& t, int cls, int n, const double* low, const double* high) {
+  if (!t.ok) return;
+  std::vector<double>& h = cls == 0 ? t.h0 : t.extra[cls - 1];
+  for (int k = 0; k < n; ++k) { h[t.off_obs_lo + k] = low[k]; h[t.off_obs_hi + k] = high[k]; }
+}
+
+void release(Tables& t) {
+  if (t.dev_int) hipFree(t.dev_int);
+  if (t.dev) hipFree(t.dev);
+  t.dev_int = nullptr;
+  t.dev = nullptr;
+}
+
+// the task (anm_model_set_env) in the tables of a lane-group family: its scalars and the observation bounds are the
+// task's, not the network's, and go into every class
+void set_lane_group_task(Tables& t, const anm_env_config& cfg, int state_dim) {
+  if (!t.ok) return;
+  auto apply = [&](std::vector<double>& hd) {
+    hd[radial::SF_C1] = cfg.clip_e_loss;
+    hd[radial::SF_C2] = cfg.clip_penalty;
+    hd[radial::SF_RTERM] = -cfg.clip_penalty / (1 - cfg.gamma);
+    hd[radial::SF_PERIOD] = cfg.period;
+    for (int k = 0; k < state_dim; ++k) {
+      if (cfg.obs_low) hd[t.off_obs_lo + k] = cfg.obs_low[k];
+      if (cfg.obs_high) hd[t.off_obs_hi + k] = cfg.obs_high[k];
+    }
+  };
+  apply(t.h0);
+  for (auto& x : t.extra) apply(x);
+}
+
+// the tables of parameter class k for a lane-group family: its plan is the model's own but for the numbers
+template <class Plan, class Build>
+bool class_tables(const Plan& own, Build build, const anm_network_desc& desc, int k, std::vector<std::vector<double>>& out) {
+  Plan P;
+  std::string err;
+  if (!build(desc, P, err) || P.hi != own.hi || P.hd.size() != own.hd.size()) {
+    g_err = "class " + std::to_string(k) + ": not the topology of the model" + (err.empty() ? "" : " (" + err + ")");
+    return false;
+  }
+  out.push_back(std::move(P.hd));
+  return true;
+}
+
+// One launch: the kernel, its shape, its arguments; `what` is "launch <kernel>", the text of a failure.
+template <class Kernel, class... Args>
+int launch(const char* what, Kernel kernel, unsigned grid, unsigned threads, size_t lds, hipStream_t s, const Args&... args) {
+  hipLaunchKernelGGL(kernel, dim3(grid), dim3(threads), lds, s, args...);
+  hipError_t e = hipGetLastError();
+  return e == hipSuccess ? 0 : fail_hip(e, what);
+}
+
+// anm_solver_opts.precision -> the arithmetic type of the Newton solve, as a tag: f(float{}) | f(double{})
+template <class F>
+int by_precision(int precision, F&& f) {
+  return precision == ANM_SOLVE_F32 ? f(float{}) : f(double{});
+}
+
+ClassSel class_sel(const anm_model* m, const Tables& t) {
+  if (!m->d_env_class) return ClassSel{m->d_zero, 0, 0, 0};
+  return ClassSel{m->d_env_class, int(t.h0.size()), 1, m->class_per_env ? 1 : 0};
 }
 
 // the variants of k_mesh a launch may pick (mesh::Launch), as function pointers: for hipFuncSetAttribute
@@ -297,21 +372,27 @@ void mesh_variants(std::vector<const void*>& out) {
   out.push_back((const void*)mesh::k_mesh<double, true, WG, SW, TL>);
 }
 
-int launch_mesh(anm_model* m, int precision, int64_t n, hipStream_t s, const radial::IO& io_in, SolverOpts so) {
-  radial::IO io = io_in;
-  io.v = m->view;
+// the variant of k_mesh for a plan (mesh::Launch: WG, SW, TL) and for how the classes are bound
+template <class JT, bool WG, int SW = 2, bool TL = !WG>
+auto mesh_kernel(bool class_per_group) {
+  return class_per_group ? mesh::k_mesh<JT, true, WG, SW, TL> : mesh::k_mesh<JT, false, WG, SW, TL>;
+}
+
+int launch_mesh(anm_model* m, int precision, int64_t n, hipStream_t s, const radial::IO& io, SolverOpts so) {
   const mesh::Dims& d = m->mplan.d;
   const mesh::Launch& L = m->mlaunch;   // (decided once, at anm_model_create)
   const int per_block = mesh::envs_per_block(d, L);
   const unsigned grid = unsigned((n + per_block - 1) / per_block), threads = unsigned(64 * L.waves);
-  const ClassSel cs = m->d_env_class ? ClassSel{m->d_env_class, int(m->mplan.hd.size()), 1, m->class_per_env ? 1 : 0} : ClassSel{m->d_zero, 0, 0, 0};
-  if (mesh::is_workgroup(d)) launch_mesh_as<true>(m, precision, grid, threads, L.lds, s, io, so, n, cs);
-  else if (!L.tables_in_lds) launch_mesh_as<false, 2, false>(m, precision, grid, threads, L.lds, s, io, so, n, cs);
-  else if (L.simd_waves == 3) launch_mesh_as<false, 3>(m, precision, grid, threads, L.lds, s, io, so, n, cs);
-  else launch_mesh_as<false>(m, precision, grid, threads, L.lds, s, io, so, n, cs);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return fail_hip(e, "launch k_mesh");
-  return 0;
+  const ClassSel cs = class_sel(m, m->t_mesh);
+  const bool pg = cs.per_group != 0;
+  return by_precision(precision, [&](auto jt) {
+    using JT = decltype(jt);
+    auto kern = mesh::is_workgroup(d) ? mesh_kernel<JT, true>(pg)
+                : !L.tables_in_lds    ? mesh_kernel<JT, false, 2, false>(pg)
+                : L.simd_waves == 3   ? mesh_kernel<JT, false, 3>(pg)
+                                      : mesh_kernel<JT, false>(pg);
+    return launch("launch k_mesh", kern, grid, threads, L.lds, s, d, m->t_mesh.dev_int, m->t_mesh.dev, io, so, n, cs);
+  });
 }
 
 // the lane-group families gather a list-form observation from one LDS row of the electrical state per environment
@@ -321,31 +402,36 @@ size_t radial_obs_lds_bytes(const anm_model* m) {
   return size_t(64 / m->plan.d.G) * size_t(m->plan.d.FS + radial::KMAX) * sizeof(double);
 }
 
-int launch_radial(anm_model* m, int precision, int64_t n, hipStream_t s, const radial::IO& io_in, SolverOpts so) {
-  radial::IO io = io_in;
-  io.v = m->view;
+int launch_radial(anm_model* m, int precision, int64_t n, hipStream_t s, const radial::IO& io, SolverOpts so) {
   const int per_wave = 64 / m->plan.d.G;
   const unsigned grid = unsigned((n + per_wave - 1) / per_wave);
   // the model is the compiled tree: the specialised Newton loop; else (generic mode) the table-driven one
   bool spec = false;
-  if constexpr (Topo::TREE != 0) spec = m->tpe_ok && m->plan.d.G == Topo::GRP && !getenv("ANM_RADIAL_GENERIC");
-  const ClassSel cs = class_sel(m, true);
-  const bool f32 = precision == ANM_SOLVE_F32;
+  if constexpr (Topo::TREE != 0) spec = m->t_thread.ok && m->plan.d.G == Topo::GRP && !getenv("ANM_RADIAL_GENERIC");
+  const ClassSel cs = class_sel(m, m->t_radial);
   const size_t obs_lds = (io.mode == 2 && io.e.n_obs > 0) ? radial_obs_lds_bytes(m) : 0;   // rows of a list-form observation
-  auto go = [&](auto kern) { hipLaunchKernelGGL(kern, dim3(grid), dim3(64), obs_lds, s, m->plan.d, m->d_ri, m->d_rd, io, so, n, cs); };
-  if (spec) {
-    if constexpr (Topo::TREE != 0) {
-      if (cs.per_group) { if (f32) go(radial::k_radial<float, Topo, true>); else go(radial::k_radial<double, Topo, true>); }
-      else { if (f32) go(radial::k_radial<float, Topo>); else go(radial::k_radial<double, Topo>); }
-    }
-  } else if (cs.per_group) {
-    if (f32) go(radial::k_radial<float, void, true>); else go(radial::k_radial<double, void, true>);
-  } else {
-    if (f32) go(radial::k_radial<float, void>); else go(radial::k_radial<double, void>);
-  }
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return fail_hip(e, "launch k_radial");
-  return 0;
+  auto go = [&](auto kern) {
+    return launch("launch k_radial", kern, grid, 64, obs_lds, s, m->plan.d, m->t_radial.dev_int, m->t_radial.dev, io, so, n, cs);
+  };
+  return by_precision(precision, [&](auto jt) {
+    using JT = decltype(jt);
+    if constexpr (Topo::TREE != 0)
+      if (spec) return cs.per_group ? go(radial::k_radial<JT, Topo, true>) : go(radial::k_radial<JT, Topo>);
+    return cs.per_group ? go(radial::k_radial<JT, void, true>) : go(radial::k_radial<JT, void>);
+  });
+}
+
+// The lane-group families serve every entry point with one kernel, told apart by radial::IO::mode: 0 transition (t),
+// 1 reset, 2 step (e)
+bool on_lane_groups(const anm_model* m) { return m->impl == ANM_IMPL_RADIAL || m->impl == ANM_IMPL_MESH; }
+int launch_lane_groups(anm_model* m, int mode, const TransitionIO* t, const EnvIO* e, int precision, int64_t n, hipStream_t s,
+                       SolverOpts so) {
+  radial::IO io{};
+  io.mode = mode;
+  if (t) io.t = *t;
+  if (e) io.e = *e;
+  io.v = m->view;
+  return m->impl == ANM_IMPL_MESH ? launch_mesh(m, precision, n, s, io, so) : launch_radial(m, precision, n, s, io, so);
 }
 
 SolverOpts solver(const anm_solver_opts* o, int& precision) {
@@ -383,9 +469,15 @@ int anm_model_create(const anm_network_desc* desc, anm_model** out) {
   if (!desc || !out) return fail("anm_model_create: null argument");
   anm_model* m = new (std::nothrow) anm_model();
   if (!m) return fail("out of host memory");
+  auto give_up = [&](int rc) {   // (every way out but the last: what was allocated so far goes the way of a finished model)
+    anm_model_destroy(m);
+    return rc;
+  };
   std::string err, err_topo;
-  m->tpe_ok = pack_constants<Topo>(*desc, m->h_const, m->ybus, err_topo);
-  if (m->tpe_ok) {
+  m->t_thread.ok = pack_constants<Topo>(*desc, m->h_const, m->ybus, err_topo);
+  if (m->t_thread.ok) {
+    m->t_thread.off_obs_lo = Layout<Topo>::OBS_LO;
+    m->t_thread.off_obs_hi = Layout<Topo>::OBS_HI;
     // k_step_general's dynamic LDS: the electrical-state rows (at most 60 KB, GenLds::FULL_OK) plus the state rows can
     // exceed the default 64 KB per workgroup (an 8-bus tree with 9 devices: 68 KB).  The attribute is set here, once,
     // not in a launch path that may be under stream capture
@@ -395,73 +487,61 @@ int anm_model_create(const anm_network_desc* desc, anm_model** out) {
     if (worst > 64 * 1024) {
       hipError_t a1 = hipFuncSetAttribute((const void*)k_step_general<float>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
       hipError_t a2 = hipFuncSetAttribute((const void*)k_step_general<double>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-      if (a1 != hipSuccess || a2 != hipSuccess) {
-        delete m;
-        return fail_hip(a1 != hipSuccess ? a1 : a2, "k_step_general: LDS size attribute");
-      }
+      if (a1 != hipSuccess || a2 != hipSuccess) return give_up(fail_hip(a1 != hipSuccess ? a1 : a2, "k_step_general: LDS size attribute"));
     }
-    hipError_t e = hipMalloc(&m->d_const, m->h_const.size() * sizeof(double));
-    if (e != hipSuccess) {
-      delete m;
-      return fail_hip(e, "hipMalloc(constants)");
-    }
+    hipError_t e = hipMalloc(&m->t_thread.dev, m->h_const.size() * sizeof(double));
+    if (e != hipSuccess) return give_up(fail_hip(e, "hipMalloc(constants)"));
   }
-  if (radial::is_radial(*desc) && radial::build_plan(*desc, m->plan, err)) {
-    hipError_t e1 = hipMalloc(&m->d_ri, m->plan.hi.size() * sizeof(int));
-    hipError_t e2 = hipMalloc(&m->d_rd, m->plan.hd.size() * sizeof(double));
-    if (e1 == hipSuccess && e2 == hipSuccess &&
-        hipMemcpy(m->d_ri, m->plan.hi.data(), m->plan.hi.size() * sizeof(int), hipMemcpyHostToDevice) == hipSuccess) {
-      m->radial_ok = true;
-      // default: the lane-group kernel once the thread-per-environment working set no longer fits
-      // in registers (measured: a 30-bus feeder spills 4.7 KB/lane); ANM_IMPL=thread|radial overrides
-      m->impl = (!m->tpe_ok || desc->n_bus > 12) ? ANM_IMPL_RADIAL : ANM_IMPL_THREAD;
+  if (radial::is_radial(*desc) && radial::build_plan(*desc, m->plan, err) && alloc_plan(m->t_radial, m->plan.hi)) {
+    m->t_radial.ok = true;
+    m->t_radial.off_obs_lo = m->plan.d.off_obs_lo;
+    m->t_radial.off_obs_hi = m->plan.d.off_obs_hi;
+    // default: the lane-group kernel once the thread-per-environment working set no longer fits
+    // in registers (measured: a 30-bus feeder spills 4.7 KB/lane); ANM_IMPL=thread|radial overrides
+    m->impl = (!m->t_thread.ok || desc->n_bus > 12) ? ANM_IMPL_RADIAL : ANM_IMPL_THREAD;
+    const char* ev = getenv("ANM_IMPL");
+    if (ev && std::string(ev) == "thread" && m->t_thread.ok) m->impl = ANM_IMPL_THREAD;
+    if (ev && std::string(ev) == "radial") m->impl = ANM_IMPL_RADIAL;
+  }
+  std::string err_mesh;
+  if (mesh::build_plan(*desc, m->mplan, err_mesh) && alloc_plan(m->t_mesh, m->mplan.hi)) {
+    // the general lane-group kernel: any topology that fits a wavefront
+    m->t_mesh.ok = true;
+    m->t_mesh.off_obs_lo = m->mplan.d.off_obs_lo;
+    m->t_mesh.off_obs_hi = m->mplan.d.off_obs_hi;
+    m->mlaunch = mesh::launch_of(m->mplan.d);
+    if (m->mlaunch.lds > 64 * 1024) {
+      // above the default per-workgroup limit: ask for the compute unit's whole LDS (once, here: an
+      // attribute call has no place in a launch path that may be under stream capture)
+      std::vector<const void*> fns;
+      mesh_variants<false, 2, true>(fns); mesh_variants<false, 3, true>(fns); mesh_variants<false, 2, false>(fns); mesh_variants<true, 2, false>(fns);
+      for (const void* fn : fns)
+        if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) m->t_mesh.ok = false;
+    }
+    if (m->t_mesh.ok) {
+      // default for what neither of the other families serves well: not a tree, and either not the compiled
+      // topology or too large for one thread's registers
+      if (!m->t_radial.ok && (!m->t_thread.ok || desc->n_bus > 12)) m->impl = ANM_IMPL_MESH;
       const char* ev = getenv("ANM_IMPL");
-      if (ev && std::string(ev) == "thread" && m->tpe_ok) m->impl = ANM_IMPL_THREAD;
-      if (ev && std::string(ev) == "radial") m->impl = ANM_IMPL_RADIAL;
-    }
-  }
-  {  // the general lane-group kernel: any topology that fits a wavefront
-    std::string err_mesh;
-    if (mesh::build_plan(*desc, m->mplan, err_mesh)) {
-      hipError_t e1 = hipMalloc(&m->d_mi, m->mplan.hi.size() * sizeof(int));
-      hipError_t e2 = hipMalloc(&m->d_md, m->mplan.hd.size() * sizeof(double));
-      if (e1 == hipSuccess && e2 == hipSuccess &&
-          hipMemcpy(m->d_mi, m->mplan.hi.data(), m->mplan.hi.size() * sizeof(int), hipMemcpyHostToDevice) == hipSuccess) {
-        m->mesh_ok = true;
-        m->mlaunch = mesh::launch_of(m->mplan.d);
-        if (m->mlaunch.lds > 64 * 1024) {
-          // above the default per-workgroup limit: ask for the compute unit's whole LDS (once, here: an
-          // attribute call has no place in a launch path that may be under stream capture)
-          std::vector<const void*> fns;
-          mesh_variants<false, 2, true>(fns); mesh_variants<false, 3, true>(fns); mesh_variants<false, 2, false>(fns); mesh_variants<true, 2, false>(fns);
-          for (const void* fn : fns)
-            if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) m->mesh_ok = false;
-        }
-      }
-      if (m->mesh_ok) {
-        // default for what neither of the other families serves well: not a tree, and either not the compiled
-        // topology or too large for one thread's registers
-        if (!m->radial_ok && (!m->tpe_ok || desc->n_bus > 12)) m->impl = ANM_IMPL_MESH;
-        const char* ev = getenv("ANM_IMPL");
-        if (ev && std::string(ev) == "mesh") m->impl = ANM_IMPL_MESH;
-      }
+      if (ev && std::string(ev) == "mesh") m->impl = ANM_IMPL_MESH;
     }
   }
   if (const char* ev = getenv("ANM_VIEW_WAVES")) {
     const int v = atoi(ev);
     if (v == 1 || v == 2) m->view_waves = v;
   }
-  if (!m->tpe_ok && !m->radial_ok && !m->mesh_ok) {
+  if (m->t_thread.ok) {
+    set_shape(m, Topo::NB, Topo::ND, Topo::NBR, Topo::NLOAD, Topo::NGEN, Topo::NDES, Topo::SDIM, Layout<Topo>::TOTAL);
+  } else if (m->t_radial.ok || m->t_mesh.ok) {
+    auto of_plan = [&](const auto& d) { set_shape(m, d.NB, d.ND, d.NBR, d.NLOAD, d.NGEN, d.NDES, d.SDIM, d.n_double); };
+    if (m->t_radial.ok) of_plan(m->plan.d);
+    else of_plan(m->mplan.d);
+  } else {
     // neither the compiled topology nor a network the generic lane-group kernels can take
-    if (m->d_ri) hipFree(m->d_ri);
-    if (m->d_rd) hipFree(m->d_rd);
-    if (m->d_mi) hipFree(m->d_mi);
-    if (m->d_md) hipFree(m->d_md);
-    delete m;
     g_err = err_topo;
-    return -3;
+    return give_up(-3);
   }
-  if (!m->tpe_ok) {  // generic model: dense Y_bus for diagnostics
+  if (!m->t_thread.ok) {  // generic model: dense Y_bus for diagnostics
     const int NB = desc->n_bus;
     m->ybus.assign(size_t(NB) * NB, cplx(0, 0));
     for (int b = 0; b < desc->n_branch; ++b) {
@@ -494,22 +574,15 @@ int anm_model_create(const anm_network_desc* desc, anm_model** out) {
         hipMemcpy(m->d_samp, tab.data(), tab.size() * sizeof(double), hipMemcpyHostToDevice) != hipSuccess)
       rc = fail("hipMalloc(sampler table)");
   }
-  if (rc) {
-    anm_model_destroy(m);
-    return rc;
-  }
+  if (rc) return give_up(rc);
   *out = m;
   return 0;
 }
 
 void anm_model_destroy(anm_model* m) {
   if (!m) return;
-  if (m->d_const) hipFree(m->d_const);
+  for (Tables* t : m->tables()) release(*t);
   if (m->d_series) hipFree(m->d_series);
-  if (m->d_ri) hipFree(m->d_ri);
-  if (m->d_rd) hipFree(m->d_rd);
-  if (m->d_mi) hipFree(m->d_mi);
-  if (m->d_md) hipFree(m->d_md);
   if (m->d_zero) hipFree(m->d_zero);
   if (m->d_samp) hipFree(m->d_samp);
   if (m->d_obs_index) hipFree(m->d_obs_index);
@@ -519,52 +592,17 @@ void anm_model_destroy(anm_model* m) {
 
 int anm_model_dims(const anm_model* m, anm_dims* out) {
   if (!m || !out) return fail("anm_model_dims: null argument");
-  if (!m->tpe_ok) {
-    auto fill = [&](const auto& d) {
-      out->n_bus = d.NB; out->n_dev = d.ND; out->n_branch = d.NBR; out->n_load = d.NLOAD; out->n_gen = d.NGEN;
-      out->n_des = d.NDES; out->action_dim = 2 * (d.NGEN + d.NDES); out->state_base_dim = d.SDIM;
-      out->full_dim = d.FS; out->const_doubles = d.n_double;
-    };
-    if (m->radial_ok) fill(m->plan.d);
-    else fill(m->mplan.d);
-    return 0;
-  }
-  out->n_bus = Topo::NB;
-  out->n_dev = Topo::ND;
-  out->n_branch = Topo::NBR;
-  out->n_load = Topo::NLOAD;
-  out->n_gen = Topo::NGEN;
-  out->n_des = Topo::NDES;
-  out->action_dim = Dims<Topo>::ADIM;
-  out->state_base_dim = Topo::SDIM;
-  out->full_dim = FullState<Topo>::SIZE;
-  out->const_doubles = Layout<Topo>::TOTAL;
+  *out = m->dims;
   return 0;
 }
 
 int anm_model_full_layout(const anm_model* m, anm_full_layout* o) {
   if (!m || !o) return fail("anm_model_full_layout: null argument");
-  if (!m->tpe_ok && !m->radial_ok) {
-    const mesh::Dims& d = m->mplan.d;
-    o->bus_p = d.f_bus_p; o->bus_q = d.f_bus_q; o->bus_v_magn = d.f_bus_vm; o->bus_v_ang = d.f_bus_va;
-    o->bus_i_magn = d.f_bus_im; o->bus_i_ang = d.f_bus_ia; o->dev_p = d.f_dev_p; o->dev_q = d.f_dev_q;
-    o->des_soc = d.f_des_soc; o->gen_p_max = d.f_gen_pmax; o->branch_p = d.f_br_p; o->branch_q = d.f_br_q;
-    o->branch_s = d.f_br_s; o->branch_i_magn = d.f_br_im; o->branch_i_ang = d.f_br_ia; o->size = d.FS;
-    return 0;
-  }
-  if (!m->tpe_ok) {
-    const radial::Dims& d = m->plan.d;
-    o->bus_p = d.f_bus_p; o->bus_q = d.f_bus_q; o->bus_v_magn = d.f_bus_vm; o->bus_v_ang = d.f_bus_va;
-    o->bus_i_magn = d.f_bus_im; o->bus_i_ang = d.f_bus_ia; o->dev_p = d.f_dev_p; o->dev_q = d.f_dev_q;
-    o->des_soc = d.f_des_soc; o->gen_p_max = d.f_gen_pmax; o->branch_p = d.f_br_p; o->branch_q = d.f_br_q;
-    o->branch_s = d.f_br_s; o->branch_i_magn = d.f_br_im; o->branch_i_ang = d.f_br_ia; o->size = d.FS;
-    return 0;
-  }
-  typedef FullState<Topo> F;
-  o->bus_p = F::BUS_P; o->bus_q = F::BUS_Q; o->bus_v_magn = F::BUS_VM; o->bus_v_ang = F::BUS_VA;
-  o->bus_i_magn = F::BUS_IM; o->bus_i_ang = F::BUS_IA; o->dev_p = F::DEV_P; o->dev_q = F::DEV_Q;
-  o->des_soc = F::DES_SOC; o->gen_p_max = F::GEN_PMAX; o->branch_p = F::BR_P; o->branch_q = F::BR_Q;
-  o->branch_s = F::BR_S; o->branch_i_magn = F::BR_IM; o->branch_i_ang = F::BR_IA; o->size = F::SIZE;
+  const int* b = m->full.base;
+  o->bus_p = b[FC_BUS_P]; o->bus_q = b[FC_BUS_Q]; o->bus_v_magn = b[FC_BUS_VM]; o->bus_v_ang = b[FC_BUS_VA];
+  o->bus_i_magn = b[FC_BUS_IM]; o->bus_i_ang = b[FC_BUS_IA]; o->dev_p = b[FC_DEV_P]; o->dev_q = b[FC_DEV_Q];
+  o->des_soc = b[FC_DES_SOC]; o->gen_p_max = b[FC_GEN_PMAX]; o->branch_p = b[FC_BR_P]; o->branch_q = b[FC_BR_Q];
+  o->branch_s = b[FC_BR_S]; o->branch_i_magn = b[FC_BR_IM]; o->branch_i_ang = b[FC_BR_IA]; o->size = b[FC_COUNT];
   return 0;
 }
 
@@ -572,46 +610,15 @@ int anm_model_set_env(anm_model* m, const anm_env_config* cfg) {
   if (!m || !cfg) return fail("anm_model_set_env: null argument");
   std::string err;
   if (cfg->K < 0 || cfg->K > radial::KMAX) return fail("K (number of aux variables) must be in [0, 8]");
-  if (m->tpe_ok && !pack_env<Topo>(*cfg, m->h_const, err)) {
+  if (m->t_thread.ok && !pack_env<Topo>(*cfg, m->h_const, err)) {
     g_err = err;
     return -3;
   }
-  if (m->tpe_ok)
-    for (auto& xc : m->x_const) pack_env<Topo>(*cfg, xc, err);
+  if (m->t_thread.ok)
+    for (auto& xc : m->t_thread.extra) pack_env<Topo>(*cfg, xc, err);
   m->K = cfg->K;
-  if (m->radial_ok) {
-    radial::Plan& P = m->plan;
-    P.hd[radial::SF_C1] = cfg->clip_e_loss;
-    P.hd[radial::SF_C2] = cfg->clip_penalty;
-    P.hd[radial::SF_RTERM] = -cfg->clip_penalty / (1 - cfg->gamma);
-    P.hd[radial::SF_PERIOD] = cfg->period;
-    for (int k = 0; k < P.d.SDIM + cfg->K; ++k) {
-      if (cfg->obs_low) P.hd[P.d.off_obs_lo + k] = cfg->obs_low[k];
-      if (cfg->obs_high) P.hd[P.d.off_obs_hi + k] = cfg->obs_high[k];
-    }
-    for (auto& xh : m->x_hd) {
-      for (int f : {int(radial::SF_C1), int(radial::SF_C2), int(radial::SF_RTERM), int(radial::SF_PERIOD)}) xh[f] = P.hd[f];
-      for (int k = 0; k < P.d.SDIM + cfg->K; ++k) {
-        xh[P.d.off_obs_lo + k] = P.hd[P.d.off_obs_lo + k];
-        xh[P.d.off_obs_hi + k] = P.hd[P.d.off_obs_hi + k];
-      }
-    }
-  }
-  if (m->mesh_ok) {
-    mesh::Plan& P = m->mplan;
-    auto apply = [&](std::vector<double>& hd) {
-      hd[radial::SF_C1] = cfg->clip_e_loss;
-      hd[radial::SF_C2] = cfg->clip_penalty;
-      hd[radial::SF_RTERM] = -cfg->clip_penalty / (1 - cfg->gamma);
-      hd[radial::SF_PERIOD] = cfg->period;
-      for (int k = 0; k < P.d.SDIM + cfg->K; ++k) {
-        if (cfg->obs_low) hd[P.d.off_obs_lo + k] = cfg->obs_low[k];
-        if (cfg->obs_high) hd[P.d.off_obs_hi + k] = cfg->obs_high[k];
-      }
-    };
-    apply(P.hd);
-    for (auto& x : m->x_md) apply(x);
-  }
+  set_lane_group_task(m->t_radial, *cfg, m->dims.state_base_dim + cfg->K);
+  set_lane_group_task(m->t_mesh, *cfg, m->dims.state_base_dim + cfg->K);
   if (m->d_series) {
     hipFree(m->d_series);
     m->d_series = nullptr;
@@ -619,9 +626,7 @@ int anm_model_set_env(anm_model* m, const anm_env_config* cfg) {
   m->period = 0;
   if (cfg->series && cfg->period > 0) {
     if (cfg->K != 1) return fail("series mode needs exactly K = 1 auxiliary variable (the time index)");
-    const size_t nexo = m->tpe_ok ? size_t(Dims<Topo>::NEXO)
-                                  : (m->radial_ok ? size_t(m->plan.d.NLOAD + m->plan.d.NGEN) : size_t(m->mplan.d.NLOAD + m->mplan.d.NGEN));
-    const size_t bytes = sizeof(double) * nexo * size_t(cfg->period);
+    const size_t bytes = sizeof(double) * size_t(m->dims.n_load + m->dims.n_gen) * size_t(cfg->period);
     hipError_t e = hipMalloc(&m->d_series, bytes ? bytes : 8);
     if (e != hipSuccess) return fail_hip(e, "hipMalloc(series)");
     e = hipMemcpy(m->d_series, cfg->series, bytes, hipMemcpyHostToDevice);
@@ -641,8 +646,8 @@ int anm_model_set_classes(anm_model* m, int32_t n_classes, const anm_network_des
   std::vector<std::vector<double>> xc, xh, xm;
   for (int k = 1; k < n_classes; ++k) {
     if (!descs[k]) return fail("anm_model_set_classes: null description");
-    std::string err;
-    if (m->tpe_ok) {
+    if (m->t_thread.ok) {
+      std::string err;
       std::vector<double> cbuf;
       std::vector<cplx> y;
       if (!pack_constants<Topo>(*descs[k], cbuf, y, err)) {
@@ -651,48 +656,14 @@ int anm_model_set_classes(anm_model* m, int32_t n_classes, const anm_network_des
       }
       xc.push_back(std::move(cbuf));
     }
-    if (m->radial_ok) {
-      radial::Plan P;
-      if (!radial::build_plan(*descs[k], P, err) || P.hi != m->plan.hi || P.hd.size() != m->plan.hd.size()) {
-        g_err = "class " + std::to_string(k) + ": not the topology of the model" + (err.empty() ? "" : " (" + err + ")");
-        return -3;
-      }
-      xh.push_back(std::move(P.hd));
-    }
-    if (m->mesh_ok) {
-      mesh::Plan P;
-      if (!mesh::build_plan(*descs[k], P, err) || P.hi != m->mplan.hi || P.hd.size() != m->mplan.hd.size()) {
-        g_err = "class " + std::to_string(k) + ": not the topology of the model" + (err.empty() ? "" : " (" + err + ")");
-        return -3;
-      }
-      xm.push_back(std::move(P.hd));
-    }
+    if (m->t_radial.ok && !class_tables(m->plan, radial::build_plan, *descs[k], k, xh)) return -3;
+    if (m->t_mesh.ok && !class_tables(m->mplan, mesh::build_plan, *descs[k], k, xm)) return -3;
   }
-  // (re)allocate the device buffers for n_classes consecutive copies
-  if (m->tpe_ok) {
-    double* p = nullptr;
-    hipError_t e = hipMalloc(&p, size_t(n_classes) * m->h_const.size() * sizeof(double));
-    if (e != hipSuccess) return fail_hip(e, "hipMalloc(class constants)");
-    hipFree(m->d_const);
-    m->d_const = p;
-  }
-  if (m->radial_ok) {
-    double* p = nullptr;
-    hipError_t e = hipMalloc(&p, size_t(n_classes) * m->plan.hd.size() * sizeof(double));
-    if (e != hipSuccess) return fail_hip(e, "hipMalloc(class tables)");
-    hipFree(m->d_rd);
-    m->d_rd = p;
-  }
-  if (m->mesh_ok) {
-    double* p = nullptr;
-    hipError_t e = hipMalloc(&p, size_t(n_classes) * m->mplan.hd.size() * sizeof(double));
-    if (e != hipSuccess) return fail_hip(e, "hipMalloc(class tables)");
-    hipFree(m->d_md);
-    m->d_md = p;
-  }
-  m->x_const = std::move(xc);
-  m->x_hd = std::move(xh);
-  m->x_md = std::move(xm);
+  for (Tables* t : m->tables())
+    if (int rc = reallocate(*t, n_classes)) return rc;
+  m->t_thread.extra = std::move(xc);
+  m->t_radial.extra = std::move(xh);
+  m->t_mesh.extra = std::move(xm);
   m->d_env_class = nullptr;
   m->class_per_env = false;
   if (m->impl_unbound >= 0) { m->impl = m->impl_unbound; m->impl_unbound = -1; }
@@ -703,21 +674,8 @@ int anm_model_set_classes(anm_model* m, int32_t n_classes, const anm_network_des
 int anm_model_set_class_obs_bounds(anm_model* m, int32_t cls, const double* low, const double* high) {
   if (!m || !low || !high) return fail("anm_model_set_class_obs_bounds: null argument");
   if (!m->env_set) return fail("anm_model_set_class_obs_bounds: call anm_model_set_env first (it writes every class)");
-  const int n_cls = 1 + int(std::max(std::max(m->x_const.size(), m->x_hd.size()), m->x_md.size()));
-  if (cls < 0 || cls >= n_cls) return fail("anm_model_set_class_obs_bounds: no such class");
-  if (m->tpe_ok) {
-    typedef Layout<Topo> L;
-    std::vector<double>& c = cls == 0 ? m->h_const : m->x_const[cls - 1];
-    for (int k = 0; k < Topo::SDIM + m->K; ++k) { c[L::OBS_LO + k] = low[k]; c[L::OBS_HI + k] = high[k]; }
-  }
-  if (m->radial_ok) {
-    std::vector<double>& h = cls == 0 ? m->plan.hd : m->x_hd[cls - 1];
-    for (int k = 0; k < m->plan.d.SDIM + m->K; ++k) { h[m->plan.d.off_obs_lo + k] = low[k]; h[m->plan.d.off_obs_hi + k] = high[k]; }
-  }
-  if (m->mesh_ok) {
-    std::vector<double>& h = cls == 0 ? m->mplan.hd : m->x_md[cls - 1];
-    for (int k = 0; k < m->mplan.d.SDIM + m->K; ++k) { h[m->mplan.d.off_obs_lo + k] = low[k]; h[m->mplan.d.off_obs_hi + k] = high[k]; }
-  }
+  if (cls < 0 || cls >= m->n_classes()) return fail("anm_model_set_class_obs_bounds: no such class");
+  for (Tables* t : m->tables()) set_obs_bounds(*t, cls, m->dims.state_base_dim + m->K, low, high);
   return upload_const(m);
 }
 
@@ -749,7 +707,7 @@ int anm_model_bind_env_classes(anm_model* m, const int32_t* env_class, int64_t n
     // class up by launch slot and an environment's by its index in the batch)
     return fail("anm_model_bind_env_classes: not while a batch view is bound (anm_model_bind_view)");
   if (num_envs <= 0) return fail("anm_model_bind_env_classes: num_envs must be positive");
-  const int n_classes = 1 + int(m->tpe_ok ? m->x_const.size() : (m->radial_ok ? m->x_hd.size() : m->x_md.size()));
+  const int n_classes = m->n_classes();
   std::vector<int32_t> h(static_cast<size_t>(num_envs));
   hipError_t e = hipMemcpy(h.data(), env_class, h.size() * sizeof(int32_t), hipMemcpyDeviceToHost);
   if (e != hipSuccess) return fail_hip(e, "anm_model_bind_env_classes");
@@ -762,7 +720,7 @@ int anm_model_bind_env_classes(anm_model* m, const int32_t* env_class, int64_t n
   // every kernel family.  Any other assignment -- a different network in every environment -- is served by the
   // lane-group families (one environment per lane group, its constants read by vector loads); the
   // thread-per-environment kernels cannot (64 environments share a wavefront's scalar constants).
-  if (!blocks && !(m->radial_ok || m->mesh_ok))
+  if (!blocks && !(m->t_radial.ok || m->t_mesh.ok))
     return fail("anm_model_bind_env_classes: a class must cover whole aligned blocks of 64 environments (this network has no lane-group kernel)");
   // (the same guard as anm_model_set_impl: the lane-group kernels do not gather a list-form observation -- moving a
   // model with one to them would silently turn its observation into clip(state))
@@ -776,7 +734,7 @@ int anm_model_bind_env_classes(anm_model* m, const int32_t* env_class, int64_t n
   if (blocks) restore_impl();
   else if (m->impl == ANM_IMPL_THREAD) {
     m->impl_unbound = ANM_IMPL_THREAD;
-    m->impl = m->radial_ok ? ANM_IMPL_RADIAL : ANM_IMPL_MESH;
+    m->impl = m->t_radial.ok ? ANM_IMPL_RADIAL : ANM_IMPL_MESH;
   }
   return 0;
 }
@@ -813,8 +771,7 @@ int anm_model_bind_view(anm_model* m, const anm_batch_view* v) {
                 "(anm_model_set_obs): clear it, or move the model to a lane-group family first (anm_model_set_impl)");
   if (m->n_obs > 0 && v->w_obs != 0 && v->w_obs < m->n_obs) return fail("anm_model_bind_view: w_obs is narrower than the observation list");
   if (m->d_state_same) return fail("anm_model_bind_view: not together with anm_model_bind_state_same (the flags are indexed by launch slot)");
-  anm_dims d;
-  anm_model_dims(m, &d);
+  const anm_dims& d = m->dims;
   const int K = m->K;
   const int n_set = d.n_gen + d.n_des;
   struct { int given, own; const char* what; } w[] = {
@@ -838,12 +795,11 @@ static unsigned magic_div(int d) { return d > 0 ? unsigned((0x100000000ull + uin
 int anm_model_obs_fusable(const anm_model* m) {
   if (!m) return 0;
   if (m->has_view && m->impl == ANM_IMPL_THREAD) return 0;   // (its step through a view moves rows per lane: no LDS rows to gather from)
-  if (m->impl == ANM_IMPL_THREAD) return (m->tpe_ok && GenLds<Topo>::FULL_OK) ? 1 : 0;
-  if (m->impl == ANM_IMPL_RADIAL) return (m->radial_ok && radial_obs_lds_bytes(m) <= 48 * 1024) ? 1 : 0;
-  if (m->impl == ANM_IMPL_MESH) return (m->mesh_ok && m->mplan.d.l_bw - m->mplan.d.l_blk >= m->mplan.d.FS + radial::KMAX) ? 1 : 0;
+  if (m->impl == ANM_IMPL_THREAD) return (m->t_thread.ok && GenLds<Topo>::FULL_OK) ? 1 : 0;
+  if (m->impl == ANM_IMPL_RADIAL) return (m->t_radial.ok && radial_obs_lds_bytes(m) <= 48 * 1024) ? 1 : 0;
+  if (m->impl == ANM_IMPL_MESH) return (m->t_mesh.ok && m->mplan.d.l_bw - m->mplan.d.l_blk >= m->mplan.d.FS + radial::KMAX) ? 1 : 0;
   return 0;
 }
-
 int anm_model_set_obs(anm_model* m, int32_t n_obs, const int32_t* index, const double* scale, const double* low,
                       const double* high) {
   if (!m) return fail("anm_model_set_obs: null model");
@@ -856,80 +812,37 @@ int anm_model_set_obs(anm_model* m, int32_t n_obs, const int32_t* index, const d
   if (!index || !scale || !low || !high) return fail("anm_model_set_obs: null argument");
   if (n_obs > 4096) return fail("anm_model_set_obs: more than 4096 observation entries");
   if (m->has_view && m->view.w_obs != 0 && m->view.w_obs < n_obs) return fail("anm_model_set_obs: the bound view's w_obs is narrower than the list");
-  if (m->impl != ANM_IMPL_THREAD) {
-    // lane-group families: the identity layout of `full` (runtime offsets of the network), the classes the list reads
-    const bool rad = m->impl == ANM_IMPL_RADIAL;
-    const int FS = rad ? m->plan.d.FS : m->mplan.d.FS;
-    int base[FC_COUNT + 1];
-    if (rad) {
-      const radial::Dims& d = m->plan.d;
-      const int b[FC_COUNT] = {d.f_bus_p, d.f_bus_q, d.f_bus_vm, d.f_bus_va, d.f_bus_im, d.f_bus_ia, d.f_dev_p, d.f_dev_q, d.f_des_soc,
-                               d.f_gen_pmax, d.f_br_p, d.f_br_q, d.f_br_s, d.f_br_im, d.f_br_ia};
-      for (unsigned c = 0; c < FC_COUNT; ++c) base[c] = b[c];
-    } else {
-      const mesh::Dims& d = m->mplan.d;
-      const int b[FC_COUNT] = {d.f_bus_p, d.f_bus_q, d.f_bus_vm, d.f_bus_va, d.f_bus_im, d.f_bus_ia, d.f_dev_p, d.f_dev_q, d.f_des_soc,
-                               d.f_gen_pmax, d.f_br_p, d.f_br_q, d.f_br_s, d.f_br_im, d.f_br_ia};
-      for (unsigned c = 0; c < FC_COUNT; ++c) base[c] = b[c];
-    }
-    base[FC_COUNT] = FS;
-    unsigned need = 0;
-    std::vector<int32_t> idx(2 * size_t(n_obs));
-    for (int k = 0; k < n_obs; ++k) {
-      const int i = index[k];
-      // (the aux slots behind the electrical state: only the K of the task are written, anm_model_set_env)
-      if (i < 0 || i >= FS + (m->env_set ? m->K : radial::KMAX)) return fail("anm_model_set_obs: index out of range");
-      if (i < FS) {
-        unsigned c = 0;
-        while (c + 1 < FC_COUNT && base[c + 1] <= i) ++c;
-        need |= 1u << c;
-      }
-      idx[k] = idx[n_obs + k] = i;   // (both halves: the identity layout)
-    }
-    std::vector<double> tab(3 * size_t(n_obs));
-    for (int k = 0; k < n_obs; ++k) { tab[k] = scale[k]; tab[n_obs + k] = low[k]; tab[2 * n_obs + k] = high[k]; }
-    hipError_t e = hipMalloc(&m->d_obs_index, idx.size() * sizeof(int32_t));
-    if (e == hipSuccess) e = hipMalloc(&m->d_obs_tab, tab.size() * sizeof(double));
-    if (e == hipSuccess) e = hipMemcpy(m->d_obs_index, idx.data(), idx.size() * sizeof(int32_t), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(m->d_obs_tab, tab.data(), tab.size() * sizeof(double), hipMemcpyHostToDevice);
-    if (e != hipSuccess) return fail_hip(e, "anm_model_set_obs");
-    m->obs_need = need;
-    m->n_obs = n_obs;
-    return 0;
-  }
-  typedef FullState<Topo> F;
-  const int FS = F::SIZE;
-  int cls_size[FC_COUNT];
-  for (unsigned c = 0; c < FC_COUNT; ++c)
-    cls_size[c] = (c + 1 < FC_COUNT ? full_class_base<Topo>(c + 1) : FS) - full_class_base<Topo>(c);
-  unsigned need = 0;
-  for (int k = 0; k < n_obs; ++k) {
-    const int i = index[k];
-    if (i < 0 || i >= FS + (m->env_set ? m->K : Layout<Topo>::KMAX)) return fail("anm_model_set_obs: index out of range");
-    if (i < FS) {
-      unsigned c = 0;
-      while (c + 1 < FC_COUNT && full_class_base<Topo>(c + 1) <= i) ++c;
-      need |= 1u << c;
-    }
-  }
-  int off = 0;
-  for (unsigned c = 0; c < FC_COUNT; ++c) {
-    m->obs_cls_off[c] = short(off);
-    if ((need >> c) & 1u) off += cls_size[c];
-  }
-  m->obs_need = need;
-  m->obs_aux_off = off;
-  m->obs_row_stride = (off + Layout<Topo>::KMAX) | 1;
+  // the family in use: the offsets of `full` (the same in all three, full_offsets), the aux slots a row has behind them
+  const bool thread = m->impl == ANM_IMPL_THREAD;
+  const int* base = m->full.base;
+  const int FS = base[FC_COUNT], aux_slots = thread ? int(Layout<Topo>::KMAX) : int(radial::KMAX);
+  auto class_of = [&](int i) {
+    unsigned c = 0;
+    while (c + 1 < FC_COUNT && base[c + 1] <= i) ++c;
+    return c;
+  };
+  unsigned need = 0;   // the classes the list reads
   std::vector<int32_t> idx(2 * size_t(n_obs));
   for (int k = 0; k < n_obs; ++k) {
     const int i = index[k];
-    idx[n_obs + k] = i;  // identity layout: FullState offsets, aux behind them
-    if (i >= FS) {
-      idx[k] = m->obs_aux_off + (i - FS);
-    } else {
-      unsigned c = 0;
-      while (c + 1 < FC_COUNT && full_class_base<Topo>(c + 1) <= i) ++c;
-      idx[k] = m->obs_cls_off[c] + (i - full_class_base<Topo>(c));
+    // (the aux slots behind the electrical state: only the K of the task are written, anm_model_set_env)
+    if (i < 0 || i >= FS + (m->env_set ? m->K : aux_slots)) return fail("anm_model_set_obs: index out of range");
+    if (i < FS) need |= 1u << class_of(i);
+    idx[k] = idx[n_obs + k] = i;   // (both halves: the identity layout -- `full` offsets, aux behind them)
+  }
+  if (thread) {
+    // thread family: rows of the compact layout (only the classes the list reads) unless the dump is asked for; the
+    // first half of the indices points into those.  The lane-group families gather from the identity layout alone
+    int off = 0;
+    for (unsigned c = 0; c < FC_COUNT; ++c) {
+      m->obs_cls_off[c] = short(off);
+      if ((need >> c) & 1u) off += base[c + 1] - base[c];
+    }
+    m->obs_aux_off = off;
+    m->obs_row_stride = (off + Layout<Topo>::KMAX) | 1;
+    for (int k = 0; k < n_obs; ++k) {
+      const int i = index[k];
+      idx[k] = i >= FS ? m->obs_aux_off + (i - FS) : m->obs_cls_off[class_of(i)] + (i - base[class_of(i)]);
     }
   }
   std::vector<double> tab(3 * size_t(n_obs));
@@ -939,19 +852,20 @@ int anm_model_set_obs(anm_model* m, int32_t n_obs, const int32_t* index, const d
   if (e == hipSuccess) e = hipMemcpy(m->d_obs_index, idx.data(), idx.size() * sizeof(int32_t), hipMemcpyHostToDevice);
   if (e == hipSuccess) e = hipMemcpy(m->d_obs_tab, tab.data(), tab.size() * sizeof(double), hipMemcpyHostToDevice);
   if (e != hipSuccess) return fail_hip(e, "anm_model_set_obs");
+  m->obs_need = need;
   m->n_obs = n_obs;
   return 0;
 }
 
 int anm_model_set_impl(anm_model* m, int32_t impl) {
   if (!m) return fail("anm_model_set_impl: null model");
-  if (impl == ANM_IMPL_RADIAL && !m->radial_ok)
+  if (impl == ANM_IMPL_RADIAL && !m->t_radial.ok)
     return fail("the lane-group kernel needs a radial (tree) network with at most 64 buses and devices");
-  if (impl == ANM_IMPL_MESH && !m->mesh_ok)
+  if (impl == ANM_IMPL_MESH && !m->t_mesh.ok)
     return fail("the general lane-group kernel needs a network of at most 65 buses, 128 branches, 64 devices");
   if (impl != ANM_IMPL_THREAD && impl != ANM_IMPL_RADIAL && impl != ANM_IMPL_MESH)
     return fail("anm_model_set_impl: unknown implementation");
-  if (impl == ANM_IMPL_THREAD && !m->tpe_ok)
+  if (impl == ANM_IMPL_THREAD && !m->t_thread.ok)
     return fail("this library was compiled for another topology: only the generic lane-group kernel is available");
   if (impl == ANM_IMPL_THREAD && m->class_per_env)
     return fail("anm_model_set_impl: the bound parameter classes change inside blocks of 64 environments: only a "
@@ -990,32 +904,12 @@ int anm_transition_f64(anm_model* m, int64_t n, const double* p_load, const doub
   int prec;
   SolverOpts so = solver(opts, prec);
   hipStream_t s = static_cast<hipStream_t>(stream);
-  if (m->impl == ANM_IMPL_RADIAL || m->impl == ANM_IMPL_MESH) {
-    radial::IO rio{};
-    rio.mode = 0;
-    rio.t = io;
-    return m->impl == ANM_IMPL_MESH ? launch_mesh(m, prec, n, s, rio, so) : launch_radial(m, prec, n, s, rio, so);
-  }
-  cptr_t C = (cptr_t)m->d_const;
-  const bool viewed = m->has_view;
-  if (io.nr_start) {
-    if (prec == ANM_SOLVE_F32)
-      hipLaunchKernelGGL((k_transition<float, true, true>), dim3(grid_for(n)), dim3(BLOCK), 0, s, C, io, so, n, class_sel(m, false), m->view);
-    else
-      hipLaunchKernelGGL((k_transition<double, true, true>), dim3(grid_for(n)), dim3(BLOCK), 0, s, C, io, so, n, class_sel(m, false), m->view);
-  } else if (viewed) {
-
-    if (prec == ANM_SOLVE_F32)
-      hipLaunchKernelGGL((k_transition<float, true>), dim3(grid_for(n)), dim3(BLOCK), 0, s, C, io, so, n, class_sel(m, false), m->view);
-    else
-      hipLaunchKernelGGL((k_transition<double, true>), dim3(grid_for(n)), dim3(BLOCK), 0, s, C, io, so, n, class_sel(m, false), m->view);
-  } else if (prec == ANM_SOLVE_F32)
-    hipLaunchKernelGGL((k_transition<float, false>), dim3(grid_for(n)), dim3(BLOCK), 0, s, C, io, so, n, class_sel(m, false), m->view);
-  else
-    hipLaunchKernelGGL((k_transition<double, false>), dim3(grid_for(n)), dim3(BLOCK), 0, s, C, io, so, n, class_sel(m, false), m->view);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return fail_hip(e, "launch k_transition");
-  return 0;
+  if (on_lane_groups(m)) return launch_lane_groups(m, 0, &io, nullptr, prec, n, s, so);
+  return by_precision(prec, [&](auto jt) {
+    using JT = decltype(jt);
+    auto kern = io.nr_start ? k_transition<JT, true, true> : m->has_view ? k_transition<JT, true> : k_transition<JT, false>;
+    return launch("launch k_transition", kern, grid_for(n), BLOCK, 0, s, (cptr_t)m->t_thread.dev, io, so, n, class_sel(m, m->t_thread), m->view);
+  });
 }
 
 int anm_reset_f64(anm_model* m, int64_t n, const double* init_state, const uint8_t* mask, uint64_t rng_seed,
@@ -1050,26 +944,12 @@ int anm_reset_f64(anm_model* m, int64_t n, const double* init_state, const uint8
   int prec;
   SolverOpts so = solver(opts, prec);
   hipStream_t s = static_cast<hipStream_t>(stream);
-  if (m->impl == ANM_IMPL_RADIAL || m->impl == ANM_IMPL_MESH) {
-    radial::IO rio{};
-    rio.mode = 1;
-    rio.e = io;
-    return m->impl == ANM_IMPL_MESH ? launch_mesh(m, prec, n, s, rio, so) : launch_radial(m, prec, n, s, rio, so);
-  }
-  cptr_t C = (cptr_t)m->d_const;
-  const bool viewed = m->has_view;
-  if (viewed) {
-    if (prec == ANM_SOLVE_F32)
-      hipLaunchKernelGGL((k_reset<float, true>), dim3(grid_for(n)), dim3(BLOCK), 0, s, C, io, so, n, class_sel(m, false), m->view);
-    else
-      hipLaunchKernelGGL((k_reset<double, true>), dim3(grid_for(n)), dim3(BLOCK), 0, s, C, io, so, n, class_sel(m, false), m->view);
-  } else if (prec == ANM_SOLVE_F32)
-    hipLaunchKernelGGL((k_reset<float, false>), dim3(grid_for(n)), dim3(BLOCK), 0, s, C, io, so, n, class_sel(m, false), m->view);
-  else
-    hipLaunchKernelGGL((k_reset<double, false>), dim3(grid_for(n)), dim3(BLOCK), 0, s, C, io, so, n, class_sel(m, false), m->view);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return fail_hip(e, "launch k_reset");
-  return 0;
+  if (on_lane_groups(m)) return launch_lane_groups(m, 1, nullptr, &io, prec, n, s, so);
+  return by_precision(prec, [&](auto jt) {
+    using JT = decltype(jt);
+    return launch("launch k_reset", m->has_view ? k_reset<JT, true> : k_reset<JT, false>, grid_for(n), BLOCK, 0, s, (cptr_t)m->t_thread.dev, io,
+                  so, n, class_sel(m, m->t_thread), m->view);
+  });
 }
 
 int anm_sample_init_state_f64(anm_model* m, int64_t n, uint64_t rng_seed, uint64_t env_offset, const int32_t* reset_count,
@@ -1080,12 +960,9 @@ int anm_sample_init_state_f64(anm_model* m, int64_t n, uint64_t rng_seed, uint64
   if (m->d_env_class) return fail("anm_sample_init_state_f64: not while parameter classes are bound (the table is class 0's)");
   if (n <= 0) return 0;
   const int n_blocks = 1 + (m->s_ngen + m->s_ndes + 1) / 2;
-  hipLaunchKernelGGL(k_sample_init_state, dim3(unsigned((n + 255) / 256)), dim3(256), 0, static_cast<hipStream_t>(stream), n,
-                     m->s_nd, m->s_nload, m->s_ngen, m->s_ndes, m->d_samp, m->d_series, m->period, rng_seed, env_offset,
-                     reset_count, init_state, raw, n_blocks);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return fail_hip(e, "launch k_sample_init_state");
-  return 0;
+  return launch("launch k_sample_init_state", k_sample_init_state, unsigned((n + 255) / 256), 256, 0, static_cast<hipStream_t>(stream), n,
+                m->s_nd, m->s_nload, m->s_ngen, m->s_ndes, m->d_samp, (const double*)m->d_series, m->period, rng_seed, env_offset,
+                (const int32_t*)reset_count, init_state, raw, n_blocks);
 }
 
 static int make_step_io(anm_model* m, const double* action, const double* exo, const double* aux_next, double* soc,
@@ -1096,10 +973,9 @@ static int make_step_io(anm_model* m, const double* action, const double* exo, c
   if (!m) return fail("anm_step_f64: null model");
   if (!m->env_set) return fail("anm_step_f64: call anm_model_set_env first");
   // (a network without set-point devices has an empty action vector: examples/simple_env.py of the reference)
-  const int action_dim = 2 * (m->tpe_ok ? Topo::NSET : (m->radial_ok ? m->plan.d.NSET : m->mplan.d.NSET));
-  if ((!action && action_dim > 0) || !state || !terminated || !obs || !reward || !e_loss || !penalty)
+  if ((!action && m->dims.action_dim > 0) || !state || !terminated || !obs || !reward || !e_loss || !penalty)
     return fail("anm_step_f64: null argument");
-  if ((m->tpe_ok ? Topo::NDES : (m->radial_ok ? m->plan.d.NDES : m->mplan.d.NDES)) > 0 && !soc) return fail("anm_step_f64: null soc");
+  if (m->dims.n_des > 0 && !soc) return fail("anm_step_f64: null soc");
   const bool series = exo == nullptr;
   if (series && m->period <= 0) return fail("anm_step_f64: no exo given and the model has no series (set_env)");
   if (!series && m->K > 0 && !aux_next) return fail("anm_step_f64: exo given without aux_next");
@@ -1128,8 +1004,8 @@ static int make_step_io(anm_model* m, const double* action, const double* exo, c
   io.aux_index = aux_index;
   io.state_same = m->d_state_same;
   io.n_obs = 0;
-  io.state_magic = magic_div((m->tpe_ok ? Topo::SDIM : (m->radial_ok ? m->plan.d.SDIM : m->mplan.d.SDIM)) + m->K);
-  if (m->tpe_ok && m->impl == ANM_IMPL_THREAD && (m->n_obs > 0 || full)) {
+  io.state_magic = magic_div(m->dims.state_base_dim + m->K);
+  if (m->t_thread.ok && m->impl == ANM_IMPL_THREAD && (m->n_obs > 0 || full)) {
     // rows of the electrical state in LDS: identity layout when the dump is asked for, else only the classes
     // the observation list reads
     const bool ident = full != nullptr;
@@ -1156,7 +1032,7 @@ static int make_step_io(anm_model* m, const double* action, const double* exo, c
     io.obs_hi = m->d_obs_tab + 2 * m->n_obs;
   }
   io.ws = nullptr;
-  if (ws && ws->buf && m->tpe_ok && !m->d_env_class) {  // (the straggler launch packs records of all blocks together)
+  if (ws && ws->buf && m->t_thread.ok && !m->d_env_class) {  // (the straggler launch packs records of all blocks together)
     // records, then the int32 list of the records the first straggler launch leaves to the second
     const int64_t cap = 2 * (ws->n_doubles - Rec<Topo>::HEADER) / (2 * Rec<Topo>::SIZE + 1);
     if (cap < 1 || ws->iter_cap < 1) return fail("anm_step_f64: step workspace too small or iter_cap < 1");
@@ -1174,17 +1050,16 @@ static int launch_step(anm_model* m, const EnvIO& io_in, int64_t n, const anm_so
   EnvIO io = io_in;
   int prec;
   SolverOpts so = solver(opts, prec);
-  if (m->impl == ANM_IMPL_RADIAL || m->impl == ANM_IMPL_MESH) {
-    if (io.state_same) {
-      hipError_t em = hipMemsetAsync(io.state_same, 0, size_t(n), s);
-      if (em != hipSuccess) return fail_hip(em, "hipMemsetAsync(state_same)");
-    }
-    radial::IO rio{};
-    rio.mode = 2;
-    rio.e = io;
-    return m->impl == ANM_IMPL_MESH ? launch_mesh(m, prec, n, s, rio, so) : launch_radial(m, prec, n, s, rio, so);
+  auto clear_state_same = [&]() {   // a kernel that writes every state row: no row is "the same as obs and left out"
+    hipError_t em = io.state_same ? hipMemsetAsync(io.state_same, 0, size_t(n), s) : hipSuccess;
+    return em == hipSuccess ? 0 : fail_hip(em, "hipMemsetAsync(state_same)");
+  };
+  if (on_lane_groups(m)) {
+    if (int rc = clear_state_same()) return rc;
+    return launch_lane_groups(m, 2, nullptr, &io, prec, n, s, so);
   }
-  cptr_t C = (cptr_t)m->d_const;
+  const cptr_t C = (cptr_t)m->t_thread.dev;
+  const unsigned grid = grid_for(n);
   if (m->has_view) {
     // a batch view: per-lane rows (the coalesced-row kernels need 64 consecutive environments)
     if (io.K > 1) return fail("anm_step_f64: a batch view in the thread-per-environment family takes K <= 1 auxiliary variables (use the general lane-group family)");
@@ -1193,64 +1068,37 @@ static int launch_step(anm_model* m, const EnvIO& io_in, int64_t n, const anm_so
     io.state_same = nullptr;
     io.aux_stride = m->view.w_aux;
     const bool dense = m->view_waves ? m->view_waves == 2 : n > int64_t(2) * 64 * 4 * 256;   // more than two wavefronts per SIMD of the chip
-    if (prec == ANM_SOLVE_F32) {
-      if (dense) hipLaunchKernelGGL((k_step_view<float, 2>), dim3(grid_for(n)), dim3(BLOCK), 0, s, C, io, so, n, m->view);
-      else hipLaunchKernelGGL((k_step_view<float, 1>), dim3(grid_for(n)), dim3(BLOCK), 0, s, C, io, so, n, m->view);
-    } else {
-      if (dense) hipLaunchKernelGGL((k_step_view<double, 2>), dim3(grid_for(n)), dim3(BLOCK), 0, s, C, io, so, n, m->view);
-      else hipLaunchKernelGGL((k_step_view<double, 1>), dim3(grid_for(n)), dim3(BLOCK), 0, s, C, io, so, n, m->view);
-    }
-    hipError_t ev = hipGetLastError();
-    if (ev != hipSuccess) return fail_hip(ev, "launch k_step_view");
-    return 0;
+    return by_precision(prec, [&](auto jt) {
+      using JT = decltype(jt);
+      return launch("launch k_step_view", dense ? k_step_view<JT, 2> : k_step_view<JT, 1>, grid, BLOCK, 0, s, C, io, so, n, m->view);
+    });
   }
+  const ClassSel cs = class_sel(m, m->t_thread);
   if (io.aux_index && io.exo == nullptr && io.K == 1 && !io.full && io.n_obs == 0) {
     // fast path: series mode, "state" observation, nothing but the batch tensors
-    if (prec == ANM_SOLVE_F32)
-      hipLaunchKernelGGL((k_step_rows<float, false>), dim3(grid_for(n)), dim3(BLOCK), 0, s, C, io, so, n, class_sel(m, false));
-    else
-      hipLaunchKernelGGL((k_step_rows<double, false>), dim3(grid_for(n)), dim3(BLOCK), 0, s, C, io, so, n, class_sel(m, false));
-    hipError_t e2 = hipGetLastError();
-    if (e2 != hipSuccess) return fail_hip(e2, "launch k_step_rows");
-    if (io.ws && io.iter_cap < so.max_iter) {
-      // second launch: the handed-over solves, grid-stride over the records (count lives on the device)
-      // (a tree topology continues them on lane groups, 8 records per wavefront, unless that was switched off)
-      constexpr bool CAN_GROUP = Topo::TREE != 0;
-      const bool groups = CAN_GROUP && so.handoff >= 0;
-      const int per_block = groups ? group::Shape<Topo>::NG : BLOCK;
-      const unsigned g2 = unsigned((io.ws_cap + per_block - 1) / per_block);  // covers every record
-      const bool two_level = groups && io.mid_cap > 0 && io.mid_cap < so.max_iter;
-      for (int level = 1; level <= (two_level ? 2 : 1); ++level) {
-        const unsigned g = g2;  // (level 2: most wavefronts find nothing and leave)
-        if constexpr (CAN_GROUP) {
-          if (groups) {
-            if (prec == ANM_SOLVE_F32)
-              hipLaunchKernelGGL((k_step_stragglers<float, true>), dim3(g), dim3(BLOCK), 0, s, C, io, so, level);
-            else
-              hipLaunchKernelGGL((k_step_stragglers<double, true>), dim3(g), dim3(BLOCK), 0, s, C, io, so, level);
-          }
-        }
-        if (!groups) {
-          if (prec == ANM_SOLVE_F32)
-            hipLaunchKernelGGL((k_step_stragglers<float, false>), dim3(g), dim3(BLOCK), 0, s, C, io, so, level);
-          else
-            hipLaunchKernelGGL((k_step_stragglers<double, false>), dim3(g), dim3(BLOCK), 0, s, C, io, so, level);
-        }
-        e2 = hipGetLastError();
-        if (e2 != hipSuccess) return fail_hip(e2, "launch k_step_stragglers");
-      }
-      const unsigned g3 = unsigned((int64_t(io.ws_cap) * SCATTER_LANES + 255) / 256);
-      hipLaunchKernelGGL(k_step_scatter, dim3(g3), dim3(256), 0, s, io);
-      e2 = hipGetLastError();
-      if (e2 != hipSuccess) return fail_hip(e2, "launch k_step_scatter");
-    }
-    return 0;
+    int rc = by_precision(prec, [&](auto jt) {
+      return launch("launch k_step_rows", k_step_rows<decltype(jt), false>, grid, BLOCK, 0, s, C, io, so, n, cs);
+    });
+    if (rc || !(io.ws && io.iter_cap < so.max_iter)) return rc;
+    // second launch: the handed-over solves, grid-stride over the records (count lives on the device)
+    // (a tree topology continues them on lane groups, 8 records per wavefront, unless that was switched off)
+    const bool groups = Topo::TREE != 0 && so.handoff >= 0;
+    const int per_block = groups ? group::Shape<Topo>::NG : BLOCK;
+    const unsigned g2 = unsigned((io.ws_cap + per_block - 1) / per_block);  // covers every record
+    const bool two_level = groups && io.mid_cap > 0 && io.mid_cap < so.max_iter;
+    for (int level = 1; level <= (two_level ? 2 : 1) && rc == 0; ++level)   // (level 2: most wavefronts find nothing and leave)
+      rc = by_precision(prec, [&](auto jt) {
+        using JT = decltype(jt);
+        if constexpr (Topo::TREE != 0)
+          if (groups) return launch("launch k_step_stragglers", k_step_stragglers<JT, true>, g2, BLOCK, 0, s, C, io, so, level);
+        return launch("launch k_step_stragglers", k_step_stragglers<JT, false>, g2, BLOCK, 0, s, C, io, so, level);
+      });
+    if (rc) return rc;
+    const unsigned g3 = unsigned((int64_t(io.ws_cap) * SCATTER_LANES + 255) / 256);
+    return launch("launch k_step_scatter", k_step_scatter, g3, 256, 0, s, io);
   }
   io.ws = nullptr;
-  if (io.state_same) {  // this kernel writes every state row: no row is "the same as obs and left out"
-    hipError_t em = hipMemsetAsync(io.state_same, 0, size_t(n), s);
-    if (em != hipSuccess) return fail_hip(em, "hipMemsetAsync(state_same)");
-  }
+  if (int rc = clear_state_same()) return rc;
   if (io.full && !GenLds<Topo>::FULL_OK) {  // rows too wide for LDS: plain per-lane dump, no fused list
     io.n_obs = 0;
   }
@@ -1261,13 +1109,9 @@ static int launch_step(anm_model* m, const EnvIO& io_in, int64_t n, const anm_so
   if (GenLds<Topo>::FULL_OK && (io.n_obs > 0 || io.full)) doubles = std::max(doubles, size_t(64) * size_t(io.row_stride));
   io.state_row_off = int(doubles);               // the state rows follow the buffer the other uses overlay
   const size_t lds_bytes = (doubles + size_t(64) * size_t(S | 1)) * sizeof(double);
-  if (prec == ANM_SOLVE_F32)
-    hipLaunchKernelGGL(k_step_general<float>, dim3(grid_for(n)), dim3(BLOCK), lds_bytes, s, C, io, so, n, class_sel(m, false));
-  else
-    hipLaunchKernelGGL(k_step_general<double>, dim3(grid_for(n)), dim3(BLOCK), lds_bytes, s, C, io, so, n, class_sel(m, false));
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return fail_hip(e, "launch k_step_general");
-  return 0;
+  return by_precision(prec, [&](auto jt) {
+    return launch("launch k_step_general", k_step_general<decltype(jt)>, grid, BLOCK, lds_bytes, s, C, io, so, n, cs);
+  });
 }
 
 int anm_step_f64(anm_model* m, int64_t n, const double* action, const double* exo, const double* aux_next,
@@ -1324,11 +1168,8 @@ int anm_gather_obs_f64(int64_t n, int32_t full_dim, const double* full, int32_t 
   if (n <= 0 || n_obs <= 0) return 0;
   const int64_t total = n * n_obs;
   unsigned grid = unsigned(std::min<int64_t>((total + 255) / 256, 2048));
-  hipLaunchKernelGGL(k_gather_obs, dim3(grid), dim3(256), 0, static_cast<hipStream_t>(stream), n, full_dim, full,
-                     state_dim, K, state, terminated, n_obs, index, scale, low, high, obs);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return fail_hip(e, "launch k_gather_obs");
-  return 0;
+  return launch("launch k_gather_obs", k_gather_obs, grid, 256, 0, static_cast<hipStream_t>(stream), n, int(full_dim), full, int(state_dim),
+                int(K), state, terminated, int(n_obs), index, scale, low, high, obs);
 }
 
 #ifdef ANM_PHASE_TIMING

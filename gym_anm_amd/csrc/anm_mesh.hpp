@@ -223,11 +223,7 @@ inline bool build_plan_zone(const anm_network_desc& n, Plan& P, std::string& err
   while (d.G < need) d.G *= 2;
   d.br_slots = (d.NBR + d.G - 1) / d.G;
   const int G = d.G, NB = d.NB;
-  d.f_bus_p = 0; d.f_bus_q = d.f_bus_p + NB; d.f_bus_vm = d.f_bus_q + NB; d.f_bus_va = d.f_bus_vm + NB;
-  d.f_bus_im = d.f_bus_va + NB; d.f_bus_ia = d.f_bus_im + NB; d.f_dev_p = d.f_bus_ia + NB;
-  d.f_dev_q = d.f_dev_p + d.ND; d.f_des_soc = d.f_dev_q + d.ND; d.f_gen_pmax = d.f_des_soc + d.NDES;
-  d.f_br_p = d.f_gen_pmax + d.NGEN; d.f_br_q = d.f_br_p + d.NBR; d.f_br_s = d.f_br_q + d.NBR;
-  d.f_br_im = d.f_br_s + d.NBR; d.f_br_ia = d.f_br_im + d.NBR; d.FS = d.f_br_ia + d.NBR;
+  set_full_offsets(d);   // full-state layout
 
   // ---- Y (dense on the host; parallel branches between the same pair of buses are not supported, as in
   // the reference whose Y[f, t] assignment keeps only the last one: refuse instead of silently differing)

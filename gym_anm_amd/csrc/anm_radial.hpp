@@ -99,12 +99,7 @@ inline bool build_plan(const anm_network_desc& n, Plan& P, std::string& err) {
   d.G = 8;
   while (d.G < need) d.G *= 2;
   const int G = d.G;
-  // full-state layout
-  d.f_bus_p = 0; d.f_bus_q = d.f_bus_p + d.NB; d.f_bus_vm = d.f_bus_q + d.NB; d.f_bus_va = d.f_bus_vm + d.NB;
-  d.f_bus_im = d.f_bus_va + d.NB; d.f_bus_ia = d.f_bus_im + d.NB; d.f_dev_p = d.f_bus_ia + d.NB;
-  d.f_dev_q = d.f_dev_p + d.ND; d.f_des_soc = d.f_dev_q + d.ND; d.f_gen_pmax = d.f_des_soc + d.NDES;
-  d.f_br_p = d.f_gen_pmax + d.NGEN; d.f_br_q = d.f_br_p + d.NBR; d.f_br_s = d.f_br_q + d.NBR;
-  d.f_br_im = d.f_br_s + d.NBR; d.f_br_ia = d.f_br_im + d.NBR; d.FS = d.f_br_ia + d.NBR;
+  set_full_offsets(d);   // full-state layout
 
   // tree rooted at the slack bus: BFS gives parent bus and the branch to it
   std::vector<std::vector<std::pair<int, int>>> adj(d.NB);  // (neighbour, branch)
