@@ -44,6 +44,7 @@ class EnvConfig(C.Structure):
     _fields_ = [
         ("K", C.c_int32), ("gamma", C.c_double), ("clip_e_loss", C.c_double), ("clip_penalty", C.c_double),
         ("obs_low", c_double_p), ("obs_high", c_double_p), ("series", c_double_p), ("period", C.c_int32),
+        ("exo_mode", C.c_int32), ("exo_low", c_double_p), ("exo_high", c_double_p),
     ]  # fmt: skip
 
 
@@ -79,6 +80,7 @@ class FullLayout(C.Structure):
 
 
 SOLVE_F64, SOLVE_F32 = 0, 1
+EXO_HOST, EXO_UNIFORM = 0, 1   # anm_env_config.exo_mode
 IMPL_THREAD, IMPL_RADIAL, IMPL_MESH = 0, 1, 2
 HANDOFF_NEVER, HANDOFF_AUTO = -1, -2
 

@@ -155,14 +155,23 @@ __global__ void k_gather_obs(int64_t n, int full_dim, const double* __restrict__
 __global__ void k_sample_init_state(int64_t n, int nd, int nload, int ngen, int ndes, const double* __restrict__ tab,
                                     const double* __restrict__ series, int period, uint64_t seed, uint64_t env_offset,
                                     const int32_t* __restrict__ reset_count, double* __restrict__ out, uint32_t* __restrict__ raw,
-                                    int n_blocks) {
+                                    int n_blocks, const double* __restrict__ exo_lo) {
+  // exo_lo != null: the uniform exogenous mode (low ends [nload + ngen], the high ends behind them) -- step index 0, loads
+  // and generator P / P_max from the step stream at index 0 instead of the series, block 0 unused
   const int64_t e = int64_t(blockIdx.x) * blockDim.x + threadIdx.x;
   if (e >= n) return;
   const int W = 2 * nd + ndes + ngen + 1;
   const uint32_t epoch = reset_count ? uint32_t(reset_count[e]) : 0u;
-  uint32_t r[4];
-  Philox::generate(seed, env_offset + uint64_t(e), epoch, 0u, r);
-  const int aux = int((uint64_t(r[0]) * uint64_t(period)) >> 32);
+  int aux = 0;
+  uint64_t key = 0;
+  const int nexo = nload + ngen;
+  if (exo_lo) {
+    key = ExoUniform::episode_key(seed, env_offset + uint64_t(e), epoch);
+  } else {
+    uint32_t r[4];
+    Philox::generate(seed, env_offset + uint64_t(e), epoch, 0u, r);
+    aux = int((uint64_t(r[0]) * uint64_t(period)) >> 32);
+  }
   double* s0 = out + e * W;
   for (int k = 0; k < W; ++k) s0[k] = 0.0;
   s0[W - 1] = double(aux);
@@ -170,7 +179,7 @@ __global__ void k_sample_init_state(int64_t n, int nd, int nload, int ngen, int 
     const double* t = tab + 6 * d;
     const int typ = int(t[0]), slot = int(t[1]);
     if (typ == DEV_LOAD) {
-      s0[d] = series[slot * period + aux];
+      s0[d] = exo_lo ? ExoUniform::draw(key, 0u, slot, exo_lo[slot], exo_lo[nexo + slot]) : series[slot * period + aux];
     } else if (typ == DEV_CLASSICAL || typ == DEV_RENEWABLE || typ == DEV_STORAGE) {
       const bool des = typ == DEV_STORAGE;
       const int u = des ? ngen + slot : slot;
@@ -180,7 +189,8 @@ __global__ void k_sample_init_state(int64_t n, int nd, int nload, int ngen, int 
       if (des) {
         s0[2 * nd + slot] = t[4] + (t[5] - t[4]) * uu;
       } else {
-        const double pm = series[(nload + slot) * period + aux];
+        const double pm = exo_lo ? ExoUniform::draw(key, 0u, nload + slot, exo_lo[nload + slot], exo_lo[nexo + nload + slot])
+                                 : series[(nload + slot) * period + aux];
         s0[d] = pm;
         s0[2 * nd + ndes + slot] = pm;
         s0[nd + d] = t[2] + (t[3] - t[2]) * uu;
@@ -249,6 +259,10 @@ struct anm_model {
   int32_t* d_zero = nullptr;                  // one zero: the class of every environment when no classes are bound
   double* d_samp = nullptr;                   // [n_dev][6] sampler table (anm_sample_init_state_f64)
   int s_nd = 0, s_nload = 0, s_ngen = 0, s_ndes = 0;
+  // uniform exogenous mode (anm_env_config.exo_mode)
+  int exo_mode = ANM_EXO_HOST;
+  std::vector<double> exo_default;            // [2][n_load + n_gen] MW: loads [p_min, 0], generators [0, p_max]
+  double* d_exo = nullptr;                    // [2][n_load + n_gen] MW: low, high of every unit
   std::vector<cplx> ybus;
 
   std::array<Tables*, 3> tables() { return {&t_thread, &t_radial, &t_mesh}; }
@@ -570,6 +584,14 @@ int anm_model_create(const anm_network_desc* desc, anm_model** out) {
       o[0] = t; o[1] = slot; o[2] = desc->dev_qmin[k]; o[3] = desc->dev_qmax[k];
       o[4] = t == DEV_STORAGE ? desc->dev_soc_min[k] : 0.0; o[5] = t == DEV_STORAGE ? desc->dev_soc_max[k] : 0.0;
     }
+    // default ends of the uniform exogenous mode, in MW, by unit (loads by device id, then non-slack generators)
+    const int nexo = m->s_nload + m->s_ngen;
+    m->exo_default.assign(2 * size_t(nexo), 0.0);
+    for (int k = 0; k < desc->n_dev; ++k) {
+      const int t = desc->dev_type[k], slot = int(tab[6 * size_t(k) + 1]);
+      if (t == DEV_LOAD) m->exo_default[slot] = desc->dev_pmin[k] * desc->base_mva;
+      else if (t == DEV_CLASSICAL || t == DEV_RENEWABLE) m->exo_default[nexo + m->s_nload + slot] = desc->dev_pmax[k] * desc->base_mva;
+    }
     if (hipMalloc(&m->d_samp, tab.size() * sizeof(double) + 8) != hipSuccess ||
         hipMemcpy(m->d_samp, tab.data(), tab.size() * sizeof(double), hipMemcpyHostToDevice) != hipSuccess)
       rc = fail("hipMalloc(sampler table)");
@@ -585,6 +607,7 @@ void anm_model_destroy(anm_model* m) {
   if (m->d_series) hipFree(m->d_series);
   if (m->d_zero) hipFree(m->d_zero);
   if (m->d_samp) hipFree(m->d_samp);
+  if (m->d_exo) hipFree(m->d_exo);
   if (m->d_obs_index) hipFree(m->d_obs_index);
   if (m->d_obs_tab) hipFree(m->d_obs_tab);
   delete m;
@@ -633,6 +656,27 @@ int anm_model_set_env(anm_model* m, const anm_env_config* cfg) {
     if (e != hipSuccess) return fail_hip(e, "hipMemcpy(series)");
     m->period = cfg->period;
   }
+  m->exo_mode = ANM_EXO_HOST;
+  if (cfg->exo_mode != ANM_EXO_HOST) {
+    if (cfg->exo_mode != ANM_EXO_UNIFORM) return fail("anm_model_set_env: unknown exo_mode");
+    if (cfg->K != 1) return fail("anm_model_set_env: the uniform exogenous mode needs exactly K = 1 auxiliary variable (the step index)");
+    if (m->period > 0) return fail("anm_model_set_env: the uniform exogenous mode and a series do not go together");
+    if (m->n_classes() > 1 || m->d_env_class) return fail("anm_model_set_env: the uniform exogenous mode does not take parameter classes");
+    const int nexo = m->dims.n_load + m->dims.n_gen;
+    if (int(m->exo_default.size()) != 2 * nexo) return fail("anm_model_set_env: no default ends for the uniform exogenous mode");
+    std::vector<double> ends(m->exo_default);
+    for (int k = 0; k < nexo; ++k) {
+      if (cfg->exo_low) ends[k] = cfg->exo_low[k];
+      if (cfg->exo_high) ends[nexo + k] = cfg->exo_high[k];
+      if (!std::isfinite(ends[k]) || !std::isfinite(ends[nexo + k]) || !(ends[k] <= ends[nexo + k]))
+        return fail("anm_model_set_env: the ends of the uniform exogenous mode must be finite with exo_low <= exo_high");
+    }
+    hipError_t e = m->d_exo ? hipSuccess : hipMalloc(&m->d_exo, sizeof(double) * size_t(2 * nexo) + 8);
+    if (e != hipSuccess) return fail_hip(e, "hipMalloc(exo ends)");
+    e = hipMemcpy(m->d_exo, ends.data(), sizeof(double) * ends.size(), hipMemcpyHostToDevice);
+    if (e != hipSuccess) return fail_hip(e, "hipMemcpy(exo ends)");
+    m->exo_mode = ANM_EXO_UNIFORM;
+  }
   m->env_set = true;
   return upload_const(m);
 }
@@ -642,6 +686,7 @@ int anm_model_set_classes(anm_model* m, int32_t n_classes, const anm_network_des
   if (n_classes > 1 && m->has_view)
     return fail("anm_model_set_classes: not while a batch view is bound (anm_model_bind_view)");
   if (n_classes < 1 || n_classes > 65536) return fail("anm_model_set_classes: n_classes must be in [1, 65536]");
+  if (n_classes > 1 && m->exo_mode != ANM_EXO_HOST) return fail("anm_model_set_classes: the uniform exogenous mode does not take parameter classes");
   if (n_classes > 1 && !descs) return fail("anm_model_set_classes: null descriptions");
   std::vector<std::vector<double>> xc, xh, xm;
   for (int k = 1; k < n_classes; ++k) {
@@ -920,10 +965,16 @@ int anm_reset_f64(anm_model* m, int64_t n, const double* init_state, const uint8
   if (!m->env_set) return fail("anm_reset_f64: call anm_model_set_env first");
   if (n <= 0) return 0;
   if (!state || !obs || !converged || !terminated) return fail("anm_reset_f64: null argument");
-  if (!init_state && (m->period <= 0 || m->K != 1 || !reset_count))
-    return fail("anm_reset_f64: drawing initial states on the device needs a series-mode model and reset_count");
+  const bool uniform = m->exo_mode == ANM_EXO_UNIFORM;
+  if (!init_state && ((m->period <= 0 && !uniform) || m->K != 1 || !reset_count))
+    return fail("anm_reset_f64: drawing initial states on the device needs a series-mode or uniform-mode model and reset_count");
+  if (uniform && (m->has_view || m->d_env_class))
+    return fail("anm_reset_f64: the uniform exogenous mode goes with neither a batch view nor parameter classes");
   EnvIO io{};
   io.K = m->K;
+  io.exo_mode = m->exo_mode;
+  io.exo_lo = m->d_exo;
+  io.exo_hi = uniform ? m->d_exo + (m->dims.n_load + m->dims.n_gen) : nullptr;
   io.init_state = init_state;
   io.series = m->d_series;
   io.period = m->period;
@@ -955,14 +1006,16 @@ int anm_reset_f64(anm_model* m, int64_t n, const double* init_state, const uint8
 int anm_sample_init_state_f64(anm_model* m, int64_t n, uint64_t rng_seed, uint64_t env_offset, const int32_t* reset_count,
                               double* init_state, uint32_t* raw, void* stream) {
   if (!m || !init_state) return fail("anm_sample_init_state_f64: null argument");
-  if (!m->env_set || m->period <= 0 || m->K != 1 || !m->d_series)
-    return fail("anm_sample_init_state_f64: the model needs a series-mode task (anm_model_set_env with series, K = 1)");
+  const bool uniform = m->env_set && m->exo_mode == ANM_EXO_UNIFORM;
+  if (!uniform && (!m->env_set || m->period <= 0 || m->K != 1 || !m->d_series))
+    return fail("anm_sample_init_state_f64: the model needs a series-mode or uniform-mode task (anm_model_set_env with series or exo_mode, K = 1)");
   if (m->d_env_class) return fail("anm_sample_init_state_f64: not while parameter classes are bound (the table is class 0's)");
   if (n <= 0) return 0;
   const int n_blocks = 1 + (m->s_ngen + m->s_ndes + 1) / 2;
+  const double* exo_lo = uniform ? m->d_exo : nullptr;
   return launch("launch k_sample_init_state", k_sample_init_state, unsigned((n + 255) / 256), 256, 0, static_cast<hipStream_t>(stream), n,
                 m->s_nd, m->s_nload, m->s_ngen, m->s_ndes, m->d_samp, (const double*)m->d_series, m->period, rng_seed, env_offset,
-                (const int32_t*)reset_count, init_state, raw, n_blocks);
+                (const int32_t*)reset_count, init_state, raw, n_blocks, exo_lo);
 }
 
 static int make_step_io(anm_model* m, const double* action, const double* exo, const double* aux_next, double* soc,
@@ -977,11 +1030,21 @@ static int make_step_io(anm_model* m, const double* action, const double* exo, c
     return fail("anm_step_f64: null argument");
   if (m->dims.n_des > 0 && !soc) return fail("anm_step_f64: null soc");
   const bool series = exo == nullptr;
-  if (series && m->period <= 0) return fail("anm_step_f64: no exo given and the model has no series (set_env)");
+  const bool uniform = m->exo_mode == ANM_EXO_UNIFORM;
+  if (uniform) {
+    if (exo || aux_next) return fail("anm_step_f64: the uniform exogenous mode draws P_load / P_pot in the kernel: exo and aux_next must be NULL");
+    if (!reset_count) return fail("anm_step_f64: the uniform exogenous mode needs reset_count (the epoch is part of the key of every draw)");
+    if (m->has_view) return fail("anm_step_f64: the uniform exogenous mode does not go with a batch view (anm_model_bind_view)");
+    if (m->d_env_class) return fail("anm_step_f64: the uniform exogenous mode does not go with parameter classes (anm_model_bind_env_classes)");
+  }
+  if (series && !uniform && m->period <= 0) return fail("anm_step_f64: no exo given and the model has no series (set_env)");
   if (!series && m->K > 0 && !aux_next) return fail("anm_step_f64: exo given without aux_next");
   if (autoreset && (!series || !reset_count)) return fail("anm_step_f64: autoreset needs series mode and reset_count");
   io = EnvIO{};
   io.K = m->K;
+  io.exo_mode = m->exo_mode;
+  io.exo_lo = m->d_exo;
+  io.exo_hi = uniform ? m->d_exo + (m->dims.n_load + m->dims.n_gen) : nullptr;
   io.action = action;
   io.exo = exo;
   io.aux_next = aux_next;
@@ -1074,7 +1137,7 @@ static int launch_step(anm_model* m, const EnvIO& io_in, int64_t n, const anm_so
     });
   }
   const ClassSel cs = class_sel(m, m->t_thread);
-  if (io.aux_index && io.exo == nullptr && io.K == 1 && !io.full && io.n_obs == 0) {
+  if (io.aux_index && io.exo == nullptr && io.exo_mode == ANM_EXO_HOST && io.K == 1 && !io.full && io.n_obs == 0) {
     // fast path: series mode, "state" observation, nothing but the batch tensors
     int rc = by_precision(prec, [&](auto jt) {
       return launch("launch k_step_rows", k_step_rows<decltype(jt), false>, grid, BLOCK, 0, s, C, io, so, n, cs);

@@ -213,6 +213,11 @@ struct EnvIO {
   int32_t* ws_list2;        // records the first straggler launch did not finish (count: counter 2 of the header)
   double* nr_diff;          // [E] or null (anm_model_bind_nr_diff; reset only): ||F||inf of the final iterate
   int aux_stride;           // row stride of aux_next (0: K; a batch view pads the rows)
+  // uniform exogenous mode (anm_env_config.exo_mode; 0 = off): exo, aux_next and series are null, K = 1, the aux variable is
+  // the step index of the episode and the loads / generator potentials are drawn in the kernel (ExoUniform)
+  int exo_mode;
+  const double* exo_lo;     // [NEXO] MW (device)
+  const double* exo_hi;     // [NEXO] MW (device)
 };
 
 // Split an init_state row (anm_env.py / simulator.py:248-268) into transition inputs.
@@ -306,6 +311,57 @@ ANM_HD int sample_series_init_state(cptr_t C, const EnvIO& io, int64_t e, uint32
   return aux;
 }
 
+// Uniform exogenous mode: the loads and generator potentials of step t of the episode with key `key` (ExoUniform)
+template <class T>
+ANM_HD void exo_uniform_draws(const EnvIO& io, uint64_t key, uint32_t t, double (&x)[Dims<T>::NEXO > 0 ? Dims<T>::NEXO : 1]) {
+  constexpr int NEXO = Dims<T>::NEXO;
+  static_for<0, (NEXO + 1) / 2>([&](auto J) {
+    constexpr int j = J;
+    uint32_t q[4];
+    ExoUniform::block(key, t, uint32_t(j), q);
+    x[2 * j] = ExoUniform::map(io.exo_lo[2 * j], io.exo_hi[2 * j], Philox::u01(q[0], q[1]));
+    if constexpr (2 * j + 1 < NEXO)
+      x[2 * j + 1] = ExoUniform::map(io.exo_lo[2 * j + 1], io.exo_hi[2 * j + 1], Philox::u01(q[2], q[3]));
+  });
+}
+
+// Initial state of the uniform exogenous mode (rng.py: uniform_init_state): step index 0, loads and generator P / P_max
+// from the step stream at index 0, generator Q and storage SoC like sample_series_init_state (same blocks, same quirks);
+// block 0 of the init sampler is not used.
+template <class T>
+ANM_HD int sample_uniform_init_state(cptr_t C, const EnvIO& io, int64_t e, uint32_t epoch, double (&s0)[T::SDIM + 1]) {
+  typedef Layout<T> L;
+  const uint64_t env = io.env_offset + uint64_t(e);
+  double x[Dims<T>::NEXO > 0 ? Dims<T>::NEXO : 1];
+  exo_uniform_draws<T>(io, ExoUniform::episode_key(io.rng_seed, env, epoch), 0u, x);
+  static_for<0, T::SDIM + 1>([&](auto I) { s0[I] = 0.0; });
+  static_for<0, T::ND>([&](auto Di) {
+    constexpr int d = Di;
+    constexpr int typ = T::DEV_TYPE[d];
+    if constexpr (typ == DEV_LOAD) {
+      s0[d] = x[T::DEV_SLOT[d]];
+    } else if constexpr (typ == DEV_CLASSICAL || typ == DEV_RENEWABLE) {
+      constexpr int g = T::DEV_SLOT[d];
+      constexpr int u = g;
+      cptr_t sd = C + L::SETDEV + SD_SIZE * T::DEV_SET[d];
+      uint32_t q[4];
+      Philox::generate(io.rng_seed, env, epoch, 1u + u / 2, q);
+      const double uu = Philox::u01(q[2 * (u % 2)], q[2 * (u % 2) + 1]);
+      s0[d] = x[T::NLOAD + g];
+      s0[2 * T::ND + T::NDES + g] = x[T::NLOAD + g];
+      s0[T::ND + d] = sd[SD_QMIN] + (sd[SD_QMAX] - sd[SD_QMIN]) * uu;
+    } else if constexpr (typ == DEV_STORAGE) {
+      constexpr int u = T::NGEN + T::DEV_SLOT[d];
+      cptr_t sd = C + L::SETDEV + SD_SIZE * T::DEV_SET[d];
+      uint32_t q[4];
+      Philox::generate(io.rng_seed, env, epoch, 1u + u / 2, q);
+      const double uu = Philox::u01(q[2 * (u % 2)], q[2 * (u % 2) + 1]);
+      s0[2 * T::ND + T::DEV_SLOT[d]] = sd[SD_SOC_MIN] + (sd[SD_SOC_MAX] - sd[SD_SOC_MIN]) * uu;
+    }
+  });
+  return 0;
+}
+
 template <class T, class JT, class S0>
 ANM_HD void reset_from(cptr_t C, const EnvIO& io, SolverOpts so, int64_t e, const S0& s0, const View& v = View{}, bool act = true,
                        double* lds = nullptr) {   // act / lds: see op_transition (lanes with !act compute along and store nothing)
@@ -351,9 +407,10 @@ ANM_HD void op_reset(cptr_t C, const EnvIO& io, SolverOpts so, int64_t slot, con
   if (!ANM_WAVE_ANY(act)) return;   // (wavefront-uniform: the hand-over to lane groups inside reset_from is collective)
   if (io.init_state) {  // the row given by the caller
     reset_from<T, JT>(C, io, so, e, io.init_state + e * (v.w_state > 0 ? v.w_state : T::SDIM + io.K), v, act, lds);
-  } else {              // device sampler (series mode, K = 1): same draws as the autoreset path, kept in registers
+  } else {              // device sampler (series or uniform mode, K = 1): same draws as the autoreset path, kept in registers
     double s0_drawn[T::SDIM + 1];
-    sample_series_init_state<T>(C, io, e, uint32_t(io.reset_count[e]), s0_drawn);
+    if (io.exo_mode) sample_uniform_init_state<T>(C, io, e, uint32_t(io.reset_count[e]), s0_drawn);
+    else sample_series_init_state<T>(C, io, e, uint32_t(io.reset_count[e]), s0_drawn);
     if (act) io.reset_count[e] += 1;
     reset_from<T, JT>(C, io, so, e, s0_drawn, v, act, lds);
   }
@@ -408,7 +465,9 @@ struct StepCtx {
 };
 
 // first half of a step: inputs -> device maps, bus sums, up to `iter_cap` Newton iterations
-template <class T, class JT, class CD, class SER = const double*>
+// UNI: the caller serves the uniform exogenous mode (io.exo_mode, a wave-uniform runtime branch); off, the mode is not in the
+// code at all -- the coalesced-row kernels keep their instruction stream
+template <class T, class JT, class CD, class SER = const double*, bool UNI = false>
 ANM_HD void step_begin(cptr_t C, CD Cd, const EnvIO& io, SolverOpts so, int64_t e, const StepIn<T>& in, StepCtx<T>& ctx,
                        EnvWork<T>& w, PFState<T>& st, int iter_cap, SER ser = nullptr) {
   if constexpr (std::is_same<SER, const double*>::value) { if (!ser) ser = io.series; }
@@ -426,12 +485,21 @@ ANM_HD void step_begin(cptr_t C, CD Cd, const EnvIO& io, SolverOpts so, int64_t 
   int aux = 0;
   if (ctx.resetting) {
     double s0[T::SDIM + 1];  // sampled initial state (K == 1 in series mode)
-    aux = sample_series_init_state<T>(C, io, e, uint32_t(in.reset_count), s0, ser);
+    if (UNI && io.exo_mode) aux = sample_uniform_init_state<T>(C, io, e, uint32_t(in.reset_count), s0);
+    else aux = sample_series_init_state<T>(C, io, e, uint32_t(in.reset_count), s0, ser);
     static_for<0, T::NDES>([&](auto I) { ctx.soc_req[I] = s0[2 * T::ND + I]; });
     inputs_from_init_state<T>(C, s0, w, P_load, P_pot, P_set, Q_set);
   } else {
     // 1. exogenous variables (next_vars, anm6_easy.py:54-65 in series mode)
-    if (series) {
+    if (UNI && io.exo_mode) {   // the step index of the episode; the draws of a step are keyed by the NEW index
+      aux = int(in.aux_prev) + 1;
+      double x[Dims<T>::NEXO > 0 ? Dims<T>::NEXO : 1];
+      // (the episode began at epoch reset_count - 1: every reset leaves the count one above the epoch it drew with)
+      exo_uniform_draws<T>(io, ExoUniform::episode_key(io.rng_seed, io.env_offset + uint64_t(e), uint32_t(in.reset_count) - 1u),
+                           uint32_t(aux), x);
+      static_for<0, T::NLOAD>([&](auto I) { P_load[I] = x[I]; });
+      static_for<0, T::NGEN>([&](auto I) { P_pot[I] = x[T::NLOAD + I]; });
+    } else if (series) {
       // (a caller that keeps the time index as an integer has formed the next one itself: in.aux_next >= 0)
       aux = in.aux_next >= 0 ? in.aux_next : int(fmod(in.aux_prev + 1.0, double(io.period)));
       static_for<0, T::NLOAD>([&](auto I) { P_load[I] = ser[I * io.period + aux]; });
@@ -972,10 +1040,11 @@ __device__ void op_step_general(cptr_t C, const EnvIO& io, SolverOpts so, int64_
   static_for<0, T::NDES>([&](auto I) { in.soc[I] = io.soc[ec * T::NDES + I]; });
   if (!series) static_for<0, D::NEXO>([&](auto I) { in.exo[I] = io.exo[ec * D::NEXO + I]; });
   in.aux_prev = series ? (io.aux_index ? double(io.aux_index[ec]) : io.state[ec * S + T::SDIM]) : 0.0;
-  in.reset_count = (io.autoreset && io.reset_count) ? io.reset_count[ec] : 0;
+  // (uniform mode: the reset epoch is part of the key of every step's draws, autoreset or not)
+  in.reset_count = ((io.autoreset || io.exo_mode) && io.reset_count) ? io.reset_count[ec] : 0;
   const int32_t ts_prev = io.timestep ? io.timestep[ec] : 0;
 
-  step_begin<T, JT>(C, C, io, so, ec, in, ctx, w, st, -1);
+  step_begin<T, JT, cptr_t, const double*, true>(C, C, io, so, ec, in, ctx, w, st, -1);
   constexpr bool CAN_GROUP = T::TREE != 0;
   const int handoff = (CAN_GROUP && so.handoff >= 0 && so.handoff < so.max_iter) ? so.handoff : -1;
   pf_iterate<T, JT>(C, w, st, so.tol, so.max_iter, handoff >= 0 ? handoff : so.max_iter);

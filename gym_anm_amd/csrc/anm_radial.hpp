@@ -345,6 +345,15 @@ __global__ __launch_bounds__(64, ANM_RADIAL_WAVES) void k_radial(Dims d, const i
     const double* s0 = nullptr;
     double s0_p = 0.0, s0_pm = 0.0;
     sampled = resetting && !(mode == 1 && io.e.init_state);
+    // uniform exogenous mode (io.e.exo_mode, wave-uniform): every load / generator lane draws its own unit from the step
+    // stream of its environment's episode -- the episode key plus one block (ExoUniform, anm_device.hpp)
+    const bool uni = io.e.exo_mode != 0;
+    const bool exo_unit = typ == DEV_LOAD || typ == DEV_CLASSICAL || typ == DEV_RENEWABLE;
+    auto exo_draw = [&](uint32_t epoch, uint32_t step) {
+      const int unit = typ == DEV_LOAD ? slot : d.NLOAD + slot;
+      const uint64_t key = ExoUniform::episode_key(io.e.rng_seed, io.e.env_offset + uint64_t(ee), epoch);
+      return ExoUniform::draw(key, step, unit, io.e.exo_lo[unit], io.e.exo_hi[unit]);
+    };
     if (mode == 1 && io.e.init_state) {
       s0 = io.e.init_state + ee * W_ST;
       if (typ != DEV_NONE) { s0_p = s0[l]; s0_q = s0[d.ND + l]; }
@@ -352,23 +361,28 @@ __global__ __launch_bounds__(64, ANM_RADIAL_WAVES) void k_radial(Dims d, const i
       if (typ == DEV_STORAGE) soc_req = s0[2 * d.ND + slot];
     } else if (resetting) {  // autoreset: ANM6Easy.init_state with the counter-based RNG
       const uint32_t epoch = uint32_t(io.e.reset_count[ee]);
-      uint32_t r[4];
-      Philox::generate(io.e.rng_seed, io.e.env_offset + uint64_t(ee), epoch, 0u, r);
-      aux = int((uint64_t(r[0]) * uint64_t(io.e.period)) >> 32);
+      double drawn = 0.0;
+      if (uni) {   // step index 0, loads and generator P / P_max from the step stream at index 0
+        if (exo_unit) drawn = exo_draw(epoch, 0u);
+      } else {
+        uint32_t r[4];
+        Philox::generate(io.e.rng_seed, io.e.env_offset + uint64_t(ee), epoch, 0u, r);
+        aux = int((uint64_t(r[0]) * uint64_t(io.e.period)) >> 32);
+      }
       cptr_t sd = C + d.off_dev + l * SD_SIZE;
-      if (typ == DEV_LOAD) s0_p = io.e.series[slot * io.e.period + aux];
+      if (typ == DEV_LOAD) s0_p = uni ? drawn : io.e.series[slot * io.e.period + aux];
       else if (typ == DEV_CLASSICAL || typ == DEV_RENEWABLE) {
         const int u = slot;
         uint32_t qd[4];
         Philox::generate(io.e.rng_seed, io.e.env_offset + uint64_t(ee), epoch, 1u + u / 2, qd);
-        const double uu = Philox::u01(qd[2 * (u % 2)], qd[2 * (u % 2) + 1]);
-        s0_p = s0_pm = io.e.series[(d.NLOAD + slot) * io.e.period + aux];
+        const double uu = Philox::u01_of(qd, u);
+        s0_p = s0_pm = uni ? drawn : io.e.series[(d.NLOAD + slot) * io.e.period + aux];
         s0_q = sd[SD_QMIN] + (sd[SD_QMAX] - sd[SD_QMIN]) * uu;
       } else if (typ == DEV_STORAGE) {
         const int u = d.NGEN + slot;
         uint32_t qd[4];
         Philox::generate(io.e.rng_seed, io.e.env_offset + uint64_t(ee), epoch, 1u + u / 2, qd);
-        const double uu = Philox::u01(qd[2 * (u % 2)], qd[2 * (u % 2) + 1]);
+        const double uu = Philox::u01_of(qd, u);
         soc_req = sd[SD_SOC_MIN] + (sd[SD_SOC_MAX] - sd[SD_SOC_MIN]) * uu;
       }
     }
@@ -382,7 +396,14 @@ __global__ __launch_bounds__(64, ANM_RADIAL_WAVES) void k_radial(Dims d, const i
       }
     } else if (!skip) {
       const double* a = io.e.action + ee * W_ACT;
-      if (series) {
+      if (uni) {   // the step index of the episode; the draws are keyed by the NEW index and the episode's epoch
+        aux = int(io.e.state[ee * W_ST + d.SDIM]) + 1;
+        if (exo_unit) {
+          const double x = exo_draw(uint32_t(io.e.reset_count[ee]) - 1u, uint32_t(aux));
+          if (typ == DEV_LOAD) in_p = x;
+          else in_pot = x;
+        }
+      } else if (series) {
         const double av = io.e.state[ee * W_ST + d.SDIM];
         aux = int(fmod(av + 1.0, double(io.e.period)));
         if (typ == DEV_LOAD) in_p = io.e.series[slot * io.e.period + aux];

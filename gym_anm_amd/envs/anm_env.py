@@ -90,7 +90,8 @@ class BatchedANMEnv(GymEnv):
     def __init__(self, network, observation, K, delta_t, gamma, lamb, aux_bounds=None, costs_clipping=None, seed=None,
                  num_envs=1, device="cuda", tol=1e-5, max_iter=100, precision="f64", autoreset=False, series=None,
                  env_offset=0, impl=None, straggler_after="auto", straggler_mid="auto", handoff_after="auto", track_full=False,
-                 fuse_observation=True, variants=None, env_variant=None, _backend=None):  # fmt: skip
+                 fuse_observation=True, variants=None, env_variant=None, exogenous=None, exo_low=None, exo_high=None,
+                 _backend=None):  # fmt: skip
         GymEnv.reset(self, seed=seed)
         self.K, self.gamma, self.lamb, self.delta_t = K, gamma, lamb, delta_t
         self.aux_bounds = aux_bounds
@@ -157,6 +158,37 @@ class BatchedANMEnv(GymEnv):
 
         # ---- environment constants for the kernels ---------------------------------------------------
         self._series = None if series is None else np.ascontiguousarray(series, dtype=np.float64)
+        # exogenous="uniform": the loads and generator potentials of every step are drawn INSIDE the step kernels,
+        # P_i ~ U(exo_low[i], exo_high[i]) MW (units: loads by device id, then non-slack generators; defaults: loads
+        # [p_min, 0], generators [0, p_max]) from the counter-based RNG -- the stream layout is rng.py's (exo_uniform).
+        # K = 1: the aux variable is the step index of the episode.  step() is one launch and never calls next_vars().
+        if exogenous not in (None, "host", "uniform"):
+            raise E.ArgsError("The argument exogenous is %r but should be None, 'host' or 'uniform'." % (exogenous,))
+        self.exogenous = "uniform" if exogenous == "uniform" else "host"
+        self._uniform = self.exogenous == "uniform"
+        self.exo_low = self.exo_high = None
+        if self._uniform:
+            from .. import rng as _rng
+
+            if self._series is not None:
+                raise E.EnvInitializationError("exogenous='uniform' and series= do not go together")
+            if K != 1:
+                raise E.EnvInitializationError("exogenous='uniform' needs K = 1 (the aux variable is the step index)")
+            if variants is not None or env_variant is not None:
+                raise E.EnvInitializationError("exogenous='uniform' does not take parameter classes (variants=)")
+            if sim.backend.device_type != "cuda":
+                # (a backend that ignores the mode would run a different task without saying so)
+                raise E.EnvInitializationError("exogenous='uniform' needs the GPU library: this backend does not draw in its kernels")
+            n_exo = sim.N_load + sim.N_non_slack_gen
+            d_lo, d_hi = _rng.default_exo_bounds(sim.model)
+            self.exo_low = d_lo if exo_low is None else np.ascontiguousarray(exo_low, dtype=np.float64)
+            self.exo_high = d_hi if exo_high is None else np.ascontiguousarray(exo_high, dtype=np.float64)
+            if self.exo_low.shape != (n_exo,) or self.exo_high.shape != (n_exo,):
+                raise E.ArgsError("exo_low / exo_high must have %d entries (loads, then non-slack generators)" % n_exo)
+            if not (np.isfinite(self.exo_low).all() and np.isfinite(self.exo_high).all() and (self.exo_low <= self.exo_high).all()):
+                raise E.ArgsError("exo_low / exo_high must be finite with exo_low <= exo_high")
+        elif exo_low is not None or exo_high is not None:
+            raise E.ArgsError("exo_low / exo_high need exogenous='uniform'")
         slo, shi = self._state_bounds_vectors()
         self._obs_is_state = self.obs_values is not None and self.obs_values == self.state_values
         if self._obs_is_state and self.observation_space is not None:
@@ -166,6 +198,9 @@ class BatchedANMEnv(GymEnv):
             obs_low=_lib.as_c(slo, np.float64)[1], obs_high=_lib.as_c(shi, np.float64)[1],
             series=None if self._series is None else self._series.ctypes.data_as(_lib.c_double_p),
             period=0 if self._series is None else int(self._series.shape[1]),
+            exo_mode=_lib.EXO_UNIFORM if self._uniform else _lib.EXO_HOST,
+            exo_low=self.exo_low.ctypes.data_as(_lib.c_double_p) if self._uniform else None,
+            exo_high=self.exo_high.ctypes.data_as(_lib.c_double_p) if self._uniform else None,
         )  # fmt: skip
         self._cfg_keep = (slo, shi)
         with sim._device_ctx():
@@ -462,7 +497,9 @@ class BatchedANMEnv(GymEnv):
         if seed is not None:
             self.rng_seed = int(seed)
         options = options or {}
-        if options.get("sampler") == "device":
+        # (uniform mode: plain reset() draws on the device unless the task brings an init_state() of its own)
+        if options.get("sampler") == "device" or (
+                self._uniform and options.get("init_state") is None and type(self).init_state is BatchedANMEnv.init_state):
             return self._reset_on_device(options.get("mask"))
         mask = options.get("mask")
         mask_u8 = None
@@ -482,6 +519,10 @@ class BatchedANMEnv(GymEnv):
                     "Expected size of initial state s0 is %d but actual is %d" % (self.state_N, s0.shape[1])
                 )
             self._launch_reset(s0.contiguous(), todo)
+            if self._uniform:
+                # a new episode for every environment this reset touched, whoever supplied the rows: one environment
+                # never uses a step stream twice (the epoch is part of its key)
+                self._reset_count += todo.to(torch.int32)
             todo = todo * (1 - self._conv_u8)
             if given is not None or not bool(todo.any()):
                 break
@@ -510,7 +551,7 @@ class BatchedANMEnv(GymEnv):
         ``(seed, env_offset + env, reset_count[env])``, instead of by ``init_state()`` on the host.
         Environments whose first power flow does not converge are redrawn, up to the reference's
         limit of 100 attempts (anm_env.py:266-289)."""
-        if self._series is None:
+        if self._series is None and not self._uniform:
             raise E.EnvInitializationError("the device sampler needs a series-mode task")
         if mask is None:
             todo = torch.ones(self.num_envs, dtype=torch.uint8, device=self.device)
@@ -536,7 +577,7 @@ class BatchedANMEnv(GymEnv):
         ``(seed, env_offset + env, reset_count[env])`` -- without resetting anything: ``[num_envs, state_N]`` in the
         layout ``reset(options={"init_state": ...})`` takes.  ``raw=True``: also the Philox words behind each row
         (``int64 [num_envs, blocks, 4]`` holding uint32 values; anm_sample_init_state_f64)."""
-        if self._series is None:
+        if self._series is None and not self._uniform:
             raise E.EnvInitializationError("the device sampler needs a series-mode task")
         sim = self.simulator
         out = torch.zeros((self.num_envs, self.state_N), dtype=torch.float64, device=self.device)
@@ -598,7 +639,7 @@ class BatchedANMEnv(GymEnv):
         if not action.is_contiguous():
             action = action.contiguous()
         exo_ptr = aux_ptr = None
-        if self._series is None:
+        if self._series is None and not self._uniform:
             v = torch.as_tensor(self.next_vars(self.state), dtype=torch.float64, device=self.device)
             expected = sim.N_load + sim.N_non_slack_gen + self.K
             if v.dim() != 2 or v.shape[1] != expected:

@@ -54,3 +54,171 @@ def series_init_state(model, series, seed, env, epoch):
     for e, k in enumerate(model.des_idx):
         s0[2 * D + e] = model.dev_soc_min[k] + (model.dev_soc_max[k] - model.dev_soc_min[k]) * uniform(ng + e)
     return s0
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# Uniform exogenous mode (``BatchedANMEnv(exogenous="uniform")``, anm_env_config.exo_mode = ANM_EXO_UNIFORM).
+#
+# Every step the kernels draw, per environment, P_i = lo_i + (hi_i - lo_i) u_i MW for unit i -- the loads by device id,
+# then the non-slack generators by device id.  NORMATIVE:
+#
+# * K = 1.  The auxiliary variable is the step index t of the episode: 0 after a reset, aux_{t+1} = aux_t + 1,
+#   t < 2^31 (the kernels keep it in an int32).  The draws of a step are keyed by the NEW index, so the stream can be
+#   replayed from a state row alone (``next_vars(state)``).
+# * An episode is named by (seed, global environment index, epoch); ``epoch`` is the value of the environment's reset
+#   count when the episode's initial state was drawn -- every reset leaves the count one above it, so during the episode
+#   epoch = reset_count - 1.
+# * Stream layout.  One block under the seed gives the episode key,
+#       K' = words 0, 1 of philox(seed; counter = (env lo, env hi, epoch, 0xFFFFFFFF)),
+#   and block j of step t is
+#       philox(K'; counter = (t, j, 0, 0x45584F31)).
+#   Unit i takes words 2 (i % 2), 2 (i % 2) + 1 of block i // 2 through u01 -- the layout of the init sampler.
+# * The init sampler keeps (seed; (env lo, env hi, epoch, draw)) with draw = 0 .. 1 + ceil((n_gen + n_des) / 2), far below
+#   0xFFFFFFFF; the step stream's counters end in 0x45584F31, which no init-sampler counter of a real network does.  So
+#   no (key, counter) pair is shared, whatever K' turns out to be (``init_pairs`` / ``exo_pairs`` list them).
+# * The affine map is ONE fused multiply-add, fma(fl(hi - lo), u, lo): device, host test double and this file agree bit
+#   for bit.  ``fma`` below evaluates it exactly in rationals and rounds once.
+# * Initial state of the mode (autoreset, reset(options={"sampler": "device"}), sample_init_state()): aux = 0; loads and
+#   generator P / P_max are the step stream at t = 0; generator Q and storage SoC are uniform from the init sampler's
+#   blocks 1 + u // 2, quirks included (``series_init_state``); block 0 is unused.
+# ---------------------------------------------------------------------------------------------------------------------
+EXO_KEY_DRAW = 0xFFFFFFFF
+EXO_TAG = 0x45584F31
+
+
+def fma(a: float, b: float, c: float) -> float:
+    """a * b + c with one rounding (finite arguments)."""
+    from fractions import Fraction
+
+    r = Fraction(a) * Fraction(b) + Fraction(c)
+    if r == 0:
+        # an exact zero: the sign IEEE gives a sum of opposite-signed terms (round to nearest) is +0 unless both are -0
+        prod_neg = (np.signbit(a) != np.signbit(b))
+        return -0.0 if (prod_neg and np.signbit(c)) else 0.0
+    return float(r)          # int / int true division: correctly rounded
+
+
+def episode_key(seed: int, env: int, epoch: int) -> int:
+    r = philox4x32(seed, env, epoch, EXO_KEY_DRAW)
+    return r[0] | (r[1] << 32)
+
+
+def exo_block(key: int, t: int, j: int):
+    return philox4x32(key, (t & MASK) | ((j & MASK) << 32), 0, EXO_TAG)
+
+
+def exo_uniform(seed, env, epoch, t, low, high):
+    """P_load / P_pot (MW, ``[n_load + n_gen]``) of step ``t`` of the episode (seed, env, epoch)."""
+    low, high = np.asarray(low, dtype=np.float64), np.asarray(high, dtype=np.float64)
+    key = episode_key(seed, env, epoch)
+    out = np.empty(len(low))
+    for i in range(len(low)):
+        q = exo_block(key, t, i // 2)
+        out[i] = fma(float(high[i] - low[i]), u01(q[2 * (i % 2)], q[2 * (i % 2) + 1]), float(low[i]))
+    return out
+
+
+def default_exo_bounds(model):
+    """Default ends in MW: loads [p_min, 0], generators [0, p_max]."""
+    low = np.zeros(model.N_load + model.N_non_slack_gen)
+    high = np.zeros_like(low)
+    for s, k in enumerate(model.load_idx):
+        low[s] = model.dev_p_min[k] * model.baseMVA
+    for g, k in enumerate(model.gen_idx):
+        high[model.N_load + g] = model.dev_p_max[k] * model.baseMVA
+    return low, high
+
+
+def uniform_init_state(model, seed, env, epoch, low, high):
+    """Initial state the kernels draw for environment ``env`` at its ``epoch``-th reset in the uniform mode."""
+    D, nd, ng = model.N_device, model.N_des, model.N_non_slack_gen
+    s0 = np.zeros(2 * D + nd + ng + 1)
+    x = exo_uniform(seed, env, epoch, 0, low, high)
+
+    def uniform(u):
+        q = philox4x32(seed, env, epoch, 1 + u // 2)
+        return u01(q[2 * (u % 2)], q[2 * (u % 2) + 1])
+
+    for s, k in enumerate(model.load_idx):
+        s0[k] = x[s]
+    for g, k in enumerate(model.gen_idx):
+        s0[k] = x[model.N_load + g]
+        s0[2 * D + nd + g] = x[model.N_load + g]
+        s0[D + k] = model.dev_q_min[k] + (model.dev_q_max[k] - model.dev_q_min[k]) * uniform(g)
+    for e, k in enumerate(model.des_idx):
+        s0[2 * D + e] = model.dev_soc_min[k] + (model.dev_soc_max[k] - model.dev_soc_min[k]) * uniform(ng + e)
+    return s0
+
+
+def init_pairs(seed, env, epoch, n_gen, n_des):
+    """The (key, counter) pairs the init sampler may use for one (seed, env, epoch)."""
+    n_draw = 2 + (n_gen + n_des + 1) // 2
+    return {(seed & 0xFFFFFFFFFFFFFFFF, (env & MASK, (env >> 32) & MASK, epoch & MASK, d)) for d in range(n_draw)}
+
+
+def exo_pairs(seed, env, epoch, t, n_exo):
+    """The (key, counter) pairs of step ``t`` of the episode (seed, env, epoch): the key block and the step blocks."""
+    key = episode_key(seed, env, epoch)
+    pairs = {(seed & 0xFFFFFFFFFFFFFFFF, (env & MASK, (env >> 32) & MASK, epoch & MASK, EXO_KEY_DRAW))}
+    pairs |= {(key, (t & MASK, j, 0, EXO_TAG)) for j in range((n_exo + 1) // 2)}
+    return pairs
+
+
+# ---- vectorised forms (uint64 arithmetic), for batch-sized checks --------------------------------------------------
+def philox4x32_v(seed, env, epoch, draw):
+    """``philox4x32`` over arrays (broadcast): returns ``uint64 [..., 4]`` holding the four 32-bit words."""
+    seed, env, epoch, draw = np.broadcast_arrays(*(np.asarray(a, dtype=np.uint64) for a in (seed, env, epoch, draw)))
+    m = np.uint64(MASK)
+    s32 = np.uint64(32)
+    c0, c1, c2, c3 = env & m, (env >> s32) & m, epoch & m, draw & m
+    k0, k1 = seed & m, (seed >> s32) & m
+    for _ in range(10):
+        p0, p1 = np.uint64(M0) * c0, np.uint64(M1) * c2
+        c0, c1, c2, c3 = ((p1 >> s32) ^ c1 ^ k0) & m, p1 & m, ((p0 >> s32) ^ c3 ^ k1) & m, p0 & m
+        k0, k1 = (k0 + np.uint64(W0)) & m, (k1 + np.uint64(W1)) & m
+    return np.stack([c0, c1, c2, c3], axis=-1)
+
+
+def u01_v(hi, lo):
+    v = ((np.asarray(hi, dtype=np.uint64) << np.uint64(32)) | np.asarray(lo, dtype=np.uint64)) >> np.uint64(11)
+    return v.astype(np.float64) * (1.0 / 9007199254740992.0)
+
+
+def exo_uniform_v(seed, env, epoch, t, low, high):
+    """``exo_uniform`` for arrays of env / epoch / t (broadcast): ``[..., n_load + n_gen]``.  The affine map is plain
+    arithmetic here, lo + (hi - lo) u: up to one rounding off the fused one."""
+    low, high = np.asarray(low, dtype=np.float64), np.asarray(high, dtype=np.float64)
+    env, epoch, t = np.broadcast_arrays(*(np.asarray(a, dtype=np.uint64) for a in (env, epoch, t)))
+    kw = philox4x32_v(np.uint64(seed & 0xFFFFFFFFFFFFFFFF), env, epoch, np.uint64(EXO_KEY_DRAW))
+    key = kw[..., 0] | (kw[..., 1] << np.uint64(32))
+    out = np.empty(env.shape + (len(low),))
+    for j in range((len(low) + 1) // 2):
+        q = philox4x32_v(key, (t & np.uint64(MASK)) | (np.uint64(j) << np.uint64(32)), np.uint64(0), np.uint64(EXO_TAG))
+        for h in range(2):
+            i = 2 * j + h
+            if i < len(low):
+                out[..., i] = low[i] + (high[i] - low[i]) * u01_v(q[..., 2 * h], q[..., 2 * h + 1])
+    return out
+
+
+def uniform_init_state_v(model, seed, env, epoch, low, high):
+    """``uniform_init_state`` for arrays of env / epoch: ``[n, state_N]`` (affine maps in plain arithmetic)."""
+    env, epoch = np.broadcast_arrays(np.asarray(env, dtype=np.uint64), np.asarray(epoch, dtype=np.uint64))
+    D, nd, ng = model.N_device, model.N_des, model.N_non_slack_gen
+    s0 = np.zeros(env.shape + (2 * D + nd + ng + 1,))
+    x = exo_uniform_v(seed, env, epoch, 0, low, high)
+    sd = np.uint64(seed & 0xFFFFFFFFFFFFFFFF)
+
+    def uniform(u):
+        q = philox4x32_v(sd, env, epoch, np.uint64(1 + u // 2))
+        return u01_v(q[..., 2 * (u % 2)], q[..., 2 * (u % 2) + 1])
+
+    for s, k in enumerate(model.load_idx):
+        s0[..., k] = x[..., s]
+    for g, k in enumerate(model.gen_idx):
+        s0[..., k] = x[..., model.N_load + g]
+        s0[..., 2 * D + nd + g] = x[..., model.N_load + g]
+        s0[..., D + k] = model.dev_q_min[k] + (model.dev_q_max[k] - model.dev_q_min[k]) * uniform(g)
+    for e, k in enumerate(model.des_idx):
+        s0[..., 2 * D + e] = model.dev_soc_min[k] + (model.dev_soc_max[k] - model.dev_soc_min[k]) * uniform(ng + e)
+    return s0

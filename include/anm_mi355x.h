@@ -95,7 +95,20 @@ typedef struct anm_env_config {
    * MW, rows = loads by device id then non-slack generators by device id; NULL / 0 = not used. */
   const double* series;
   int32_t period;
+  /* where P_load / P_pot of a step come from when anm_step_f64 gets no `exo` and the task has no `series`:
+   * ANM_EXO_HOST (0, the default: a zero-filled tail keeps this behaviour): nowhere -- such a step is an error;
+   * ANM_EXO_UNIFORM: drawn inside the step kernels, P_i = fma(exo_high[i] - exo_low[i], u_i, exo_low[i]) MW for unit i
+   * (loads by device id, then non-slack generators by device id), u_i from the counter-based RNG as a pure function of
+   * (rng_seed, env_offset + env, reset_count[env], step index, i): the stream layout is gym_anm_amd/rng.py's (exo_uniform).
+   * Needs K = 1 (the aux variable is the step index of the episode) and no series.
+   * exo_low / exo_high: host arrays [n_load + n_gen] in MW, finite, low <= high; NULL = the defaults, loads
+   * [p_min, 0], generators [0, p_max] (MW). */
+  int32_t exo_mode;
+  const double* exo_low;
+  const double* exo_high;
 } anm_env_config;
+#define ANM_EXO_HOST 0
+#define ANM_EXO_UNIFORM 1
 
 const char* anm_last_error(void);
 const char* anm_topology_name(void);  /* name of the topology this library was compiled for */
@@ -240,7 +253,10 @@ int anm_transition_f64(anm_model* m, int64_t num_envs, const double* p_load, con
  * clears terminated/timestep of the environments it touches.
  * init_state == NULL (series mode): the initial states are drawn inside the kernel like
  * ANM6Easy.init_state (anm6_easy.py:25-52) from the counter-based RNG keyed by
- * (rng_seed, env_offset + env, reset_count[env]); reset_count[env] is then incremented. */
+ * (rng_seed, env_offset + env, reset_count[env]); reset_count[env] is then incremented.
+ * init_state == NULL, ANM_EXO_UNIFORM: step index 0, loads and generator potentials from the step stream at index 0,
+ * generator Q and storage SoC as in series mode (rng.py: uniform_init_state); reset_count[env] is incremented.
+ * (The mode goes with neither parameter classes nor a batch view: refused.) */
 int anm_reset_f64(anm_model* m, int64_t num_envs, const double* init_state, const uint8_t* mask,
                   uint64_t rng_seed, uint64_t env_offset, int32_t* reset_count, double* soc, double* state, double* obs, uint8_t* converged, uint8_t* terminated,
                   int32_t* timestep, int32_t* nr_iters, double* full, int32_t* aux_index,
@@ -255,7 +271,9 @@ int anm_reset_f64(anm_model* m, int64_t num_envs, const double* init_state, cons
  * raw: NULL, or dev uint32 [num_envs, 1 + ceil((n_gen + n_des) / 2), 4]: the Philox blocks behind each row (block 0: word 0
  * gives t_0 = (word * period) >> 32; block 1 + u / 2, words 2 (u % 2), 2 (u % 2) + 1: the 53-bit uniform u of generator u /
  * storage unit u - n_gen).  Pinned by tests to the Random123 known answers, to gym_anm_amd/rng.py, to the kernels' own
- * in-line samplers (bit for bit) and to the distribution of the reference's init_state().  Rows are contiguous (no view). */
+ * in-line samplers (bit for bit) and to the distribution of the reference's init_state().  Rows are contiguous (no view).
+ * ANM_EXO_UNIFORM: the rows of that mode instead (aux = 0, loads / generator P and P_max from the step stream at index 0,
+ * Q and SoC from blocks 1 + u / 2 as above; block 0 is unused); raw, if given, still holds the init sampler's blocks. */
 int anm_sample_init_state_f64(anm_model* m, int64_t num_envs, uint64_t rng_seed, uint64_t env_offset,
                               const int32_t* reset_count, double* init_state, uint32_t* raw, void* stream);
 
@@ -284,16 +302,19 @@ int anm_step_ws_record_doubles(void);
 
 /* ANMEnv.step for num_envs environments.
  *   in : action [E, action_dim];  exo [E, n_load+n_gen] MW and aux_next [E, K] (the output of
- *        next_vars), or both NULL in series mode (aux = (aux+1) mod period, table lookup)
+ *        next_vars), or both NULL in series mode (aux = (aux+1) mod period, table lookup) and in the uniform
+ *        mode (anm_env_config.exo_mode = ANM_EXO_UNIFORM: aux = aux + 1, the step index of the episode; P_load /
+ *        P_pot drawn in the kernel, keyed by the NEW index; `exo` given in that mode is an error)
  *   io : soc [E, n_des], state [E, state_base_dim+K], terminated [E], timestep [E] (nullable)
  *   out: obs [E, state_base_dim+K] = clip(state, obs_low, obs_high), reward/e_loss/penalty [E]
  *        (clipped like anm_env.py:423-432), nr_iters (nullable), full (nullable)
- *   autoreset (series mode only): an environment that is terminated on entry is re-initialised
+ *   autoreset (series mode and uniform mode): an environment that is terminated on entry is re-initialised
  *        instead of stepped (Gymnasium "next step" autoreset): its initial state is drawn like
  *        ANM6Easy.init_state (anm6_easy.py:25-52) from a counter-based RNG keyed by
  *        (rng_seed, env_offset + env index, reset_count[e]); reward 0, terminated 0.  env_offset is
  *        the global index of this batch's first environment, so a batch sharded over several GPUs
- *        draws exactly what the unsharded batch would.
+ *        draws exactly what the unsharded batch would.  (Uniform mode: the initial state of that mode, see
+ *        anm_reset_f64.)
  *   aux_index (optional, series mode, K = 1): int32 [E] compact copy of the time index kept by the
  *        library next to `state`; when given (and `full` is NULL) the thread-per-environment family
  *        uses its coalesced-row kernel: action / state / obs rows move through LDS as whole-wave
