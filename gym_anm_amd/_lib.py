@@ -40,12 +40,31 @@ class Dims(C.Structure):
                  "full_dim", "const_doubles"]]  # fmt: skip
 
 
+class EpisodeBuffers(C.Structure):
+    """anm_episode_buffers: device pointers, 0 = not kept"""
+    _fields_ = [(k, C.c_void_p) for k in ["truncated", "ep_return", "ep_disc_return", "ep_discount", "last_return",
+                                          "last_disc_return", "last_length", "episodes_done"]]  # fmt: skip
+
+
 class EnvConfig(C.Structure):
     _fields_ = [
         ("K", C.c_int32), ("gamma", C.c_double), ("clip_e_loss", C.c_double), ("clip_penalty", C.c_double),
         ("obs_low", c_double_p), ("obs_high", c_double_p), ("series", c_double_p), ("period", C.c_int32),
         ("exo_mode", C.c_int32), ("exo_low", c_double_p), ("exo_high", c_double_p),
     ]  # fmt: skip
+
+
+ENV_TAIL_NONE, ENV_TAIL_EPISODE = 0, 1   # anm_env_config.tail
+
+
+class EnvConfigEpisode(EnvConfig):
+    """anm_env_config with the episode fields behind exo_high.  `tail` -- the int32 in what is alignment padding behind K in
+    EnvConfig (zero there: "the struct ends at exo_high") -- tells the library that they are present."""
+    _fields_ = [("max_episode_steps", C.c_int32), ("episode", C.POINTER(EpisodeBuffers))]
+
+    def __init__(self, *a, **kw):
+        super().__init__(*a, **kw)
+        C.c_int32.from_address(C.addressof(self) + EnvConfig.K.offset + 4).value = ENV_TAIL_EPISODE
 
 
 class StepWs(C.Structure):

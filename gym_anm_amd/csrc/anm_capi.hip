@@ -109,6 +109,17 @@ __global__ __launch_bounds__(BLOCK, ANM_ROWS_WAVES) void k_step_rows(cptr_t C0, 
 #endif
 }
 
+// the fast path with the episode time limit and statistics (anm_env_config.max_episode_steps / .episode): a kernel of its
+// own, so that k_step_rows carries none of it
+template <class JT>
+__global__ __launch_bounds__(BLOCK, ANM_ROWS_WAVES) void k_step_rows_ep(cptr_t C0, EnvIO io, SolverOpts so, int64_t n, ClassSel cs) {
+#ifndef ANM_DEV_LANE_GROUPS_ONLY   // (tuning builds of the lane-group kernels alone: minutes less to compile)
+  __shared__ double lds[64 * (Topo::SDIM + 2)];
+  const cptr_t C = class_constants(C0, cs, int64_t(blockIdx.x) * BLOCK);
+  op_step_rows<Topo, JT, false, true>(C, io, so, n, lds);
+#endif
+}
+
 // general step (host next_vars, K != 1, list-form observations, `full` dump): see op_step_general
 template <class JT>
 __global__ __launch_bounds__(BLOCK) void k_step_general(cptr_t C0, EnvIO io, SolverOpts so, int64_t n, ClassSel cs) {
@@ -263,6 +274,7 @@ struct anm_model {
   int exo_mode = ANM_EXO_HOST;
   std::vector<double> exo_default;            // [2][n_load + n_gen] MW: loads [p_min, 0], generators [0, p_max]
   double* d_exo = nullptr;                    // [2][n_load + n_gen] MW: low, high of every unit
+  EpisodeIO ep{};                             // episode time limit and statistics (anm_env_config.max_episode_steps / .episode)
   std::vector<cplx> ybus;
 
   std::array<Tables*, 3> tables() { return {&t_thread, &t_radial, &t_mesh}; }
@@ -677,6 +689,33 @@ int anm_model_set_env(anm_model* m, const anm_env_config* cfg) {
     if (e != hipSuccess) return fail_hip(e, "hipMemcpy(exo ends)");
     m->exo_mode = ANM_EXO_UNIFORM;
   }
+  m->ep = EpisodeIO{};
+  if (cfg->tail != ANM_ENV_TAIL_NONE && cfg->tail != ANM_ENV_TAIL_EPISODE) return fail("anm_model_set_env: unknown value of tail");
+  const bool has_ep = cfg->tail >= ANM_ENV_TAIL_EPISODE;   // (a struct that ends at exo_high: nothing behind it is read)
+  if (has_ep && cfg->max_episode_steps < 0) return fail("anm_model_set_env: max_episode_steps must not be negative (0 = no limit)");
+  if (has_ep && (cfg->max_episode_steps > 0 || cfg->episode)) {
+    if (m->has_view)
+      return fail("anm_model_set_env: an episode time limit or episode buffers do not go with a bound batch view (anm_model_bind_view)");
+    EpisodeIO ep{};
+    ep.max_steps = cfg->max_episode_steps;
+    ep.gamma = cfg->gamma;
+    if (const anm_episode_buffers* b = cfg->episode) {
+      if ((b->ep_disc_return == nullptr) != (b->ep_discount == nullptr))
+        return fail("anm_model_set_env: ep_disc_return and ep_discount go together");
+      if ((b->last_return && !b->ep_return) || (b->last_disc_return && !b->ep_disc_return))
+        return fail("anm_model_set_env: last_return needs ep_return and last_disc_return needs ep_disc_return");
+      ep.truncated = b->truncated;
+      ep.ret = b->ep_return;
+      ep.disc_ret = b->ep_disc_return;
+      ep.discount = b->ep_discount;
+      ep.last_ret = b->last_return;
+      ep.last_disc_ret = b->last_disc_return;
+      ep.last_len = b->last_length;
+      ep.n_done = b->episodes_done;
+    }
+    ep.on = (ep.max_steps > 0 || ep.truncated || ep.ret || ep.disc_ret || ep.last_len || ep.n_done) ? 1 : 0;
+    m->ep = ep;
+  }
   m->env_set = true;
   return upload_const(m);
 }
@@ -816,6 +855,8 @@ int anm_model_bind_view(anm_model* m, const anm_batch_view* v) {
                 "(anm_model_set_obs): clear it, or move the model to a lane-group family first (anm_model_set_impl)");
   if (m->n_obs > 0 && v->w_obs != 0 && v->w_obs < m->n_obs) return fail("anm_model_bind_view: w_obs is narrower than the observation list");
   if (m->d_state_same) return fail("anm_model_bind_view: not together with anm_model_bind_state_same (the flags are indexed by launch slot)");
+  if (m->ep.on)
+    return fail("anm_model_bind_view: a batch view does not go with an episode time limit or episode buffers (anm_env_config.max_episode_steps / .episode)");
   const anm_dims& d = m->dims;
   const int K = m->K;
   const int n_set = d.n_gen + d.n_des;
@@ -992,6 +1033,8 @@ int anm_reset_f64(anm_model* m, int64_t n, const double* init_state, const uint8
   io.full = full;
   io.aux_index = aux_index;
   io.nr_diff = m->d_nr_diff;
+  io.ep = m->ep;
+  if (io.ep.on && m->has_view) return fail("anm_reset_f64: an episode time limit or episode buffers do not go with a batch view (anm_model_bind_view)");
   int prec;
   SolverOpts so = solver(opts, prec);
   hipStream_t s = static_cast<hipStream_t>(stream);
@@ -1066,6 +1109,11 @@ static int make_step_io(anm_model* m, const double* action, const double* exo, c
   io.reset_count = reset_count;
   io.aux_index = aux_index;
   io.state_same = m->d_state_same;
+  io.ep = m->ep;
+  if (io.ep.on) {
+    if (m->has_view) return fail("anm_step_f64: an episode time limit or episode buffers do not go with a batch view (anm_model_bind_view)");
+    if (!timestep) return fail("anm_step_f64: an episode time limit or episode buffers need the timestep buffer");
+  }
   io.n_obs = 0;
   io.state_magic = magic_div(m->dims.state_base_dim + m->K);
   if (m->t_thread.ok && m->impl == ANM_IMPL_THREAD && (m->n_obs > 0 || full)) {
@@ -1140,6 +1188,7 @@ static int launch_step(anm_model* m, const EnvIO& io_in, int64_t n, const anm_so
   if (io.aux_index && io.exo == nullptr && io.exo_mode == ANM_EXO_HOST && io.K == 1 && !io.full && io.n_obs == 0) {
     // fast path: series mode, "state" observation, nothing but the batch tensors
     int rc = by_precision(prec, [&](auto jt) {
+      if (io.ep.on) return launch("launch k_step_rows_ep", k_step_rows_ep<decltype(jt)>, grid, BLOCK, 0, s, C, io, so, n, cs);
       return launch("launch k_step_rows", k_step_rows<decltype(jt), false>, grid, BLOCK, 0, s, C, io, so, n, cs);
     });
     if (rc || !(io.ws && io.iter_cap < so.max_iter)) return rc;

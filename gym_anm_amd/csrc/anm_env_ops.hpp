@@ -166,6 +166,58 @@ ANM_HD void op_transition(cptr_t C, const TransitionIO& io, SolverOpts so, int64
   if (io.full) write_full_state<T>(w, io.full + e * WF);
 }
 
+// Episode time limit and statistics (anm_env_config.max_episode_steps / .episode; gym_anm_amd/episode.py is the
+// specification these follow).  Everything is optional: max_steps == 0 is "no limit", a null pointer "not kept".
+struct EpisodeIO {
+  int max_steps;            // T: an environment whose timestep has reached T is truncated (0: no limit)
+  int on;                   // a limit or a buffer is set: the wave-uniform switch of the kernels that serve both
+  double gamma;             // discount factor of the task
+  uint8_t* truncated;       // [E]
+  double* ret;              // [E] running return of the episode
+  double* disc_ret;         // [E] ... discounted return (with `discount`)
+  double* discount;         // [E] gamma^(steps of the episode so far)
+  double* last_ret;         // [E] return of the last finished episode (with `ret`)
+  double* last_disc_ret;    // [E] (with `disc_ret`)
+  int32_t* last_len;        // [E] its length
+  int32_t* n_done;          // [E] episodes finished so far
+};
+
+// the time-limit half of "the episode has ended" at the entry of a step; t: timestep[e] on entry
+ANM_HD bool episode_timed_out(const EpisodeIO& ep, int32_t t) { return ep.max_steps > 0 && t >= ep.max_steps; }
+
+// a reset of environment e (in-kernel autoreset or a reset launch), a failed draw included: no episode ends here
+ANM_HD void episode_clear(const EpisodeIO& ep, int64_t e) {
+  if (ep.truncated) ep.truncated[e] = 0;
+  if (ep.ret) ep.ret[e] = 0.0;
+  if (ep.disc_ret) {
+    ep.disc_ret[e] = 0.0;
+    ep.discount[e] = 1.0;
+  }
+}
+
+// a real step of environment e that stored reward r and left timestep = t1 (the absorbing no-op step is not one)
+ANM_HD void episode_step(const EpisodeIO& ep, int64_t e, double r, bool terminated, int32_t t1) {
+  if (ep.truncated) ep.truncated[e] = (ep.max_steps > 0 && t1 >= ep.max_steps) ? 1 : 0;
+  // `==`: an environment stepped on beyond the limit (no autoreset) has ended ONE episode
+  const bool ended = terminated || t1 == ep.max_steps;
+  if (ep.ret) {
+    const double ret = ep.ret[e] + r;
+    ep.ret[e] = ret;
+    if (ended && ep.last_ret) ep.last_ret[e] = ret;
+  }
+  if (ep.disc_ret) {
+    const double g = ep.discount[e];
+    const double dr = fma(g, r, ep.disc_ret[e]);   // one rounding, spelled out: rng.fma is the host counterpart
+    ep.disc_ret[e] = dr;
+    ep.discount[e] = g * ep.gamma;
+    if (ended && ep.last_disc_ret) ep.last_disc_ret[e] = dr;
+  }
+  if (ended) {
+    if (ep.last_len) ep.last_len[e] = t1;
+    if (ep.n_done) ep.n_done[e] += 1;
+  }
+}
+
 struct EnvIO {
   int K;                    // number of aux variables
   const double* action;     // [E, ADIM]
@@ -218,6 +270,7 @@ struct EnvIO {
   int exo_mode;
   const double* exo_lo;     // [NEXO] MW (device)
   const double* exo_hi;     // [NEXO] MW (device)
+  EpisodeIO ep;             // episode time limit and statistics (all zero: off)
 };
 
 // Split an init_state row (anm_env.py / simulator.py:248-268) into transition inputs.
@@ -394,6 +447,7 @@ ANM_HD void reset_from(cptr_t C, const EnvIO& io, SolverOpts so, int64_t e, cons
   io.converged[e] = w.converged ? 1 : 0;
   io.terminated[e] = 0;
   if (io.timestep) io.timestep[e] = 0;
+  if (io.ep.on) episode_clear(io.ep, e);
   if (io.nr_iters) io.nr_iters[e] = w.n_iter;
   if (io.nr_diff) io.nr_diff[e] = w.diff;
   if (io.aux_index && io.K == 1) io.aux_index[e] = int32_t(s0[T::SDIM]);
@@ -622,9 +676,17 @@ ANM_HD void step_compute(cptr_t C, const EnvIO& io, SolverOpts so, int64_t e, co
 }
 
 // everything of StepOut except the state / obs rows
-template <class T, int KCAP>
+// EP: the caller serves the episode time limit and statistics (io.ep, a wave-uniform runtime switch); off, they are not in
+// the code at all (the fast path of the step keeps its instruction stream: k_step_rows / k_step_rows_ep)
+template <class T, int KCAP, bool EP = false>
 ANM_HD void store_step_scalars(const EnvIO& io, int64_t e, const StepFlags<T>& o, bool have_ts = false,
                                int32_t ts_prev = 0) {  // have_ts: the caller already read timestep[e]
+  if constexpr (EP) {
+    if (io.ep.on) {   // (needs timestep: the C ABI refuses the feature without it)
+      if (o.timestep_op == 1) episode_clear(io.ep, e);
+      else if (o.timestep_op == 2) episode_step(io.ep, e, o.reward, o.terminated == 1, (have_ts ? ts_prev : io.timestep[e]) + 1);
+    }
+  }
   if (o.write_soc) static_for<0, T::NDES>([&](auto I) { io.soc[e * T::NDES + I] = o.soc[I]; });
   if (o.terminated >= 0) io.terminated[e] = uint8_t(o.terminated);
   io.reward[e] = o.reward;
@@ -649,6 +711,7 @@ ANM_HD void op_step(cptr_t C, const EnvIO& io, SolverOpts so, int64_t e) {
   StepOut<T> out;
   EnvWork<T> w;
   in.was_term = io.terminated[e] != 0;
+  if (io.ep.on && io.autoreset && io.timestep) in.was_term = in.was_term || episode_timed_out(io.ep, io.timestep[e]);
   static_for<0, D::ADIM>([&](auto I) { in.action[I] = io.action[e * D::ADIM + I]; });
   if (io.exo) static_for<0, D::NEXO>([&](auto I) { in.exo[I] = io.exo[e * D::NEXO + I]; });
   static_for<0, T::NDES>([&](auto I) { in.soc[I] = io.soc[e * T::NDES + I]; });
@@ -664,7 +727,7 @@ ANM_HD void op_step(cptr_t C, const EnvIO& io, SolverOpts so, int64_t e) {
       if (out.write_obs) obs[k] = out.obs[k];
     }
   });
-  store_step_scalars<T, Layout<T>::KMAX>(io, e, out);
+  store_step_scalars<T, Layout<T>::KMAX, true>(io, e, out);
   if (io.full && out.write_state) write_full_state<T>(w, io.full + e * FullState<T>::SIZE);
   ANM_PHASE(6);
 }
@@ -728,7 +791,7 @@ __device__ int64_t load_record(const double* r, StepCtx<T>& ctx, EnvWork<T>& w, 
   return int64_t(r[R::E]);
 }
 
-template <class T, bool FULL>
+template <class T, bool FULL, bool EP = false>
 __device__ __forceinline__ void epilogue_stores(const EnvIO& io, int64_t e0, int64_t e, int lane, bool store, int32_t ts_prev,
                                                 StepOut<T, 1>& out, const EnvWork<T>& w, double* lds) {
   constexpr int S = T::SDIM + 1;
@@ -741,7 +804,7 @@ __device__ __forceinline__ void epilogue_stores(const EnvIO& io, int64_t e0, int
     state_dup = same;
   }
   if (store) {
-    store_step_scalars<T, 1>(io, e, out, true, ts_prev);
+    store_step_scalars<T, 1, EP>(io, e, out, true, ts_prev);
     if (io.state_same && out.write_state) io.state_same[e] = state_dup ? 1 : 0;
     if (out.write_state) io.aux_index[e] = int32_t(out.state[T::SDIM]);
     if constexpr (FULL) {
@@ -866,7 +929,8 @@ __device__ void op_step_view(cptr_t C, const EnvIO& io, SolverOpts so, int64_t n
 // (Measured and left out, profiles/r05_h_*: one throw-away scalar load per 64-byte line of the constant buffer while the wavefront
 // waits for its action rows, so that the dozen dependent batches of constant loads along the prologue hit the scalar cache --
 // headline kernel 87.03 -> 86.79 us over four same-box pairs, 524 288 environments unchanged: not worth 40 instructions.)
-template <class T, class JT, bool FULL>
+// EP: the launch serves the episode time limit and statistics (k_step_rows_ep; see store_step_scalars)
+template <class T, class JT, bool FULL, bool EP = false>
 __device__ void op_step_rows(cptr_t C, const EnvIO& io, SolverOpts so, int64_t n, double* lds) {
   typedef Dims<T> D;
   constexpr int S = T::SDIM + 1;
@@ -891,6 +955,8 @@ __device__ void op_step_rows(cptr_t C, const EnvIO& io, SolverOpts so, int64_t n
   in.aux_prev = double(aux_prev_i);
   in.reset_count = io.autoreset ? io.reset_count[ec] : 0;
   const int32_t ts_prev = io.timestep ? io.timestep[ec] : 0;  // read now: the epilogue only stores
+  // time limit: with autoreset an environment past it is re-initialised like a terminated one (without, it is stepped on)
+  if constexpr (EP) in.was_term = in.was_term || (io.autoreset && episode_timed_out(io.ep, ts_prev));
 
   // ---- coalesced loads: 64 x ADIM doubles of actions
   {
@@ -967,7 +1033,7 @@ __device__ void op_step_rows(cptr_t C, const EnvIO& io, SolverOpts so, int64_t n
   }
   step_end<T, 1>(C, io, so, ec, ctx, w, st, out);
   const bool store = valid && !pending;
-  epilogue_stores<T, FULL>(io, e0, e, lane, store, ts_prev, out, w, lds);
+  epilogue_stores<T, FULL, EP>(io, e0, e, lane, store, ts_prev, out, w, lds);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1043,6 +1109,7 @@ __device__ void op_step_general(cptr_t C, const EnvIO& io, SolverOpts so, int64_
   // (uniform mode: the reset epoch is part of the key of every step's draws, autoreset or not)
   in.reset_count = ((io.autoreset || io.exo_mode) && io.reset_count) ? io.reset_count[ec] : 0;
   const int32_t ts_prev = io.timestep ? io.timestep[ec] : 0;
+  if (io.ep.on) in.was_term = in.was_term || (io.autoreset && episode_timed_out(io.ep, ts_prev));
 
   step_begin<T, JT, cptr_t, const double*, true>(C, C, io, so, ec, in, ctx, w, st, -1);
   constexpr bool CAN_GROUP = T::TREE != 0;
@@ -1087,7 +1154,7 @@ __device__ void op_step_general(cptr_t C, const EnvIO& io, SolverOpts so, int64_
   step_end<T, KM, false, RowOut>(C, io, so, ec, ctx, w, st, out);
   const bool store = valid;
   if (store) {
-    store_step_scalars<T, KM>(io, e, out, true, ts_prev);
+    store_step_scalars<T, KM, true>(io, e, out, true, ts_prev);
     if (io.aux_index && out.write_state) io.aux_index[e] = int32_t(out.row[T::SDIM]);
   }
   const bool zero_obs = ctx.absorbing || out.terminated == 1;   // anm_env.py:365-367, 442-446
@@ -1258,7 +1325,7 @@ __device__ void op_step_scatter(const EnvIO& io) {
     out.reward = r[Q::REWARD]; out.e_loss = r[Q::ELOSS]; out.penalty = r[Q::PENALTY];
     out.n_iter = int(r[Q::NITER]); out.terminated = int(r[Q::TERM]); out.timestep_op = int(r[Q::TSOP]);
     static_for<0, T::NDES>([&](auto I) { out.soc[I] = r[Q::SOC + I]; });
-    store_step_scalars<T, 1>(io, e, out);
+    store_step_scalars<T, 1, true>(io, e, out);   // (reads timestep[e] itself: the first launch stored nothing for e)
     if (flags & 1) {
       if (io.state_same) io.state_same[e] = 0;
       io.aux_index[e] = int32_t(r[Q::STATE + T::SDIM]);

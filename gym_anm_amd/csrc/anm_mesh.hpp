@@ -798,7 +798,9 @@ __global__ __launch_bounds__(WG ? 512 : 256, SW == 2 ? ANM_MESH_MINWAVES2 : SW) 
       soc = io.t.soc[ee * W_DES + slot];
     }
   } else {
-    const bool was_term = (mode == 2) && io.e.terminated[ee] != 0;
+    bool was_term = (mode == 2) && io.e.terminated[ee] != 0;
+    // episode time limit (io.e.ep, wave-uniform): with autoreset an environment past it is re-initialised like a terminated one
+    if (mode == 2 && io.e.ep.on && io.e.autoreset) was_term = was_term || episode_timed_out(io.e.ep, io.e.timestep[ee]);
     const bool series = io.e.exo == nullptr;
     resetting = (mode == 1) || (was_term && io.e.autoreset && series);
     skip = (mode == 2) && was_term && !resetting;
@@ -1404,6 +1406,7 @@ __global__ __launch_bounds__(WG ? 512 : 256, SW == 2 ? ANM_MESH_MINWAVES2 : SW) 
         for (int k = l; k < K; k += G) put(d.SDIM + k, s0[d.SDIM + k]);
       }
       if (l == 0) { io.e.converged[e] = converged ? 1 : 0; io.e.terminated[e] = 0; if (io.e.timestep) io.e.timestep[e] = 0; }
+      if (l == 0 && io.e.ep.on) episode_clear(io.e.ep, e);
       if (l == 0 && nr_diff) nr_diff[e] = fdiff;
     } else {
       if (l == 0) {
@@ -1412,6 +1415,7 @@ __global__ __launch_bounds__(WG ? 512 : 256, SW == 2 ? ANM_MESH_MINWAVES2 : SW) 
         io.e.terminated[e] = converged ? 0 : 1;
         if (io.e.timestep) io.e.timestep[e] = 0;
         io.e.reward[e] = 0.0; io.e.e_loss[e] = 0.0; io.e.penalty[e] = 0.0;
+        if (io.e.ep.on) episode_clear(io.e.ep, e);
       }
       lo_mode = converged ? 2 : 1;
     }
@@ -1436,14 +1440,18 @@ __global__ __launch_bounds__(WG ? 512 : 256, SW == 2 ? ANM_MESH_MINWAVES2 : SW) 
   if (l == 0) {
     const double c1 = rd[SF_C1], c2 = rd[SF_C2];
     io.e.terminated[e] = term ? 1 : 0;
+    double rwd;
     if (!term) {
       const double sg2 = (e_loss > 0.0) ? 1.0 : ((e_loss < 0.0) ? -1.0 : 0.0);
       const double elc = sg2 * fmin(fabs(e_loss), c1);
       const double pn = fmin(fmax(penalty, 0.0), c2);
-      io.e.e_loss[e] = elc; io.e.penalty[e] = pn; io.e.reward[e] = -(elc + pn);
+      rwd = -(elc + pn);
+      io.e.e_loss[e] = elc; io.e.penalty[e] = pn; io.e.reward[e] = rwd;
     } else {
-      io.e.reward[e] = rd[SF_RTERM]; io.e.e_loss[e] = c1; io.e.penalty[e] = c2;
+      rwd = rd[SF_RTERM];
+      io.e.reward[e] = rwd; io.e.e_loss[e] = c1; io.e.penalty[e] = c2;
     }
+    if (io.e.ep.on) episode_step(io.e.ep, e, rwd, term, io.e.timestep[e] + 1);   // (before the increment below)
     if (io.e.timestep) io.e.timestep[e] += 1;
   }
   dump = true;

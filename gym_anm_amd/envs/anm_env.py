@@ -29,6 +29,7 @@ import numpy as np
 import torch
 
 from .. import _lib
+from .. import episode as _episode
 from .. import errors as E
 from ..model import STATE_VARIABLES
 from ..simulator import BatchedSimulator, StateView, _stream_ptr
@@ -91,7 +92,7 @@ class BatchedANMEnv(GymEnv):
                  num_envs=1, device="cuda", tol=1e-5, max_iter=100, precision="f64", autoreset=False, series=None,
                  env_offset=0, impl=None, straggler_after="auto", straggler_mid="auto", handoff_after="auto", track_full=False,
                  fuse_observation=True, variants=None, env_variant=None, exogenous=None, exo_low=None, exo_high=None,
-                 _backend=None):  # fmt: skip
+                 max_episode_steps=None, episode_stats=False, _backend=None):  # fmt: skip
         GymEnv.reset(self, seed=seed)
         self.K, self.gamma, self.lamb, self.delta_t = K, gamma, lamb, delta_t
         self.aux_bounds = aux_bounds
@@ -112,6 +113,13 @@ class BatchedANMEnv(GymEnv):
         sim = self.simulator
         self.device = sim.device
         check_env_args(K, delta_t, lamb, gamma, observation, aux_bounds, sim.state_bounds)
+        # episode time limit and statistics, kept by the step kernels (gym_anm_amd/episode.py has the semantics)
+        self.max_episode_steps = _episode.check_limit(max_episode_steps)
+        self.episode_stats = bool(episode_stats)
+        if (self.max_episode_steps or self.episode_stats) and sim.backend.device_type != "cuda":
+            # (a backend that ignores the fields would run another task without saying so)
+            raise E.EnvInitializationError("max_episode_steps / episode_stats need the GPU library: this backend keeps no "
+                                           "episode time limit or statistics in its kernels")
 
         self.state_values = self._expand_all_ids(
             [("dev_p", "all", "MW"), ("dev_q", "all", "MVAr"), ("des_soc", "all", "MWh"), ("gen_p_max", "all", "MW"),
@@ -146,7 +154,27 @@ class BatchedANMEnv(GymEnv):
         self._conv_bool = torch.ones(E_, dtype=torch.bool, device=self.device)
         self._conv_stale = False
         self._reset_count = torch.zeros(E_, dtype=torch.int32, device=self.device)
-        self._truncated = torch.zeros(E_, dtype=torch.bool, device=self.device)
+        self._trunc_u8 = torch.zeros(E_, dtype=torch.uint8, device=self.device)
+        self._truncated = self._trunc_u8.view(torch.bool)  # zero-copy: written by the kernels when a limit is set
+        self._episode_bufs = None
+        if self.episode_stats:
+            i32 = dict(dtype=torch.int32, device=self.device)
+            self.episode_return = torch.zeros(E_, **f64)
+            self.episode_discounted_return = torch.zeros(E_, **f64)
+            self._episode_discount = torch.ones(E_, **f64)
+            self.last_episode_return = torch.zeros(E_, **f64)
+            self.last_episode_discounted_return = torch.zeros(E_, **f64)
+            self.last_episode_length = torch.zeros(E_, **i32)
+            self.episodes_done = torch.zeros(E_, **i32)
+        if self.max_episode_steps or self.episode_stats:
+            b = _lib.EpisodeBuffers(truncated=self._trunc_u8.data_ptr())
+            if self.episode_stats:
+                b.ep_return, b.ep_disc_return = self.episode_return.data_ptr(), self.episode_discounted_return.data_ptr()
+                b.ep_discount = self._episode_discount.data_ptr()
+                b.last_return = self.last_episode_return.data_ptr()
+                b.last_disc_return = self.last_episode_discounted_return.data_ptr()
+                b.last_length, b.episodes_done = self.last_episode_length.data_ptr(), self.episodes_done.data_ptr()
+            self._episode_bufs = b
         # key of the device-side sampler (reset(options={"sampler": "device"}), autoreset).  Unseeded
         # environments draw it from np_random (entropy-seeded in that case), so that two unseeded
         # environments -- e.g. the ranks of a sharded batch -- are not correlated; explicit seeds stay
@@ -193,7 +221,10 @@ class BatchedANMEnv(GymEnv):
         self._obs_is_state = self.obs_values is not None and self.obs_values == self.state_values
         if self._obs_is_state and self.observation_space is not None:
             slo, shi = np.asarray(self.observation_space.low, float), np.asarray(self.observation_space.high, float)
-        cfg = _lib.EnvConfig(
+        ep_kw = {}
+        if self._episode_bufs is not None:
+            ep_kw = dict(max_episode_steps=self.max_episode_steps or 0, episode=C.pointer(self._episode_bufs))
+        cfg = (_lib.EnvConfigEpisode if ep_kw else _lib.EnvConfig)(
             K=K, gamma=float(gamma), clip_e_loss=float(c1), clip_penalty=float(c2),
             obs_low=_lib.as_c(slo, np.float64)[1], obs_high=_lib.as_c(shi, np.float64)[1],
             series=None if self._series is None else self._series.ctypes.data_as(_lib.c_double_p),
@@ -201,6 +232,7 @@ class BatchedANMEnv(GymEnv):
             exo_mode=_lib.EXO_UNIFORM if self._uniform else _lib.EXO_HOST,
             exo_low=self.exo_low.ctypes.data_as(_lib.c_double_p) if self._uniform else None,
             exo_high=self.exo_high.ctypes.data_as(_lib.c_double_p) if self._uniform else None,
+            **ep_kw,
         )  # fmt: skip
         self._cfg_keep = (slo, shi)
         with sim._device_ctx():
@@ -444,6 +476,16 @@ class BatchedANMEnv(GymEnv):
     @property
     def terminated(self):
         return self._term_bool
+
+    @property
+    def truncated(self):
+        """``timestep >= max_episode_steps`` as the last step (or reset) left it; all False without a limit."""
+        return self._truncated
+
+    @property
+    def episode_length(self):
+        """Steps of the running episode (``timestep``)."""
+        return self.timestep
 
     @property
     def pfe_converged(self):

@@ -140,7 +140,11 @@ class MixedBatchedANMEnv:
     ``[0, 0]``); ``single_observation_spaces[k]`` / ``single_action_spaces[k]`` are those of task k."""
 
     def __init__(self, tasks, env_task, device="cuda", seed=None, tol=1e-5, max_iter=100, precision="f64", autoreset=False,
-                 env_offset=0, streams=True):
+                 env_offset=0, streams=True, max_episode_steps=None, episode_stats=False):
+        if max_episode_steps is not None or episode_stats:
+            # (the kernels keep the time limit and the statistics per batch row of ONE model; a batch view is refused by the library)
+            raise E.EnvInitializationError("MixedBatchedANMEnv steps through batch views, which take no episode time limit or "
+                                           "episode statistics (max_episode_steps / episode_stats): use BatchedANMEnv")
         env_task = np.asarray(env_task, dtype=np.int64)
         if env_task.ndim != 1 or env_task.size == 0 or env_task.min() < 0 or env_task.max() >= len(tasks):
             raise ValueError("env_task must be a 1-D array of indices into `tasks`")

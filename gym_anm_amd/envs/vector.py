@@ -33,6 +33,10 @@ class NumpyVectorEnv:
         self.render_mode = None
         env.check_actions = False                     # checked here on the host, where the data already is
         self._pinned = None
+        # episode statistics kept by the step kernels (BatchedANMEnv(episode_stats=True)): reported like Gymnasium's vector
+        # RecordEpisodeStatistics, the rows whose episode ended at a step found from the change of `episodes_done`
+        self._stats = bool(getattr(env, "episode_stats", False))
+        self._n_done = env.episodes_done.cpu().numpy().copy() if self._stats else None
 
     def reset(self, *, seed=None, options=None):
         obs, info = self.env.reset(seed=seed, options=options)
@@ -44,6 +48,17 @@ class NumpyVectorEnv:
         if actions.shape != (self.num_envs, lo.shape[0]) or not ((actions >= lo) & (actions <= hi)).all():
             raise AssertionError("Action %r (%s) invalid." % (actions, type(actions)))  # anm_env.py:356-357
         obs, rew, term, trunc, info = self.env.step(torch.from_numpy(actions).to(self.env.device))
+        if self._stats:
+            env = self.env
+            n_done = env.episodes_done.cpu().numpy()
+            ended = n_done != self._n_done
+            self._n_done = n_done.copy()
+            info = dict(info)
+            # "d": the discounted return (the return the reference's write-ups report); rows outside the mask are 0
+            info["episode"] = {"r": np.where(ended, env.last_episode_return.cpu().numpy(), 0.0),
+                               "l": np.where(ended, env.last_episode_length.cpu().numpy(), 0).astype(np.int32),
+                               "d": np.where(ended, env.last_episode_discounted_return.cpu().numpy(), 0.0)}
+            info["_episode"] = ended
         return (obs.cpu().numpy(), rew.cpu().numpy(), term.cpu().numpy(), trunc.cpu().numpy(), info)
 
     def close(self):

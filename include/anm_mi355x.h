@@ -83,9 +83,32 @@ typedef struct anm_dims {
   int32_t const_doubles;        /* size of the device constant buffer (diagnostic) */
 } anm_dims;
 
+/* Episode buffers (anm_env_config.episode): DEVICE arrays [num_envs], caller-owned, alive while the model uses them;
+ * every one is nullable (NULL = not kept).  The step and reset kernels write them; gym_anm_amd/episode.py states what.
+ *   truncated         1 after a step that left timestep >= max_episode_steps, 0 after a reset (never 1 without a limit)
+ *   ep_return         running sum of the rewards of the episode
+ *   ep_disc_return    ... discounted: fma(ep_discount, reward, ep_disc_return), one rounding
+ *   ep_discount       gamma^(steps of the episode so far); goes with ep_disc_return (both or neither)
+ *   last_return, last_disc_return, last_length   those of the last FINISHED episode, its last step included
+ *                     (last_return needs ep_return, last_disc_return needs ep_disc_return)
+ *   episodes_done     episodes finished so far (never cleared by the library)
+ * An episode finishes on the step that terminates it or brings timestep to max_episode_steps. */
+typedef struct anm_episode_buffers {
+  uint8_t* truncated;
+  double* ep_return;
+  double* ep_disc_return;
+  double* ep_discount;
+  double* last_return;
+  double* last_disc_return;
+  int32_t* last_length;
+  int32_t* episodes_done;
+} anm_episode_buffers;
+
 /* Environment-level constants (ANMEnv.__init__, anm_env.py:79-156). */
 typedef struct anm_env_config {
   int32_t K;          /* number of auxiliary variables at the tail of the state vector */
+  int32_t tail;       /* which fields behind exo_high the caller's struct HAS (this slot was alignment padding: zero-filled
+                         structs of callers that end at exo_high say 0): ANM_ENV_TAIL_NONE or ANM_ENV_TAIL_EPISODE */
   double gamma;       /* discount factor (terminal reward -c2/(1-gamma), anm_env.py:430) */
   double clip_e_loss; /* costs_clipping[0] (+inf = none) */
   double clip_penalty;/* costs_clipping[1] (+inf = none) */
@@ -106,7 +129,18 @@ typedef struct anm_env_config {
   int32_t exo_mode;
   const double* exo_low;
   const double* exo_high;
+  /* ---- read only when tail >= ANM_ENV_TAIL_EPISODE ----
+   * Episode time limit and statistics, kept by the step kernels (zero / NULL: neither).
+   * max_episode_steps = T > 0: a step that leaves timestep >= T sets truncated; with autoreset an environment whose timestep
+   * has reached T on entry is re-initialised instead of stepped, exactly like a terminated one (without autoreset it is
+   * stepped on, and nothing but the buffers below differs from a model without a limit).  0 = no limit, < 0 refused.
+   * episode: HOST struct of device pointers (copied by anm_model_set_env), NULL = no buffers.
+   * A limit or a buffer needs `timestep` in anm_step_f64 and does not go with a batch view (anm_model_bind_view). */
+  int32_t max_episode_steps;
+  const anm_episode_buffers* episode;
 } anm_env_config;
+#define ANM_ENV_TAIL_NONE 0
+#define ANM_ENV_TAIL_EPISODE 1
 #define ANM_EXO_HOST 0
 #define ANM_EXO_UNIFORM 1
 
@@ -256,7 +290,9 @@ int anm_transition_f64(anm_model* m, int64_t num_envs, const double* p_load, con
  * (rng_seed, env_offset + env, reset_count[env]); reset_count[env] is then incremented.
  * init_state == NULL, ANM_EXO_UNIFORM: step index 0, loads and generator potentials from the step stream at index 0,
  * generator Q and storage SoC as in series mode (rng.py: uniform_init_state); reset_count[env] is incremented.
- * (The mode goes with neither parameter classes nor a batch view: refused.) */
+ * (The mode goes with neither parameter classes nor a batch view: refused.)
+ * Episode buffers (anm_env_config.episode): truncated is cleared and ep_return, ep_disc_return, ep_discount are set to
+ * 0, 0, 1 for the environments the call touches; last_* and episodes_done are left alone. */
 int anm_reset_f64(anm_model* m, int64_t num_envs, const double* init_state, const uint8_t* mask,
                   uint64_t rng_seed, uint64_t env_offset, int32_t* reset_count, double* soc, double* state, double* obs, uint8_t* converged, uint8_t* terminated,
                   int32_t* timestep, int32_t* nr_iters, double* full, int32_t* aux_index,
@@ -315,6 +351,11 @@ int anm_step_ws_record_doubles(void);
  *        the global index of this batch's first environment, so a batch sharded over several GPUs
  *        draws exactly what the unsharded batch would.  (Uniform mode: the initial state of that mode, see
  *        anm_reset_f64.)
+ *   episode time limit and statistics (anm_env_config.max_episode_steps / .episode; `timestep` must be given): with
+ *        autoreset, "terminated on entry" above reads "terminated, or timestep >= max_episode_steps, on entry".  A real
+ *        step writes truncated = (timestep after >= limit) and updates the statistics; the re-initialising call
+ *        writes truncated = 0 and clears the running values; the no-op step of an absorbing environment touches
+ *        neither.  Still one launch (the two-launch step: the same launches), nothing allocated, graph-capturable.
  *   aux_index (optional, series mode, K = 1): int32 [E] compact copy of the time index kept by the
  *        library next to `state`; when given (and `full` is NULL) the thread-per-environment family
  *        uses its coalesced-row kernel: action / state / obs rows move through LDS as whole-wave
