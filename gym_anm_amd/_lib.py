@@ -100,6 +100,7 @@ class FullLayout(C.Structure):
 
 SOLVE_F64, SOLVE_F32 = 0, 1
 EXO_HOST, EXO_UNIFORM = 0, 1   # anm_env_config.exo_mode
+IO_F64, IO_F32 = 0, 1   # anm_model_set_io
 IMPL_THREAD, IMPL_RADIAL, IMPL_MESH = 0, 1, 2
 HANDOFF_NEVER, HANDOFF_AUTO = -1, -2
 
@@ -131,6 +132,7 @@ ABI = {
     "anm_model_set_class_obs_bounds": (C.c_int, [C.c_void_p, C.c_int32, c_double_p, c_double_p]),
     "anm_model_bind_env_classes": (C.c_int, [C.c_void_p, _P, C.c_int64]),
     "anm_model_bind_state_same": (C.c_int, [C.c_void_p, _P]),
+    "anm_model_set_io": (C.c_int, [C.c_void_p, C.c_int32]),
     "anm_model_bind_nr_diff": (C.c_int, [C.c_void_p, _P]),
     "anm_model_bind_nr_start": (C.c_int, [C.c_void_p, _P]),
     "anm_model_bind_view": (C.c_int, [C.c_void_p, C.POINTER(BatchView)]),
@@ -152,9 +154,16 @@ ABI = {
 }  # fmt: skip
 
 
-def bind(cdll):
-    """Attach argtypes / restypes; raises AttributeError if the library lacks a declared symbol."""
+# entry points of modes that live in the GPU kernels alone: a backend that is not the GPU library (the host test double)
+# may lack them -- the host layer refuses those modes on such a backend before it would call them
+GPU_ONLY = ("anm_model_set_io",)
+
+
+def bind(cdll, optional=()):
+    """Attach argtypes / restypes; raises AttributeError if the library lacks a declared symbol (but those in `optional`)."""
     for name, (res, args) in ABI.items():
+        if name in optional and not hasattr(cdll, name):
+            continue
         fn = getattr(cdll, name)
         fn.restype = res
         fn.argtypes = args
@@ -165,7 +174,7 @@ class Backend:
     """A bound per-topology library plus what the host layer needs to know about it."""
 
     def __init__(self, cdll, device_type, path):
-        self.lib = bind(cdll)
+        self.lib = bind(cdll, optional=() if device_type == "cuda" else GPU_ONLY)
         self.device_type = device_type  # "cuda" for the product; the test double says "cpu"
         self.path = path
         self.generic = False  # True: library compiled for another topology, lane-group kernel only

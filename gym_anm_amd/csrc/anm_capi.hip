@@ -120,6 +120,17 @@ __global__ __launch_bounds__(BLOCK, ANM_ROWS_WAVES) void k_step_rows_ep(cptr_t C
 #endif
 }
 
+// the fast path with float32 action, obs and reward I/O (anm_model_set_io, ANM_IO_F32), without and with the episode
+// time limit and statistics: kernels of their own under their own names, so that k_step_rows / k_step_rows_ep carry none of it
+template <class JT, bool EP>
+__global__ __launch_bounds__(BLOCK, ANM_ROWS_WAVES) void k_step_rows_io32(cptr_t C0, EnvIO io, SolverOpts so, int64_t n, ClassSel cs) {
+#ifndef ANM_DEV_LANE_GROUPS_ONLY   // (tuning builds of the lane-group kernels alone: minutes less to compile)
+  __shared__ double lds[64 * (Topo::SDIM + 2)];
+  const cptr_t C = class_constants(C0, cs, int64_t(blockIdx.x) * BLOCK);
+  op_step_rows<Topo, JT, false, EP, true>(C, io, so, n, lds);
+#endif
+}
+
 // general step (host next_vars, K != 1, list-form observations, `full` dump): see op_step_general
 template <class JT>
 __global__ __launch_bounds__(BLOCK) void k_step_general(cptr_t C0, EnvIO io, SolverOpts so, int64_t n, ClassSel cs) {
@@ -275,6 +286,7 @@ struct anm_model {
   std::vector<double> exo_default;            // [2][n_load + n_gen] MW: loads [p_min, 0], generators [0, p_max]
   double* d_exo = nullptr;                    // [2][n_load + n_gen] MW: low, high of every unit
   EpisodeIO ep{};                             // episode time limit and statistics (anm_env_config.max_episode_steps / .episode)
+  int io_mode = ANM_IO_F64;                   // anm_model_set_io: float32 action / obs / reward arrays
   std::vector<cplx> ybus;
 
   std::array<Tables*, 3> tables() { return {&t_thread, &t_radial, &t_mesh}; }
@@ -726,6 +738,7 @@ int anm_model_set_classes(anm_model* m, int32_t n_classes, const anm_network_des
     return fail("anm_model_set_classes: not while a batch view is bound (anm_model_bind_view)");
   if (n_classes < 1 || n_classes > 65536) return fail("anm_model_set_classes: n_classes must be in [1, 65536]");
   if (n_classes > 1 && m->exo_mode != ANM_EXO_HOST) return fail("anm_model_set_classes: the uniform exogenous mode does not take parameter classes");
+  if (n_classes > 1 && m->io_mode == ANM_IO_F32) return fail("anm_model_set_classes: the float32 I/O mode (anm_model_set_io) does not take parameter classes");
   if (n_classes > 1 && !descs) return fail("anm_model_set_classes: null descriptions");
   std::vector<std::vector<double>> xc, xh, xm;
   for (int k = 1; k < n_classes; ++k) {
@@ -790,6 +803,7 @@ int anm_model_bind_env_classes(anm_model* m, const int32_t* env_class, int64_t n
   if (m->has_view)   // (the same rule as anm_model_bind_view, from the other side: k_mesh looks a block's
     // class up by launch slot and an environment's by its index in the batch)
     return fail("anm_model_bind_env_classes: not while a batch view is bound (anm_model_bind_view)");
+  if (m->io_mode == ANM_IO_F32) return fail("anm_model_bind_env_classes: the float32 I/O mode (anm_model_set_io) does not take parameter classes");
   if (num_envs <= 0) return fail("anm_model_bind_env_classes: num_envs must be positive");
   const int n_classes = m->n_classes();
   std::vector<int32_t> h(static_cast<size_t>(num_envs));
@@ -826,6 +840,8 @@ int anm_model_bind_env_classes(anm_model* m, const int32_t* env_class, int64_t n
 int anm_model_bind_state_same(anm_model* m, uint8_t* state_same) {
   if (!m) return fail("anm_model_bind_state_same: null model");
   if (state_same && m->has_view) return fail("anm_model_bind_state_same: not while a batch view is bound");
+  if (state_same && m->io_mode == ANM_IO_F32)
+    return fail("anm_model_bind_state_same: not in the float32 I/O mode (anm_model_set_io): the state row has no float64 twin in obs and is always written");
   m->d_state_same = state_same;
   return 0;
 }
@@ -842,6 +858,20 @@ int anm_model_bind_nr_start(anm_model* m, const double* x0) {
   return 0;
 }
 
+int anm_model_set_io(anm_model* m, int32_t io) {
+  if (!m) return fail("anm_model_set_io: null model");
+  if (io != ANM_IO_F64 && io != ANM_IO_F32) return fail("anm_model_set_io: unknown value (ANM_IO_F64 | ANM_IO_F32)");
+  if (io == ANM_IO_F32) {
+    if (m->has_view) return fail("anm_model_set_io: the float32 I/O mode does not go with a batch view (anm_model_bind_view)");
+    if (m->n_classes() > 1 || m->d_env_class)
+      return fail("anm_model_set_io: the float32 I/O mode does not take parameter classes (anm_model_set_classes / anm_model_bind_env_classes)");
+    if (m->d_state_same)
+      return fail("anm_model_set_io: the float32 I/O mode does not go with anm_model_bind_state_same (the state row has no float64 twin in obs)");
+  }
+  m->io_mode = io;
+  return 0;
+}
+
 int anm_model_bind_view(anm_model* m, const anm_batch_view* v) {
   if (!m) return fail("anm_model_bind_view: null model");
   if (!v) {
@@ -850,6 +880,7 @@ int anm_model_bind_view(anm_model* m, const anm_batch_view* v) {
     return 0;
   }
   if (m->d_env_class) return fail("anm_model_bind_view: not together with parameter classes (anm_model_bind_env_classes)");
+  if (m->io_mode == ANM_IO_F32) return fail("anm_model_bind_view: a batch view does not go with the float32 I/O mode (anm_model_set_io)");
   if (m->n_obs > 0 && m->impl == ANM_IMPL_THREAD)
     return fail("anm_model_bind_view: the thread-per-environment family gathers no list-form observation through a view "
                 "(anm_model_set_obs): clear it, or move the model to a lane-group family first (anm_model_set_impl)");
@@ -1034,6 +1065,8 @@ int anm_reset_f64(anm_model* m, int64_t n, const double* init_state, const uint8
   io.aux_index = aux_index;
   io.nr_diff = m->d_nr_diff;
   io.ep = m->ep;
+  io.io32 = m->io_mode == ANM_IO_F32 ? 1 : 0;
+  if (io.io32 && m->has_view) return fail("anm_reset_f64: the float32 I/O mode (anm_model_set_io) does not go with a batch view (anm_model_bind_view)");
   if (io.ep.on && m->has_view) return fail("anm_reset_f64: an episode time limit or episode buffers do not go with a batch view (anm_model_bind_view)");
   int prec;
   SolverOpts so = solver(opts, prec);
@@ -1114,6 +1147,13 @@ static int make_step_io(anm_model* m, const double* action, const double* exo, c
     if (m->has_view) return fail("anm_step_f64: an episode time limit or episode buffers do not go with a batch view (anm_model_bind_view)");
     if (!timestep) return fail("anm_step_f64: an episode time limit or episode buffers need the timestep buffer");
   }
+  io.io32 = m->io_mode == ANM_IO_F32 ? 1 : 0;
+  if (io.io32) {
+    if (m->has_view) return fail("anm_step_f64: the float32 I/O mode (anm_model_set_io) does not go with a batch view (anm_model_bind_view)");
+    if (full && m->n_obs == 0)
+      return fail("anm_step_f64: the float32 I/O mode (anm_model_set_io) has no unfused observation gather: `full` + anm_gather_obs_f64 "
+                  "writes float64 observations; set the list in the kernel (anm_model_set_obs) or leave `full` NULL");
+  }
   io.n_obs = 0;
   io.state_magic = magic_div(m->dims.state_base_dim + m->K);
   if (m->t_thread.ok && m->impl == ANM_IMPL_THREAD && (m->n_obs > 0 || full)) {
@@ -1188,6 +1228,10 @@ static int launch_step(anm_model* m, const EnvIO& io_in, int64_t n, const anm_so
   if (io.aux_index && io.exo == nullptr && io.exo_mode == ANM_EXO_HOST && io.K == 1 && !io.full && io.n_obs == 0) {
     // fast path: series mode, "state" observation, nothing but the batch tensors
     int rc = by_precision(prec, [&](auto jt) {
+      if (io.io32) {
+        if (io.ep.on) return launch("launch k_step_rows_io32", k_step_rows_io32<decltype(jt), true>, grid, BLOCK, 0, s, C, io, so, n, cs);
+        return launch("launch k_step_rows_io32", k_step_rows_io32<decltype(jt), false>, grid, BLOCK, 0, s, C, io, so, n, cs);
+      }
       if (io.ep.on) return launch("launch k_step_rows_ep", k_step_rows_ep<decltype(jt)>, grid, BLOCK, 0, s, C, io, so, n, cs);
       return launch("launch k_step_rows", k_step_rows<decltype(jt), false>, grid, BLOCK, 0, s, C, io, so, n, cs);
     });

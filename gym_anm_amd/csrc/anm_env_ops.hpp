@@ -84,8 +84,12 @@ ANM_HD void write_state_obs(cptr_t C, const EnvWork<T>& w, Out& out) {
 struct RowPtrs {
   double* state;
   double* obs;
+  float* obs32 = nullptr;   // float32 I/O (EnvIO::io32): the obs row is this one, of floats
   ANM_HD void put_st(int k, double v) { state[k] = v; }
-  ANM_HD void put_ob(int k, double v) { obs[k] = v; }
+  ANM_HD void put_ob(int k, double v) {
+    if (obs32) obs32[k] = float(v);
+    else obs[k] = v;
+  }
 };
 
 struct TransitionIO {
@@ -271,7 +275,24 @@ struct EnvIO {
   const double* exo_lo;     // [NEXO] MW (device)
   const double* exo_hi;     // [NEXO] MW (device)
   EpisodeIO ep;             // episode time limit and statistics (all zero: off)
+  int io32;                 // float32 policy-facing I/O (anm_model_set_io; 0 = off): action, obs and reward point at floats
 };
+
+// Float32 policy-facing I/O (ANM_IO_F32; gym_anm_amd/io_dtype.py is the specification): the arrays behind EnvIO::action,
+// obs and reward hold floats of the same shapes.  An action entry widens to double exactly; an observation entry or a
+// reward is the double the float64 mode would have stored, converted ONCE (round to nearest even).  `f32` is wave-uniform.
+// (one address for both formats, element size by shift: the branch holds the access alone, not a second address computation)
+ANM_HD double io_load(const double* p, int64_t i, bool f32) {
+  const char* q = reinterpret_cast<const char*>(p) + (i << (f32 ? 2 : 3));
+  return f32 ? double(*reinterpret_cast<const float*>(q)) : *reinterpret_cast<const double*>(q);
+}
+ANM_HD void io_store(double* p, int64_t i, double v, bool f32) {
+  char* q = reinterpret_cast<char*>(p) + (i << (f32 ? 2 : 3));
+  if (f32) *reinterpret_cast<float*>(q) = float(v);
+  else *reinterpret_cast<double*>(q) = v;
+}
+// how a piece of code learns the mode: not at all (float64 alone), at compile time, or from EnvIO::io32 at run time
+constexpr int IO_F64 = 0, IO_F32 = 1, IO_RT = 2;
 
 // Split an init_state row (anm_env.py / simulator.py:248-268) into transition inputs.
 // (S0: anything indexable -- a row in memory or a register array with constant indices)
@@ -443,6 +464,7 @@ ANM_HD void reset_from(cptr_t C, const EnvIO& io, SolverOpts so, int64_t e, cons
   }
   if (!act) return;
   RowPtrs rows{io.state + e * S, io.obs + e * S};
+  if (io.io32) rows.obs32 = reinterpret_cast<float*>(io.obs) + e * S;
   finish_reset<T, Layout<T>::KMAX, S0>(C, w, s0, io.K, io.soc + e * WD, rows);
   io.converged[e] = w.converged ? 1 : 0;
   io.terminated[e] = 0;
@@ -678,7 +700,8 @@ ANM_HD void step_compute(cptr_t C, const EnvIO& io, SolverOpts so, int64_t e, co
 // everything of StepOut except the state / obs rows
 // EP: the caller serves the episode time limit and statistics (io.ep, a wave-uniform runtime switch); off, they are not in
 // the code at all (the fast path of the step keeps its instruction stream: k_step_rows / k_step_rows_ep)
-template <class T, int KCAP, bool EP = false>
+// IOM: the float32 I/O of the reward (IO_F64 | IO_F32 | IO_RT); the statistics above accumulate the double either way
+template <class T, int KCAP, bool EP = false, int IOM = IO_F64>
 ANM_HD void store_step_scalars(const EnvIO& io, int64_t e, const StepFlags<T>& o, bool have_ts = false,
                                int32_t ts_prev = 0) {  // have_ts: the caller already read timestep[e]
   if constexpr (EP) {
@@ -689,7 +712,8 @@ ANM_HD void store_step_scalars(const EnvIO& io, int64_t e, const StepFlags<T>& o
   }
   if (o.write_soc) static_for<0, T::NDES>([&](auto I) { io.soc[e * T::NDES + I] = o.soc[I]; });
   if (o.terminated >= 0) io.terminated[e] = uint8_t(o.terminated);
-  io.reward[e] = o.reward;
+  if constexpr (IOM == IO_F64) io.reward[e] = o.reward;
+  else io_store(io.reward, e, o.reward, IOM == IO_F32 || io.io32 != 0);
   if (o.write_costs) {
     io.e_loss[e] = o.e_loss;
     io.penalty[e] = o.penalty;
@@ -791,7 +815,9 @@ __device__ int64_t load_record(const double* r, StepCtx<T>& ctx, EnvWork<T>& w, 
   return int64_t(r[R::E]);
 }
 
-template <class T, bool FULL, bool EP = false>
+// IO32: float32 I/O of the obs rows and the reward (k_step_rows_io32 / _ep): the obs block leaves as 64 x S floats, whole-wave
+// 256-byte transactions with the same tail handling; the state rows are always written (no state_same in that mode)
+template <class T, bool FULL, bool EP = false, bool IO32 = false>
 __device__ __forceinline__ void epilogue_stores(const EnvIO& io, int64_t e0, int64_t e, int lane, bool store, int32_t ts_prev,
                                                 StepOut<T, 1>& out, const EnvWork<T>& w, double* lds) {
   constexpr int S = T::SDIM + 1;
@@ -804,7 +830,7 @@ __device__ __forceinline__ void epilogue_stores(const EnvIO& io, int64_t e0, int
     state_dup = same;
   }
   if (store) {
-    store_step_scalars<T, 1, EP>(io, e, out, true, ts_prev);
+    store_step_scalars<T, 1, EP, IO32 ? IO_F32 : IO_F64>(io, e, out, true, ts_prev);
     if (io.state_same && out.write_state) io.state_same[e] = state_dup ? 1 : 0;
     if (out.write_state) io.aux_index[e] = int32_t(out.state[T::SDIM]);
     if constexpr (FULL) {
@@ -812,7 +838,8 @@ __device__ __forceinline__ void epilogue_stores(const EnvIO& io, int64_t e0, int
     }
   }
   // ---- coalesced stores of the state and obs rows
-  auto store_rows = [&](double* gbase, const double* row, bool wr) {
+  auto store_rows = [&](auto* gbase, const double* row, bool wr) {
+    typedef std::remove_pointer_t<decltype(gbase)> GT;   // double, or float: converted as it is stored
     const unsigned long long mask = __ballot(wr && store);
     if (mask == 0ull) return;   // no row of this wavefront is written (the state rows that equal their obs rows: the usual case)
     static_for<0, S>([&](auto K) { lds[lane * SP + K] = row[K]; });
@@ -825,7 +852,7 @@ __device__ __forceinline__ void epilogue_stores(const EnvIO& io, int64_t e0, int
         const int l = idx / S, k = idx - l * S;
         v[J] = lds[l * SP + k];
       });
-      static_for<0, S>([&](auto J) { gbase[J * 64 + lane] = v[J]; });
+      static_for<0, S>([&](auto J) { gbase[J * 64 + lane] = GT(v[J]); });
     } else {
       bool on[S];
       static_for<0, S>([&](auto J) {
@@ -835,13 +862,14 @@ __device__ __forceinline__ void epilogue_stores(const EnvIO& io, int64_t e0, int
         on[J] = ((mask >> l) & 1ull) != 0;
       });
       static_for<0, S>([&](auto J) {
-        if (on[J]) gbase[J * 64 + lane] = v[J];
+        if (on[J]) gbase[J * 64 + lane] = GT(v[J]);
       });
     }
     ANM_WAVE_SYNC();
   };
   store_rows(io.state + e0 * S, out.state, out.write_state && !state_dup);
-  store_rows(io.obs + e0 * S, out.obs, out.write_obs);
+  if constexpr (IO32) store_rows(reinterpret_cast<float*>(io.obs) + e0 * S, out.obs, out.write_obs);
+  else store_rows(io.obs + e0 * S, out.obs, out.write_obs);
   ANM_PHASE(6);
 }
 
@@ -930,7 +958,10 @@ __device__ void op_step_view(cptr_t C, const EnvIO& io, SolverOpts so, int64_t n
 // waits for its action rows, so that the dozen dependent batches of constant loads along the prologue hit the scalar cache --
 // headline kernel 87.03 -> 86.79 us over four same-box pairs, 524 288 environments unchanged: not worth 40 instructions.)
 // EP: the launch serves the episode time limit and statistics (k_step_rows_ep; see store_step_scalars)
-template <class T, class JT, bool FULL, bool EP = false>
+// IO32: float32 I/O (k_step_rows_io32 / _ep, anm_model_set_io): the 64 x ADIM actions arrive as floats, 256 bytes per wave
+// transaction, and widen on their way into LDS; obs and reward leave as floats (epilogue_stores).  Compile-time, like EP:
+// the float64 kernels carry none of it
+template <class T, class JT, bool FULL, bool EP = false, bool IO32 = false>
 __device__ void op_step_rows(cptr_t C, const EnvIO& io, SolverOpts so, int64_t n, double* lds) {
   typedef Dims<T> D;
   constexpr int S = T::SDIM + 1;
@@ -958,14 +989,15 @@ __device__ void op_step_rows(cptr_t C, const EnvIO& io, SolverOpts so, int64_t n
   // time limit: with autoreset an environment past it is re-initialised like a terminated one (without, it is stepped on)
   if constexpr (EP) in.was_term = in.was_term || (io.autoreset && episode_timed_out(io.ep, ts_prev));
 
-  // ---- coalesced loads: 64 x ADIM doubles of actions
+  // ---- coalesced loads: 64 x ADIM doubles (IO32: floats) of actions
   {
-    const double* g = io.action + e0 * D::ADIM;
+    typedef std::conditional_t<IO32, float, double> AT;
+    const AT* g = reinterpret_cast<const AT*>(io.action) + e0 * D::ADIM;
     constexpr int AP = D::ADIM + 1;
     // all loads are issued before the first use (one exposed memory latency, not ADIM of them):
     // out-of-range lanes re-read the last element instead of branching around the load
     const int last = rows * D::ADIM - 1;
-    double tmp[D::ADIM > 0 ? D::ADIM : 1];
+    AT tmp[D::ADIM > 0 ? D::ADIM : 1];
     static_for<0, D::ADIM>([&](auto J) {
       const int idx = J * 64 + lane;
       tmp[J] = g[idx < last ? idx : last];
@@ -1033,7 +1065,7 @@ __device__ void op_step_rows(cptr_t C, const EnvIO& io, SolverOpts so, int64_t n
   }
   step_end<T, 1>(C, io, so, ec, ctx, w, st, out);
   const bool store = valid && !pending;
-  epilogue_stores<T, FULL, EP>(io, e0, e, lane, store, ts_prev, out, w, lds);
+  epilogue_stores<T, FULL, EP, IO32>(io, e0, e, lane, store, ts_prev, out, w, lds);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1083,16 +1115,26 @@ __device__ void op_step_general(cptr_t C, const EnvIO& io, SolverOpts so, int64_
   StepCtx<T> ctx;
   PFState<T> st;
   EnvWork<T> w;
+  const bool f32 = io.io32 != 0;   // float32 I/O of action, obs and reward: wave-uniform, here and where they are stored
   // ---- coalesced loads of the action rows (as op_step_rows)
   {
-    const double* g = io.action + e0 * D::ADIM;
+    const int64_t g0 = e0 * D::ADIM;
     constexpr int AP = D::ADIM + 1;
     const int last = rows * D::ADIM - 1;
     double tmp[D::ADIM > 0 ? D::ADIM : 1];
-    static_for<0, D::ADIM>([&](auto J) {
-      const int idx = J * 64 + lane;
-      tmp[J] = g[idx < last ? idx : last];
-    });
+    if (f32) {
+      const float* g = reinterpret_cast<const float*>(io.action) + g0;
+      static_for<0, D::ADIM>([&](auto J) {
+        const int idx = J * 64 + lane;
+        tmp[J] = double(g[idx < last ? idx : last]);
+      });
+    } else {
+      const double* g = io.action + g0;
+      static_for<0, D::ADIM>([&](auto J) {
+        const int idx = J * 64 + lane;
+        tmp[J] = g[idx < last ? idx : last];
+      });
+    }
     static_for<0, D::ADIM>([&](auto J) {
       const int idx = J * 64 + lane;
       if (idx <= last) ldsB[(idx / D::ADIM) * AP + (idx % D::ADIM)] = tmp[J];
@@ -1154,7 +1196,7 @@ __device__ void op_step_general(cptr_t C, const EnvIO& io, SolverOpts so, int64_
   step_end<T, KM, false, RowOut>(C, io, so, ec, ctx, w, st, out);
   const bool store = valid;
   if (store) {
-    store_step_scalars<T, KM, true>(io, e, out, true, ts_prev);
+    store_step_scalars<T, KM, true, IO_RT>(io, e, out, true, ts_prev);
     if (io.aux_index && out.write_state) io.aux_index[e] = int32_t(out.row[T::SDIM]);
   }
   const bool zero_obs = ctx.absorbing || out.terminated == 1;   // anm_env.py:365-367, 442-446
@@ -1169,13 +1211,13 @@ __device__ void op_step_general(cptr_t C, const EnvIO& io, SolverOpts so, int64_
       ANM_WAVE_SYNC();
       if (list) {  // obs[e0 + r, k] for flat index idx = r * n_obs + k: coalesced stores, LDS gathers
         const int total = rows * io.n_obs;
-        double* gobs = io.obs + e0 * io.n_obs;
+        const int64_t gobs0 = e0 * io.n_obs;
         for (int idx = lane; idx < total; idx += 64) {
           const int r = int(__umulhi(unsigned(idx), io.obs_magic));
           const int k = idx - r * io.n_obs;
           const double v = ldsA[r * RS + io.obs_index[k]] * io.obs_scale[k];
           const double c = fmin(fmax(v, io.obs_lo[k]), io.obs_hi[k]);
-          if ((obs_rows >> r) & 1ull) gobs[idx] = ((zero_rows >> r) & 1ull) ? 0.0 : c;
+          if ((obs_rows >> r) & 1ull) io_store(io.obs, gobs0 + idx, ((zero_rows >> r) & 1ull) ? 0.0 : c, f32);
         }
       }
       if (io.full) {
@@ -1197,7 +1239,7 @@ __device__ void op_step_general(cptr_t C, const EnvIO& io, SolverOpts so, int64_
   {
     const int total = rows * S;
     double* gstate = io.state + e0 * S;
-    double* gobs = io.obs + e0 * S;
+    const int64_t gobs0 = e0 * S;
     for (int idx = lane; idx < total; idx += 64) {
       const int r = int(__umulhi(unsigned(idx), io.state_magic));
       const int k = idx - r * S;
@@ -1205,7 +1247,7 @@ __device__ void op_step_general(cptr_t C, const EnvIO& io, SolverOpts so, int64_
       if ((state_rows >> r) & 1ull) gstate[idx] = v;
       if (!list && ((obs_rows >> r) & 1ull)) {
         const double c = fmin(fmax(v, C[L::OBS_LO + k]), C[L::OBS_HI + k]);
-        gobs[idx] = ((zero_rows >> r) & 1ull) ? 0.0 : c;
+        io_store(io.obs, gobs0 + idx, ((zero_rows >> r) & 1ull) ? 0.0 : c, f32);
       }
     }
   }
@@ -1325,7 +1367,7 @@ __device__ void op_step_scatter(const EnvIO& io) {
     out.reward = r[Q::REWARD]; out.e_loss = r[Q::ELOSS]; out.penalty = r[Q::PENALTY];
     out.n_iter = int(r[Q::NITER]); out.terminated = int(r[Q::TERM]); out.timestep_op = int(r[Q::TSOP]);
     static_for<0, T::NDES>([&](auto I) { out.soc[I] = r[Q::SOC + I]; });
-    store_step_scalars<T, 1, true>(io, e, out);   // (reads timestep[e] itself: the first launch stored nothing for e)
+    store_step_scalars<T, 1, true, IO_RT>(io, e, out);   // (reads timestep[e] itself: the first launch stored nothing for e)
     if (flags & 1) {
       if (io.state_same) io.state_same[e] = 0;
       io.aux_index[e] = int32_t(r[Q::STATE + T::SDIM]);
@@ -1334,7 +1376,7 @@ __device__ void op_step_scatter(const EnvIO& io) {
   if (flags & 1)
     for (int k = l; k < S; k += SCATTER_LANES) io.state[e * S + k] = r[Q::STATE + k];
   if (flags & 2)
-    for (int k = l; k < S; k += SCATTER_LANES) io.obs[e * S + k] = r[Q::OBS + k];
+    for (int k = l; k < S; k += SCATTER_LANES) io_store(io.obs, e * S + k, r[Q::OBS + k], io.io32 != 0);
 }
 #endif
 

@@ -872,7 +872,17 @@ __global__ __launch_bounds__(WG ? 512 : 256, SW == 2 ? ANM_MESH_MINWAVES2 : SW) 
         if (typ == DEV_LOAD) in_p = io.e.exo[ee * W_EXO + slot];
         else if (typ == DEV_CLASSICAL || typ == DEV_RENEWABLE) in_pot = io.e.exo[ee * W_EXO + d.NLOAD + slot];
       }
-      if (typ == DEV_CLASSICAL || typ == DEV_RENEWABLE) { in_p = a[slot]; in_q = a[d.NGEN + slot]; }
+      // (float32 I/O, EnvIO::io32: the action row holds floats, widened here; ONE wave-uniform branch, the float64 arm is
+      // the code it was)
+      if (io.e.io32) {
+        const float* af = reinterpret_cast<const float*>(io.e.action) + ee * W_ACT;
+        if (typ == DEV_CLASSICAL || typ == DEV_RENEWABLE) { in_p = af[slot]; in_q = af[d.NGEN + slot]; }
+        else if (typ == DEV_STORAGE) {
+          in_p = af[2 * d.NGEN + slot];
+          in_q = af[2 * d.NGEN + d.NDES + slot];
+          soc = io.e.soc[ee * W_DES + slot];
+        }
+      } else if (typ == DEV_CLASSICAL || typ == DEV_RENEWABLE) { in_p = a[slot]; in_q = a[d.NGEN + slot]; }
       else if (typ == DEV_STORAGE) {
         in_p = a[2 * d.NGEN + slot];
         in_q = a[2 * d.NGEN + d.NDES + slot];
@@ -1310,6 +1320,11 @@ __global__ __launch_bounds__(WG ? 512 : 256, SW == 2 ? ANM_MESH_MINWAVES2 : SW) 
   // mode and branch -- the branches only decide: lo_mode 0 none, 1 zeros, 2 gather; dump)
   int lo_mode = 0;
   bool dump = false;
+  // The output sections below exist twice, for float64 and for float32 obs rows and reward (EnvIO::io32, a wave-uniform
+  // flag; the float64 values rounded once as they are stored): ONE branch chooses, nothing of it is inside the Newton
+  // trips, and the float64 path is the code it was without the mode
+  auto outputs = [&](auto F32c) {
+  constexpr bool f32 = decltype(F32c)::value;
   double* state = io.e.state + e * W_ST;
   // the observation: clip(state, Box) next to the state row, or (a list is set: anm_env.py:497-521, 562-592; see
   // anm_radial.hpp) n_obs entries gathered from this environment's electrical state
@@ -1317,15 +1332,24 @@ __global__ __launch_bounds__(WG ? 512 : 256, SW == 2 ? ANM_MESH_MINWAVES2 : SW) 
   const int ON = list ? io.e.n_obs : W_ST;                                  // entries of an observation row
   const int OW = list ? (io.v.w_obs > 0 ? io.v.w_obs : io.e.n_obs) : W_ST;   // its stride (a view pads the rows)
   double* obs = io.e.obs + e * OW;
+  float* obs32 = reinterpret_cast<float*>(io.e.obs) + e * OW;
+  auto put_obs = [&](int k, double v) {
+    if constexpr (f32) obs32[k] = float(v);
+    else obs[k] = v;
+  };
+  auto put_reward = [&](double v) {
+    if constexpr (f32) reinterpret_cast<float*>(io.e.reward)[e] = float(v);
+    else io.e.reward[e] = v;
+  };
   cptr_t lo = C + d.off_obs_lo, hi = C + d.off_obs_hi;
   auto put = [&](int k, double v) {
     state[k] = v;
-    if (!list) obs[k] = fmin(fmax(v, lo[k]), hi[k]);
+    if (!list) put_obs(k, fmin(fmax(v, lo[k]), hi[k]));
   };
   auto list_obs = [&](bool zero) {
     if (!list) return;
     if (zero) {   // terminal / absorbing: the observation is 0 (anm_env.py:365-367, 442-446)
-      for (int k = l; k < ON; k += G) obs[k] = 0.0;
+      for (int k = l; k < ON; k += G) put_obs(k, 0.0);
       return;
     }
     // the row lives where the Jacobian blocks were (l_blk ... l_bw: free once the solve is over; anm_model_set_obs has
@@ -1362,7 +1386,7 @@ __global__ __launch_bounds__(WG ? 512 : 256, SW == 2 ? ANM_MESH_MINWAVES2 : SW) 
     ANM_MESH_SYNC();
     for (int k = l; k < ON; k += G) {
       const double v = row[io.e.obs_index[k]] * io.e.obs_scale[k];
-      obs[k] = fmin(fmax(v, io.e.obs_lo[k]), io.e.obs_hi[k]);
+      put_obs(k, fmin(fmax(v, io.e.obs_lo[k]), io.e.obs_hi[k]));
     }
   };
   do {
@@ -1380,8 +1404,8 @@ __global__ __launch_bounds__(WG ? 512 : 256, SW == 2 ? ANM_MESH_MINWAVES2 : SW) 
   if (skip) {
     if (mode == 2) {  // absorbing terminal state
       if (list) lo_mode = 1;
-      else for (int k = l; k < SD_; k += G) obs[k] = 0.0;
-      if (l == 0) { io.e.reward[e] = 0.0; if (io.e.nr_iters) io.e.nr_iters[e] = 0; }
+      else for (int k = l; k < SD_; k += G) put_obs(k, 0.0);
+      if (l == 0) { put_reward(0.0); if (io.e.nr_iters) io.e.nr_iters[e] = 0; }
     }
     break;
   }
@@ -1392,7 +1416,7 @@ __global__ __launch_bounds__(WG ? 512 : 256, SW == 2 ? ANM_MESH_MINWAVES2 : SW) 
       io.e.soc[e * W_DES + slot] = soc;
     }
     if (mode == 2 && !converged) {
-      for (int k = l; k < SD_; k += G) { state[k] = 0.0; if (!list) obs[k] = 0.0; }
+      for (int k = l; k < SD_; k += G) { state[k] = 0.0; if (!list) put_obs(k, 0.0); }
     } else {
       if (typ != DEV_NONE) { put(l, dev_p * base); put(d.ND + l, dev_q * base); }
       if (typ == DEV_STORAGE) put(2 * d.ND + slot, soc * base);
@@ -1414,7 +1438,7 @@ __global__ __launch_bounds__(WG ? 512 : 256, SW == 2 ? ANM_MESH_MINWAVES2 : SW) 
         io.e.reset_count[e] += 1;
         io.e.terminated[e] = converged ? 0 : 1;
         if (io.e.timestep) io.e.timestep[e] = 0;
-        io.e.reward[e] = 0.0; io.e.e_loss[e] = 0.0; io.e.penalty[e] = 0.0;
+        put_reward(0.0); io.e.e_loss[e] = 0.0; io.e.penalty[e] = 0.0;
         if (io.e.ep.on) episode_clear(io.e.ep, e);
       }
       lo_mode = converged ? 2 : 1;
@@ -1434,7 +1458,7 @@ __global__ __launch_bounds__(WG ? 512 : 256, SW == 2 ? ANM_MESH_MINWAVES2 : SW) 
       for (int k = l; k < K; k += G) put(d.SDIM + k, io.e.aux_next[e * W_AUX + k]);
     }
   } else {
-    for (int k = l; k < SD_; k += G) { state[k] = 0.0; if (!list) obs[k] = 0.0; }
+    for (int k = l; k < SD_; k += G) { state[k] = 0.0; if (!list) put_obs(k, 0.0); }
   }
   lo_mode = term ? 1 : 2;
   if (l == 0) {
@@ -1446,10 +1470,10 @@ __global__ __launch_bounds__(WG ? 512 : 256, SW == 2 ? ANM_MESH_MINWAVES2 : SW) 
       const double elc = sg2 * fmin(fabs(e_loss), c1);
       const double pn = fmin(fmax(penalty, 0.0), c2);
       rwd = -(elc + pn);
-      io.e.e_loss[e] = elc; io.e.penalty[e] = pn; io.e.reward[e] = rwd;
+      io.e.e_loss[e] = elc; io.e.penalty[e] = pn; put_reward(rwd);
     } else {
       rwd = rd[SF_RTERM];
-      io.e.reward[e] = rwd; io.e.e_loss[e] = c1; io.e.penalty[e] = c2;
+      put_reward(rwd); io.e.e_loss[e] = c1; io.e.penalty[e] = c2;
     }
     if (io.e.ep.on) episode_step(io.e.ep, e, rwd, term, io.e.timestep[e] + 1);   // (before the increment below)
     if (io.e.timestep) io.e.timestep[e] += 1;
@@ -1458,6 +1482,9 @@ __global__ __launch_bounds__(WG ? 512 : 256, SW == 2 ? ANM_MESH_MINWAVES2 : SW) 
   } while (false);
   // (lo_mode and dump are uniform over the lanes of an environment: list_obs synchronises them)
   if (list && lo_mode != 0) list_obs(lo_mode == 1);
+  };
+  if (io.e.io32) outputs(std::true_type{});
+  else outputs(std::false_type{});
   if (dump) write_full();
 }
 #endif  // __HIPCC__

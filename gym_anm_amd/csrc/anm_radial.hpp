@@ -414,7 +414,17 @@ __global__ __launch_bounds__(64, ANM_RADIAL_WAVES) void k_radial(Dims d, const i
         if (typ == DEV_LOAD) in_p = io.e.exo[ee * W_EXO + slot];
         else if (typ == DEV_CLASSICAL || typ == DEV_RENEWABLE) in_pot = io.e.exo[ee * W_EXO + d.NLOAD + slot];
       }
-      if (typ == DEV_CLASSICAL || typ == DEV_RENEWABLE) { in_p = a[slot]; in_q = a[d.NGEN + slot]; }
+      // (float32 I/O, EnvIO::io32: the action row holds floats, widened here; ONE wave-uniform branch, the float64 arm is
+      // the code it was)
+      if (io.e.io32) {
+        const float* af = reinterpret_cast<const float*>(io.e.action) + ee * W_ACT;
+        if (typ == DEV_CLASSICAL || typ == DEV_RENEWABLE) { in_p = af[slot]; in_q = af[d.NGEN + slot]; }
+        else if (typ == DEV_STORAGE) {
+          in_p = af[2 * d.NGEN + slot];
+          in_q = af[2 * d.NGEN + d.NDES + slot];
+          soc = io.e.soc[ee * W_DES + slot];
+        }
+      } else if (typ == DEV_CLASSICAL || typ == DEV_RENEWABLE) { in_p = a[slot]; in_q = a[d.NGEN + slot]; }
       else if (typ == DEV_STORAGE) {
         in_p = a[2 * d.NGEN + slot];
         in_q = a[2 * d.NGEN + d.NDES + slot];
@@ -758,6 +768,12 @@ __global__ __launch_bounds__(64, ANM_RADIAL_WAVES) void k_radial(Dims d, const i
     break;
   }
 
+  // The output sections below exist twice, for float64 and for float32 obs rows and reward (EnvIO::io32, a wave-uniform
+  // flag; the float64 values rounded once as they are stored): ONE branch chooses, nothing of it is inside the Newton
+  // trips, and the float64 path is the code it was without the mode
+  auto outputs = [&](auto F32c) {
+  constexpr bool f32 = decltype(F32c)::value;
+  do {
   double* state = io.e.state + e * W_ST;
   // the observation: clip(state, Box) next to the state row, or (a list is set: anm_env.py:497-521, 562-592) n_obs entries
   // gathered from this environment's electrical state
@@ -765,17 +781,26 @@ __global__ __launch_bounds__(64, ANM_RADIAL_WAVES) void k_radial(Dims d, const i
   const int ON = list ? io.e.n_obs : W_ST;                                  // entries of an observation row
   const int OW = list ? (io.v.w_obs > 0 ? io.v.w_obs : io.e.n_obs) : W_ST;   // its stride (a view pads the rows)
   double* obs = io.e.obs + e * OW;
+  float* obs32 = reinterpret_cast<float*>(io.e.obs) + e * OW;
+  auto put_obs = [&](int k, double v) {
+    if constexpr (f32) obs32[k] = float(v);
+    else obs[k] = v;
+  };
+  auto put_reward = [&](double v) {
+    if constexpr (f32) reinterpret_cast<float*>(io.e.reward)[e] = float(v);
+    else io.e.reward[e] = v;
+  };
   cptr_t lo = C + d.off_obs_lo, hi = C + d.off_obs_hi;
   auto put = [&](int k, double v) {
     state[k] = v;
-    if (!list) obs[k] = fmin(fmax(v, lo[k]), hi[k]);
+    if (!list) put_obs(k, fmin(fmax(v, lo[k]), hi[k]));
   };
   // (called by all lanes of an environment together -- every condition around it is uniform over the lane group -- so the
   // row is written and read back in program order of one control path: LDS operations of a wavefront complete in order)
   auto list_obs = [&](bool zero) {
     if (!list) return;
     if (zero) {   // terminal / absorbing: the observation is 0 (anm_env.py:365-367, 442-446)
-      for (int k = l; k < ON; k += G) obs[k] = 0.0;
+      for (int k = l; k < ON; k += G) put_obs(k, 0.0);
       return;
     }
     double* row = sh_obs_rows + (t / G) * (d.FS + KMAX);
@@ -809,14 +834,14 @@ __global__ __launch_bounds__(64, ANM_RADIAL_WAVES) void k_radial(Dims d, const i
     ANM_GROUP_SYNC();
     for (int k = l; k < ON; k += G) {
       const double v = row[io.e.obs_index[k]] * io.e.obs_scale[k];
-      obs[k] = fmin(fmax(v, io.e.obs_lo[k]), io.e.obs_hi[k]);
+      put_obs(k, fmin(fmax(v, io.e.obs_lo[k]), io.e.obs_hi[k]));
     }
   };
   if (skip) {
     if (mode == 2) {  // absorbing terminal state
       if (list) list_obs(true);
-      else for (int k = l; k < S; k += G) obs[k] = 0.0;
-      if (l == 0) { io.e.reward[e] = 0.0; if (io.e.nr_iters) io.e.nr_iters[e] = 0; }
+      else for (int k = l; k < S; k += G) put_obs(k, 0.0);
+      if (l == 0) { put_reward(0.0); if (io.e.nr_iters) io.e.nr_iters[e] = 0; }
     }
     break;
   }
@@ -829,7 +854,7 @@ __global__ __launch_bounds__(64, ANM_RADIAL_WAVES) void k_radial(Dims d, const i
     if (mode == 2 && !converged) {
       // a redraw whose first power flow does not converge looks like the absorbing terminal state
       // until the next call draws again
-      for (int k = l; k < S; k += G) { state[k] = 0.0; if (!list) obs[k] = 0.0; }
+      for (int k = l; k < S; k += G) { state[k] = 0.0; if (!list) put_obs(k, 0.0); }
     } else {
       if (typ != DEV_NONE) { put(l, dev_p * base); put(d.ND + l, dev_q * base); }
       if (typ == DEV_STORAGE) put(2 * d.ND + slot, soc * base);
@@ -851,7 +876,7 @@ __global__ __launch_bounds__(64, ANM_RADIAL_WAVES) void k_radial(Dims d, const i
         io.e.reset_count[e] += 1;
         io.e.terminated[e] = converged ? 0 : 1;
         if (io.e.timestep) io.e.timestep[e] = 0;
-        io.e.reward[e] = 0.0; io.e.e_loss[e] = 0.0; io.e.penalty[e] = 0.0;
+        put_reward(0.0); io.e.e_loss[e] = 0.0; io.e.penalty[e] = 0.0;
         if (io.e.ep.on) episode_clear(io.e.ep, e);
       }
       list_obs(!converged);
@@ -872,7 +897,7 @@ __global__ __launch_bounds__(64, ANM_RADIAL_WAVES) void k_radial(Dims d, const i
       for (int k = l; k < K; k += G) put(d.SDIM + k, io.e.aux_next[e * W_AUX + k]);
     }
   } else {
-    for (int k = l; k < S; k += G) { state[k] = 0.0; if (!list) obs[k] = 0.0; }
+    for (int k = l; k < S; k += G) { state[k] = 0.0; if (!list) put_obs(k, 0.0); }
   }
   list_obs(term);
   if (l == 0) {
@@ -884,15 +909,19 @@ __global__ __launch_bounds__(64, ANM_RADIAL_WAVES) void k_radial(Dims d, const i
       const double elc = sg2 * fmin(fabs(e_loss), c1);
       const double pn = fmin(fmax(penalty, 0.0), c2);
       rwd = -(elc + pn);
-      io.e.e_loss[e] = elc; io.e.penalty[e] = pn; io.e.reward[e] = rwd;
+      io.e.e_loss[e] = elc; io.e.penalty[e] = pn; put_reward(rwd);
     } else {
       rwd = rd[SF_RTERM];
-      io.e.reward[e] = rwd; io.e.e_loss[e] = c1; io.e.penalty[e] = c2;
+      put_reward(rwd); io.e.e_loss[e] = c1; io.e.penalty[e] = c2;
     }
     if (io.e.ep.on) episode_step(io.e.ep, e, rwd, term, io.e.timestep[e] + 1);   // (before the increment below)
     if (io.e.timestep) io.e.timestep[e] += 1;
   }
   dump = true;
+  } while (false);
+  };
+  if (io.e.io32) outputs(std::true_type{});
+  else outputs(std::false_type{});
   } while (false);
   if (dump) write_full();
   ANM_PHASE(5);

@@ -18,6 +18,10 @@ an error: it sets ``terminated`` (anm_env.py:421), the environment then stays in
 zero state with reward 0 (anm_env.py:365-367) until it is reset -- explicitly through
 ``reset(options={"mask": ...})``, or by itself at the next ``step`` when ``autoreset=True``
 (series-mode tasks; Gymnasium's "next step" vector autoreset).
+
+Every tensor is float64 unless ``io_dtype=torch.float32``: then the kernels read float32 actions and write float32
+observations and rewards (the float64 values rounded once), the spaces are float32 ``Box``es and everything else stays
+float64 (gym_anm_amd/io_dtype.py).
 """
 
 from __future__ import annotations
@@ -31,6 +35,7 @@ import torch
 from .. import _lib
 from .. import episode as _episode
 from .. import errors as E
+from .. import io_dtype as _io
 from ..model import STATE_VARIABLES
 from ..simulator import BatchedSimulator, StateView, _stream_ptr
 from ..spaces import Box, GymEnv
@@ -92,7 +97,7 @@ class BatchedANMEnv(GymEnv):
                  num_envs=1, device="cuda", tol=1e-5, max_iter=100, precision="f64", autoreset=False, series=None,
                  env_offset=0, impl=None, straggler_after="auto", straggler_mid="auto", handoff_after="auto", track_full=False,
                  fuse_observation=True, variants=None, env_variant=None, exogenous=None, exo_low=None, exo_high=None,
-                 max_episode_steps=None, episode_stats=False, _backend=None):  # fmt: skip
+                 max_episode_steps=None, episode_stats=False, io_dtype=None, _backend=None):  # fmt: skip
         GymEnv.reset(self, seed=seed)
         self.K, self.gamma, self.lamb, self.delta_t = K, gamma, lamb, delta_t
         self.aux_bounds = aux_bounds
@@ -105,6 +110,12 @@ class BatchedANMEnv(GymEnv):
         self.num_envs = int(num_envs)
         self.autoreset = bool(autoreset)
         self.env_offset = int(env_offset)  # global index of environment 0 (sharded batches)
+        # float32 policy-facing I/O, produced and consumed by the kernels (gym_anm_amd/io_dtype.py has the semantics):
+        # actions in, observations and rewards out as float32; everything else stays float64
+        self.io_dtype = _io.check_io_dtype(io_dtype)
+        self._io32 = self.io_dtype == torch.float32
+        if self._io32 and (variants is not None or env_variant is not None):
+            raise E.EnvInitializationError("io_dtype=torch.float32 does not take parameter classes (variants=)")
 
         self.simulator = BatchedSimulator(network, delta_t, lamb, num_envs=num_envs, device=device, tol=tol,
                                           max_iter=max_iter, precision=precision, impl=impl,
@@ -121,28 +132,41 @@ class BatchedANMEnv(GymEnv):
             raise E.EnvInitializationError("max_episode_steps / episode_stats need the GPU library: this backend keeps no "
                                            "episode time limit or statistics in its kernels")
 
+        if self._io32 and sim.backend.device_type != "cuda":
+            # (a backend that ignores the mode would read float32 actions as doubles without saying so)
+            raise E.EnvInitializationError("io_dtype=torch.float32 needs the GPU library: this backend reads and writes "
+                                           "float64 arrays alone")
+
         self.state_values = self._expand_all_ids(
             [("dev_p", "all", "MW"), ("dev_q", "all", "MVAr"), ("des_soc", "all", "MWh"), ("gen_p_max", "all", "MW"),
              ("aux", "all", None)]
         )  # fmt: skip
         self.state_N = sum(len(s[1]) for s in self.state_values)
         lo, hi = sim.model.action_bounds()
-        self.action_space = Box(low=lo, high=hi, dtype=np.float64)
+        if self._io32:  # bounds rounded inward: every float32 point of the Box lies in the reference's float64 Box
+            lo, hi = _io.action_bounds32(lo, hi)
+        self.action_space = Box(low=lo, high=hi, dtype=np.float32 if self._io32 else np.float64)
         self.single_action_space = self.action_space
 
         self.obs_values = self._build_observation_space(observation)
         self.observation_space = self.observation_bounds()
+        # the float64 Box the kernels clip to; in float32 mode the space itself has its bounds rounded to nearest
+        self._obs_space64 = self.observation_space
         if self.observation_space is not None:
             self.observation_N = self.observation_space.shape[0]
+            if self._io32:
+                lo32, hi32 = _io.observation_bounds32(self.observation_space.low, self.observation_space.high)
+                self.observation_space = Box(low=lo32, high=hi32, dtype=np.float32)
         self.single_observation_space = self.observation_space
 
         # ---- device-resident per-environment state ------------------------------------------------
         E_, S = self.num_envs, self.state_N
         f64 = dict(dtype=torch.float64, device=self.device)
+        fio = dict(dtype=self.io_dtype, device=self.device)   # what the policy sees: obs and reward
         self._state_buf = torch.zeros((E_, S), **f64)
         self._state_same = None  # uint8 [E]: 1 = the state row equals the obs row and was left unwritten (see `state`)
-        self._state_obs = torch.zeros((E_, S), **f64)  # clip(state, state-space bounds), written by the kernel
-        self.reward = torch.zeros(E_, **f64)
+        self._state_obs = torch.zeros((E_, S), **fio)  # clip(state, state-space bounds), written by the kernel
+        self.reward = torch.zeros(E_, **fio)
         self.e_loss = torch.zeros(E_, **f64)
         self.penalty = torch.zeros(E_, **f64)
         self._term_u8 = torch.zeros(E_, dtype=torch.uint8, device=self.device)
@@ -180,8 +204,8 @@ class BatchedANMEnv(GymEnv):
         # environments -- e.g. the ranks of a sharded batch -- are not correlated; explicit seeds stay
         # deterministic.
         self.rng_seed = int(self.np_random.integers(2**62)) if seed is None else int(seed)
-        self._act_low = torch.as_tensor(lo, **f64)
-        self._act_high = torch.as_tensor(hi, **f64)
+        self._act_low = torch.as_tensor(lo, **fio)
+        self._act_high = torch.as_tensor(hi, **fio)
         self.check_actions = True
 
         # ---- environment constants for the kernels ---------------------------------------------------
@@ -220,7 +244,7 @@ class BatchedANMEnv(GymEnv):
         slo, shi = self._state_bounds_vectors()
         self._obs_is_state = self.obs_values is not None and self.obs_values == self.state_values
         if self._obs_is_state and self.observation_space is not None:
-            slo, shi = np.asarray(self.observation_space.low, float), np.asarray(self.observation_space.high, float)
+            slo, shi = np.asarray(self._obs_space64.low, float), np.asarray(self._obs_space64.high, float)
         ep_kw = {}
         if self._episode_bufs is not None:
             ep_kw = dict(max_episode_steps=self.max_episode_steps or 0, episode=C.pointer(self._episode_bufs))
@@ -237,6 +261,8 @@ class BatchedANMEnv(GymEnv):
         self._cfg_keep = (slo, shi)
         with sim._device_ctx():
             sim.backend.check(sim.backend.lib.anm_model_set_env(sim._handle, C.byref(cfg)), "anm_model_set_env")
+            if self._io32:
+                sim.backend.check(sim.backend.lib.anm_model_set_io(sim._handle, _lib.IO_F32), "anm_model_set_io")
         # parameter classes: the reference builds one environment per network, each clipping its observation to the
         # Box of ITS network (anm_env.py:193-233, 313-331).  For the "state" observation every class gets its own
         # bounds; `class_observation_bounds` has them ([n_classes, state_N] each).  (observation_space itself, one
@@ -260,6 +286,7 @@ class BatchedANMEnv(GymEnv):
         self._gather = None  # (index, scale, low, high) device tensors
         self._obs_fused = False
         self._obs_buf = None
+        self._obs_gather64 = None   # float32 mode: where reset() gathers a list-form observation before the one cast
         if self.obs_values is not None and not self._obs_is_state:
             self._gather = self._build_gather(self.obs_values)
             lib = sim.backend.lib
@@ -270,10 +297,18 @@ class BatchedANMEnv(GymEnv):
                 with sim._device_ctx():
                     sim.backend.check(lib.anm_model_set_obs(sim._handle, len(a_i), p_i, p_s, p_l, p_h), "anm_model_set_obs")
                 self._obs_fused = True
-                self._obs_buf = torch.zeros((E_, len(a_i)), dtype=torch.float64, device=self.device)
+                self._obs_buf = torch.zeros((E_, len(a_i)), **fio)
+            if self._io32 and not self._obs_fused:
+                raise E.EnvInitializationError(
+                    "io_dtype=torch.float32 needs the list-form observation gathered inside the step kernel: "
+                    + ("fuse_observation=False" if not fuse_observation else "this model cannot gather in its kernel")
+                    + " leaves it to anm_gather_obs_f64, which writes float64 observations")
         # track_full: also dump the electrical state of every step, so that simulator.state /
         # simulator.pfe_converged follow the environment like the reference's (simulator.py:529-537)
         self.track_full = bool(track_full)
+        if self._io32 and self.track_full and not self._obs_fused:
+            raise E.EnvInitializationError("io_dtype=torch.float32 takes track_full=True only next to a list-form observation "
+                                           "gathered inside the step kernel")
         self._need_full_reset = self._gather is not None or self.track_full
         self._need_full = (self._gather is not None and not self._obs_fused) or self.track_full
         self._after_step = False
@@ -287,7 +322,8 @@ class BatchedANMEnv(GymEnv):
         self._aux_index_ptr = None if self._aux_index is None else self._aux_index.data_ptr()
         # "state" observation on the fast path: obs = clip(state) is the state itself unless a bound bites, so
         # the kernel writes the state row only then and flags the rest (anm_model_bind_state_same)
-        if self._aux_index is not None and self._obs_is_state and sim.backend.device_type == "cuda":
+        # (float32 mode: the state row has no float64 twin in obs and is always written)
+        if self._aux_index is not None and self._obs_is_state and sim.backend.device_type == "cuda" and not self._io32:
             self._state_same = torch.zeros(E_, dtype=torch.uint8, device=self.device)
             with sim._device_ctx():
                 sim.backend.check(sim.backend.lib.anm_model_bind_state_same(sim._handle, self._state_same.data_ptr()),
@@ -437,12 +473,12 @@ class BatchedANMEnv(GymEnv):
                 if key.startswith("branch"):  # kA for branches is not defined by the reference (pu only)
                     kv_j = 0
                 scale.append(sim.unit_scale(key, unit, kv_j))
-        space = self.observation_space
+        space = self._obs_space64
         dev = self.device
         return (
             torch.as_tensor(index, dtype=torch.int32, device=dev),
             torch.as_tensor(scale, dtype=torch.float64, device=dev),
-            torch.as_tensor(np.asarray(space.low, float), dtype=torch.float64, device=dev),
+            torch.as_tensor(np.asarray(space.low, float), dtype=torch.float64, device=dev),   # (the float64 Box)
             torch.as_tensor(np.asarray(space.high, float), dtype=torch.float64, device=dev),
         )
 
@@ -456,13 +492,20 @@ class BatchedANMEnv(GymEnv):
         n_obs = index.numel()
         if self._obs_buf is None:
             self._obs_buf = torch.zeros((self.num_envs, n_obs), dtype=torch.float64, device=self.device)
+        out = self._obs_buf
+        if self._io32:   # (reset() only: gathered in float64, cast once -- io_dtype.py rule 5)
+            if self._obs_gather64 is None:
+                self._obs_gather64 = torch.zeros((self.num_envs, n_obs), dtype=torch.float64, device=self.device)
+            out = self._obs_gather64
         with sim._device_ctx():
             rc = sim.backend.lib.anm_gather_obs_f64(
                 self.num_envs, sim.full.shape[1], sim.full.data_ptr(), self._state_buf.shape[1], self.K,
                 self._state_buf.data_ptr(), self._term_u8.data_ptr(), n_obs, index.data_ptr(), scale.data_ptr(),
-                low.data_ptr(), high.data_ptr(), self._obs_buf.data_ptr(), _stream_ptr(self.device),
+                low.data_ptr(), high.data_ptr(), out.data_ptr(), _stream_ptr(self.device),
             )  # fmt: skip
         sim.backend.check(rc, "anm_gather_obs_f64")
+        if out is not self._obs_buf:
+            self._obs_buf.copy_(out)
         return self._obs_buf
 
     @property
@@ -669,8 +712,9 @@ class BatchedANMEnv(GymEnv):
 
     def step(self, action):
         sim = self.simulator
-        if not (isinstance(action, torch.Tensor) and action.dtype == torch.float64 and action.device == self.device):
-            action = torch.as_tensor(action, dtype=torch.float64, device=self.device)
+        # (float32 mode: a float32, contiguous, on-device tensor goes to the kernel as it is -- no copy, no second launch)
+        if not (isinstance(action, torch.Tensor) and action.dtype == self.io_dtype and action.device == self.device):
+            action = torch.as_tensor(action, dtype=self.io_dtype, device=self.device)
         if action.dim() == 1:
             action = action.unsqueeze(0)
         if action.shape != (self.num_envs, sim.dims.action_dim):

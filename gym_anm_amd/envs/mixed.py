@@ -140,7 +140,13 @@ class MixedBatchedANMEnv:
     ``[0, 0]``); ``single_observation_spaces[k]`` / ``single_action_spaces[k]`` are those of task k."""
 
     def __init__(self, tasks, env_task, device="cuda", seed=None, tol=1e-5, max_iter=100, precision="f64", autoreset=False,
-                 env_offset=0, streams=True, max_episode_steps=None, episode_stats=False):
+                 env_offset=0, streams=True, max_episode_steps=None, episode_stats=False, io_dtype=None):
+        from ..io_dtype import check_io_dtype
+
+        if check_io_dtype(io_dtype) != torch.float64:
+            # (float32 action / obs / reward I/O lives in the kernels of ONE model's own batch; a batch view is refused by the library)
+            raise E.EnvInitializationError("MixedBatchedANMEnv steps through batch views, which take no float32 I/O "
+                                           "(io_dtype=torch.float32): use BatchedANMEnv")
         if max_episode_steps is not None or episode_stats:
             # (the kernels keep the time limit and the statistics per batch row of ONE model; a batch view is refused by the library)
             raise E.EnvInitializationError("MixedBatchedANMEnv steps through batch views, which take no episode time limit or "

@@ -43,7 +43,7 @@ class NumpyVectorEnv:
         return obs.cpu().numpy(), info
 
     def step(self, actions):
-        actions = np.asarray(actions, dtype=np.float64)
+        actions = np.asarray(actions, dtype=self.single_action_space.dtype)   # (float32 with io_dtype=torch.float32)
         lo, hi = self.single_action_space.low, self.single_action_space.high
         if actions.shape != (self.num_envs, lo.shape[0]) or not ((actions >= lo) & (actions <= hi)).all():
             raise AssertionError("Action %r (%s) invalid." % (actions, type(actions)))  # anm_env.py:356-357

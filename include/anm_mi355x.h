@@ -231,6 +231,23 @@ int anm_model_bind_view(anm_model* m, const anm_batch_view* view);
  * bytes of the 401 an ANM6Easy env-step moves.  Kernels that always write both rows clear the flags. */
 int anm_model_bind_state_same(anm_model* m, uint8_t* state_same);
 
+/* Float32 policy-facing I/O.  ANM_IO_F64 (the default): every array of the entry points below holds doubles.  ANM_IO_F32:
+ * the parameters `action`, `obs` and `reward` of anm_step_f64 and anm_time_step_launches and `obs` of anm_reset_f64 point
+ * at FLOAT arrays of the same shapes (the C types of the parameters stay `double*`: cast).  The kernels widen every action
+ * entry to double (exact), compute in float64 exactly as in ANM_IO_F64, and store obs = (float) obs64 and reward =
+ * (float) reward64: ONE round-to-nearest-even conversion of the double the other mode would have stored (after the clip;
+ * subnormals kept, overflow to +-inf), for both forms of the observation, the zero rows of terminated environments and the
+ * rows an in-kernel autoreset writes.  state, soc, e_loss, penalty, the episode buffers and everything else stay float64
+ * and are bit-identical to an ANM_IO_F64 step fed the widened actions; the episode statistics accumulate the float64
+ * reward.  Still one launch, nothing allocated, graph-capturable (gym_anm_amd/io_dtype.py has the semantics).
+ * Refused: an unknown value; ANM_IO_F32 together with a batch view (anm_model_bind_view), with parameter classes
+ * (anm_model_set_classes with more than one class, anm_model_bind_env_classes), with anm_model_bind_state_same (the
+ * state row has no float64 twin in obs: it is always written) -- from either side -- and, at anm_step_f64, with `full`
+ * when no list-form observation is set in the kernel (`full` + anm_gather_obs_f64 writes float64 observations). */
+#define ANM_IO_F64 0
+#define ANM_IO_F32 1
+int anm_model_set_io(anm_model* m, int32_t io);
+
 /* The reference's solver returns the final mismatch next to the iteration count (`diff` of
  * _newton_raphson_sparse, solve_load_flow.py:176-226: ||F(x)||inf of the iterate it stopped at).  With an array bound here
  * (DEVICE double [num_envs], caller-owned, alive while bound; NULL unbinds) anm_transition_f64 and anm_reset_f64 write it per
@@ -292,7 +309,8 @@ int anm_transition_f64(anm_model* m, int64_t num_envs, const double* p_load, con
  * generator Q and storage SoC as in series mode (rng.py: uniform_init_state); reset_count[env] is incremented.
  * (The mode goes with neither parameter classes nor a batch view: refused.)
  * Episode buffers (anm_env_config.episode): truncated is cleared and ep_return, ep_disc_return, ep_discount are set to
- * 0, 0, 1 for the environments the call touches; last_* and episodes_done are left alone. */
+ * 0, 0, 1 for the environments the call touches; last_* and episodes_done are left alone.
+ * ANM_IO_F32 (anm_model_set_io): `obs` points at float [E, state_base_dim + K]; not through a batch view. */
 int anm_reset_f64(anm_model* m, int64_t num_envs, const double* init_state, const uint8_t* mask,
                   uint64_t rng_seed, uint64_t env_offset, int32_t* reset_count, double* soc, double* state, double* obs, uint8_t* converged, uint8_t* terminated,
                   int32_t* timestep, int32_t* nr_iters, double* full, int32_t* aux_index,
@@ -360,7 +378,10 @@ int anm_step_ws_record_doubles(void);
  *        library next to `state`; when given (and `full` is NULL) the thread-per-environment family
  *        uses its coalesced-row kernel: action / state / obs rows move through LDS as whole-wave
  *        512-byte transactions and the time index is not re-read from the state rows.  Must be the
- *        same buffer in anm_reset_f64 and anm_step_f64. */
+ *        same buffer in anm_reset_f64 and anm_step_f64.
+ *   ANM_IO_F32 (anm_model_set_io): `action` points at float [E, action_dim], `obs` at float [E, state_base_dim+K] (or
+ *        [E, n_obs] with a list set by anm_model_set_obs) and `reward` at float [E]; everything else is as above.  The
+ *        coalesced-row kernel then moves the action and obs rows as whole-wave 256-byte transactions. */
 int anm_step_f64(anm_model* m, int64_t num_envs, const double* action, const double* exo,
                  const double* aux_next, double* soc, double* state, uint8_t* terminated,
                  int32_t* timestep, double* obs, double* reward, double* e_loss, double* penalty,
@@ -484,7 +505,8 @@ int anm_model_full_layout(const anm_model* m, anm_full_layout* out);
 
 /* Timing helper for benchmarks: enqueue `n_launch` identical steps bracketed by HIP events on
  * `stream` and return the average milliseconds per step (synchronises).  With a workspace a step
- * is three kernel launches. */
+ * is three kernel launches.  ANM_IO_F32 (anm_model_set_io): `action`, `obs` and `reward` point at float arrays, as in
+ * anm_step_f64. */
 int anm_time_step_launches(anm_model* m, int64_t num_envs, const double* action, double* soc,
                            double* state, uint8_t* terminated, int32_t* timestep, double* obs,
                            double* reward, double* e_loss, double* penalty, int32_t autoreset,
