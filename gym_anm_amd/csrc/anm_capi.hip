@@ -172,7 +172,7 @@ __global__ void k_gather_obs(int64_t n, int full_dim, const double* __restrict__
 
 // ANM6Easy.init_state (anm6_easy.py:25-52) for any series-mode task, the draws alone: one thread per environment, table-driven
 // (tab[d] = type, slot, q_min, q_max, soc_min, soc_max of device d), the very expressions of the samplers inside the reset /
-// step kernels (sample_series_init_state, anm_radial.hpp, anm_mesh.hpp) -- tests/test_gpu_sampler.py holds them to it bit for
+// step kernels (sample_init_state, anm_lane_io.inc) -- tests/test_gpu_sampler.py holds them to it bit for
 // bit.  raw (nullable): the Philox words behind the row, blocks 0 .. n_blocks - 1 of key (seed, env_offset + e, epoch).
 __global__ void k_sample_init_state(int64_t n, int nd, int nload, int ngen, int ndes, const double* __restrict__ tab,
                                     const double* __restrict__ series, int period, uint64_t seed, uint64_t env_offset,
@@ -204,10 +204,7 @@ __global__ void k_sample_init_state(int64_t n, int nd, int nload, int ngen, int 
       s0[d] = exo_lo ? ExoUniform::draw(key, 0u, slot, exo_lo[slot], exo_lo[nexo + slot]) : series[slot * period + aux];
     } else if (typ == DEV_CLASSICAL || typ == DEV_RENEWABLE || typ == DEV_STORAGE) {
       const bool des = typ == DEV_STORAGE;
-      const int u = des ? ngen + slot : slot;
-      uint32_t q[4];
-      Philox::generate(seed, env_offset + uint64_t(e), epoch, 1u + u / 2, q);
-      const double uu = Philox::u01(q[2 * (u % 2)], q[2 * (u % 2) + 1]);
+      const double uu = Philox::unit_u01(seed, env_offset + uint64_t(e), epoch, des ? ngen + slot : slot);
       if (des) {
         s0[2 * nd + slot] = t[4] + (t[5] - t[4]) * uu;
       } else {
@@ -1029,6 +1026,26 @@ int anm_transition_f64(anm_model* m, int64_t n, const double* p_load, const doub
   });
 }
 
+// What a reset and a step take from the model alike: the task's exogenous mode and tables, the episode settings and the
+// I/O mode -- and what of these a bound batch view does not go with.  `who`: the entry point, for the error texts.
+static int env_io_of_model(const anm_model* m, const char* who, EnvIO& io) {
+  io = EnvIO{};
+  io.K = m->K;
+  io.exo_mode = m->exo_mode;
+  io.exo_lo = m->d_exo;
+  io.exo_hi = m->exo_mode == ANM_EXO_UNIFORM ? m->d_exo + (m->dims.n_load + m->dims.n_gen) : nullptr;
+  io.series = m->d_series;
+  io.period = m->period;
+  io.ep = m->ep;
+  io.io32 = m->io_mode == ANM_IO_F32 ? 1 : 0;
+  if (m->has_view) {
+    const std::string w(who);
+    if (io.io32) return fail((w + ": the float32 I/O mode (anm_model_set_io) does not go with a batch view (anm_model_bind_view)").c_str());
+    if (io.ep.on) return fail((w + ": an episode time limit or episode buffers do not go with a batch view (anm_model_bind_view)").c_str());
+  }
+  return 0;
+}
+
 int anm_reset_f64(anm_model* m, int64_t n, const double* init_state, const uint8_t* mask, uint64_t rng_seed,
                   uint64_t env_offset, int32_t* reset_count, double* soc, double* state,
                   double* obs, uint8_t* converged, uint8_t* terminated, int32_t* timestep, int32_t* nr_iters,
@@ -1042,14 +1059,9 @@ int anm_reset_f64(anm_model* m, int64_t n, const double* init_state, const uint8
     return fail("anm_reset_f64: drawing initial states on the device needs a series-mode or uniform-mode model and reset_count");
   if (uniform && (m->has_view || m->d_env_class))
     return fail("anm_reset_f64: the uniform exogenous mode goes with neither a batch view nor parameter classes");
-  EnvIO io{};
-  io.K = m->K;
-  io.exo_mode = m->exo_mode;
-  io.exo_lo = m->d_exo;
-  io.exo_hi = uniform ? m->d_exo + (m->dims.n_load + m->dims.n_gen) : nullptr;
+  EnvIO io;
+  if (int rc = env_io_of_model(m, "anm_reset_f64", io)) return rc;
   io.init_state = init_state;
-  io.series = m->d_series;
-  io.period = m->period;
   io.rng_seed = rng_seed;
   io.env_offset = env_offset;
   io.reset_count = reset_count;
@@ -1064,10 +1076,6 @@ int anm_reset_f64(anm_model* m, int64_t n, const double* init_state, const uint8
   io.full = full;
   io.aux_index = aux_index;
   io.nr_diff = m->d_nr_diff;
-  io.ep = m->ep;
-  io.io32 = m->io_mode == ANM_IO_F32 ? 1 : 0;
-  if (io.io32 && m->has_view) return fail("anm_reset_f64: the float32 I/O mode (anm_model_set_io) does not go with a batch view (anm_model_bind_view)");
-  if (io.ep.on && m->has_view) return fail("anm_reset_f64: an episode time limit or episode buffers do not go with a batch view (anm_model_bind_view)");
   int prec;
   SolverOpts so = solver(opts, prec);
   hipStream_t s = static_cast<hipStream_t>(stream);
@@ -1116,16 +1124,10 @@ static int make_step_io(anm_model* m, const double* action, const double* exo, c
   if (series && !uniform && m->period <= 0) return fail("anm_step_f64: no exo given and the model has no series (set_env)");
   if (!series && m->K > 0 && !aux_next) return fail("anm_step_f64: exo given without aux_next");
   if (autoreset && (!series || !reset_count)) return fail("anm_step_f64: autoreset needs series mode and reset_count");
-  io = EnvIO{};
-  io.K = m->K;
-  io.exo_mode = m->exo_mode;
-  io.exo_lo = m->d_exo;
-  io.exo_hi = uniform ? m->d_exo + (m->dims.n_load + m->dims.n_gen) : nullptr;
+  if (int rc = env_io_of_model(m, "anm_step_f64", io)) return rc;
   io.action = action;
   io.exo = exo;
   io.aux_next = aux_next;
-  io.series = m->d_series;
-  io.period = m->period;
   io.soc = soc;
   io.state = state;
   io.terminated = terminated;
@@ -1142,18 +1144,10 @@ static int make_step_io(anm_model* m, const double* action, const double* exo, c
   io.reset_count = reset_count;
   io.aux_index = aux_index;
   io.state_same = m->d_state_same;
-  io.ep = m->ep;
-  if (io.ep.on) {
-    if (m->has_view) return fail("anm_step_f64: an episode time limit or episode buffers do not go with a batch view (anm_model_bind_view)");
-    if (!timestep) return fail("anm_step_f64: an episode time limit or episode buffers need the timestep buffer");
-  }
-  io.io32 = m->io_mode == ANM_IO_F32 ? 1 : 0;
-  if (io.io32) {
-    if (m->has_view) return fail("anm_step_f64: the float32 I/O mode (anm_model_set_io) does not go with a batch view (anm_model_bind_view)");
-    if (full && m->n_obs == 0)
-      return fail("anm_step_f64: the float32 I/O mode (anm_model_set_io) has no unfused observation gather: `full` + anm_gather_obs_f64 "
-                  "writes float64 observations; set the list in the kernel (anm_model_set_obs) or leave `full` NULL");
-  }
+  if (io.ep.on && !timestep) return fail("anm_step_f64: an episode time limit or episode buffers need the timestep buffer");
+  if (io.io32 && full && m->n_obs == 0)
+    return fail("anm_step_f64: the float32 I/O mode (anm_model_set_io) has no unfused observation gather: `full` + anm_gather_obs_f64 "
+                "writes float64 observations; set the list in the kernel (anm_model_set_obs) or leave `full` NULL");
   io.n_obs = 0;
   io.state_magic = magic_div(m->dims.state_base_dim + m->K);
   if (m->t_thread.ok && m->impl == ANM_IMPL_THREAD && (m->n_obs > 0 || full)) {

@@ -57,6 +57,29 @@ struct Dims {
   static constexpr int SBASE = T::SDIM;  // 2 ND + NDES + NGEN
 };
 
+// In-wave hand-over of the solves still running to lane groups (anm_group.hpp), in two halves around the thread-mode
+// iterations.  The decision: the Newton iteration at which a solve in thread mode stops -- so.handoff for a tree topology
+// on the GPU that was given an LDS buffer for the hand-over slots, if 0 <= so.handoff < so.max_iter; so.max_iter ("never")
+// otherwise.
+template <class T>
+ANM_HD int handoff_cap(SolverOpts so, const double* lds) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  if constexpr (T::TREE != 0)
+    if (lds && so.handoff >= 0 && so.handoff < so.max_iter) return so.handoff;
+#endif
+  return so.max_iter;
+}
+// ... and the continuation, for a caller that stopped below so.max_iter.  Collective: every lane of the wavefront comes
+// here (hence no early return before it); the lanes beyond the batch or masked out (!valid) lend their hands and hand
+// nothing over.
+template <class T, class JT>
+ANM_HD void continue_handed_over(cptr_t C, EnvWork<T>& w, PFState<T>& st, bool valid, SolverOpts so, double* lds) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  if constexpr (T::TREE != 0)
+    if (ANM_WAVE_ANY(st.active && valid)) group::continue_in_groups<T, JT>(C, w, st, st.active && valid, so.tol, so.max_iter, lds);
+#endif
+}
+
 // state vector (anm_env.py:139-147): [dev_p MW, dev_q MVAr, des_soc MWh, gen_p_max MW, aux(K)]
 // `out`: where the state / observation entries go -- anything with put_st(k, v) / put_ob(k, v) (register
 // arrays: StepOut; rows in memory: RowPtrs; an LDS row: op_step_general).  Setters, not references: a
@@ -115,8 +138,8 @@ ANM_HD void op_transition(cptr_t C, const TransitionIO& io, SolverOpts so, int64
                           double* lds = nullptr) {
   // valid / lds (GPU): `slot` is clamped for the lanes beyond the batch (they compute along and store nothing), and a tree
   // topology hands the solves still running after so.handoff iterations over to lane groups inside the wavefront, like the
-  // step kernels (group::continue_in_groups, collective: hence no early return) -- 65 536 ANM6 transitions 242 -> ~100 us:
-  // the launch waits for its diverging solves, and a lane group's trip is a quarter of a thread's
+  // step kernels (handoff_cap / continue_handed_over) -- 65 536 ANM6 transitions 242 -> ~100 us: the launch waits for its
+  // diverging solves, and a lane group's trip is a quarter of a thread's
   const int64_t e = v.index ? int64_t(v.index[slot]) : slot;
   const int WL = v.w_load > 0 ? v.w_load : T::NLOAD, WG = v.w_gen > 0 ? v.w_gen : T::NGEN, WS = v.w_set > 0 ? v.w_set : T::NSET;
   const int WD = v.w_des > 0 ? v.w_des : T::NDES, WF = v.w_full > 0 ? v.w_full : FullState<T>::SIZE;
@@ -146,17 +169,9 @@ ANM_HD void op_transition(cptr_t C, const TransitionIO& io, SolverOpts so, int64
     transition_end<T>(C, w, st, so.tol);
   } else {
     PFState<T> st;
-    int cap = so.max_iter;
-#if defined(__HIP_DEVICE_COMPILE__)
-    if constexpr (T::TREE != 0)
-      if (lds && so.handoff >= 0 && so.handoff < so.max_iter) cap = so.handoff;
-#endif
+    const int cap = handoff_cap<T>(so, lds);
     transition_begin<T, JT>(C, C, w, st, P_load, P_pot, P_set, Q_set, so.tol, so.max_iter, cap);
-#if defined(__HIP_DEVICE_COMPILE__)
-    if constexpr (T::TREE != 0)
-      if (cap < so.max_iter && ANM_WAVE_ANY(st.active && valid))
-        group::continue_in_groups<T, JT>(C, w, st, st.active && valid, so.tol, so.max_iter, lds);
-#endif
+    if (cap < so.max_iter) continue_handed_over<T, JT>(C, w, st, valid, so, lds);
     transition_end<T>(C, w, st, so.tol);
   }
   if (!valid) return;
@@ -343,48 +358,6 @@ ANM_HD void finish_reset(cptr_t C, EnvWork<T>& w, const S0& s0, int K, double* s
   });
 }
 
-// ANM6Easy.init_state (anm6_easy.py:25-52) generalised to any series-mode task, drawn on the device:
-// time index uniform in [0, period), loads and generator potentials from the series at that index,
-// generator Q uniform in its p.u. range (stored in the MVAr slot, sic), storage SoC uniform in its
-// p.u. range (stored in the MWh slot, sic).  Counter-based: (seed, global env index, epoch).
-// SER: where the exogenous series are read from -- io.series (global memory; the default) or a copy in LDS
-template <class T, class SER = const double*>
-ANM_HD int sample_series_init_state(cptr_t C, const EnvIO& io, int64_t e, uint32_t epoch, double (&s0)[T::SDIM + 1], SER ser = nullptr) {
-  if constexpr (std::is_same<SER, const double*>::value) { if (!ser) ser = io.series; }
-  typedef Layout<T> L;
-  uint32_t r[4];
-  Philox::generate(io.rng_seed, io.env_offset + uint64_t(e), epoch, 0u, r);
-  const int aux = int((uint64_t(r[0]) * uint64_t(io.period)) >> 32);
-  static_for<0, T::SDIM>([&](auto I) { s0[I] = 0.0; });
-  s0[T::SDIM] = double(aux);
-  static_for<0, T::ND>([&](auto Di) {
-    constexpr int d = Di;
-    constexpr int typ = T::DEV_TYPE[d];
-    if constexpr (typ == DEV_LOAD) {
-      s0[d] = ser[T::DEV_SLOT[d] * io.period + aux];
-    } else if constexpr (typ == DEV_CLASSICAL || typ == DEV_RENEWABLE) {
-      constexpr int g = T::DEV_SLOT[d];
-      constexpr int u = g;  // uniform index
-      cptr_t sd = C + L::SETDEV + SD_SIZE * T::DEV_SET[d];
-      uint32_t q[4];
-      Philox::generate(io.rng_seed, io.env_offset + uint64_t(e), epoch, 1u + u / 2, q);
-      const double uu = Philox::u01(q[2 * (u % 2)], q[2 * (u % 2) + 1]);
-      const double pm = ser[(T::NLOAD + g) * io.period + aux];
-      s0[d] = pm;
-      s0[2 * T::ND + T::NDES + g] = pm;
-      s0[T::ND + d] = sd[SD_QMIN] + (sd[SD_QMAX] - sd[SD_QMIN]) * uu;
-    } else if constexpr (typ == DEV_STORAGE) {
-      constexpr int u = T::NGEN + T::DEV_SLOT[d];
-      cptr_t sd = C + L::SETDEV + SD_SIZE * T::DEV_SET[d];
-      uint32_t q[4];
-      Philox::generate(io.rng_seed, io.env_offset + uint64_t(e), epoch, 1u + u / 2, q);
-      const double uu = Philox::u01(q[2 * (u % 2)], q[2 * (u % 2) + 1]);
-      s0[2 * T::ND + T::DEV_SLOT[d]] = sd[SD_SOC_MIN] + (sd[SD_SOC_MAX] - sd[SD_SOC_MIN]) * uu;
-    }
-  });
-  return aux;
-}
-
 // Uniform exogenous mode: the loads and generator potentials of step t of the episode with key `key` (ExoUniform)
 template <class T>
 ANM_HD void exo_uniform_draws(const EnvIO& io, uint64_t key, uint32_t t, double (&x)[Dims<T>::NEXO > 0 ? Dims<T>::NEXO : 1]) {
@@ -399,41 +372,61 @@ ANM_HD void exo_uniform_draws(const EnvIO& io, uint64_t key, uint32_t t, double 
   });
 }
 
-// Initial state of the uniform exogenous mode (rng.py: uniform_init_state): step index 0, loads and generator P / P_max
-// from the step stream at index 0, generator Q and storage SoC like sample_series_init_state (same blocks, same quirks);
-// block 0 of the init sampler is not used.
-template <class T>
-ANM_HD int sample_uniform_init_state(cptr_t C, const EnvIO& io, int64_t e, uint32_t epoch, double (&s0)[T::SDIM + 1]) {
+// ANM6Easy.init_state (anm6_easy.py:25-52) generalised to any series-mode task, drawn on the device:
+// time index uniform in [0, period), loads and generator potentials from the series at that index,
+// generator Q uniform in its p.u. range (stored in the MVAr slot, sic), storage SoC uniform in its
+// p.u. range (stored in the MWh slot, sic).  Counter-based: (seed, global env index, epoch); block 0 holds the time
+// index, unit u of the generators and storage units its own uniform (Philox::unit_u01).
+// UNI: the initial state of the uniform exogenous mode instead (rng.py: uniform_init_state) -- step index 0, loads and
+// generator P / P_max from the step stream at index 0, generator Q and storage SoC as above (same blocks, same quirks);
+// block 0 is not used.
+// SER: where the exogenous series are read from -- io.series (global memory; the default) or a copy in LDS
+template <class T, bool UNI = false, class SER = const double*>
+ANM_HD int sample_init_state(cptr_t C, const EnvIO& io, int64_t e, uint32_t epoch, double (&s0)[T::SDIM + 1], SER ser = nullptr) {
   typedef Layout<T> L;
   const uint64_t env = io.env_offset + uint64_t(e);
-  double x[Dims<T>::NEXO > 0 ? Dims<T>::NEXO : 1];
-  exo_uniform_draws<T>(io, ExoUniform::episode_key(io.rng_seed, env, epoch), 0u, x);
-  static_for<0, T::SDIM + 1>([&](auto I) { s0[I] = 0.0; });
+  int aux = 0;
+  double x[Dims<T>::NEXO > 0 ? Dims<T>::NEXO : 1];   // UNI: the draws of step 0
+  if constexpr (UNI) {
+    exo_uniform_draws<T>(io, ExoUniform::episode_key(io.rng_seed, env, epoch), 0u, x);
+  } else {
+    if constexpr (std::is_same<SER, const double*>::value) { if (!ser) ser = io.series; }
+    uint32_t r[4];
+    Philox::generate(io.rng_seed, env, epoch, 0u, r);
+    aux = int((uint64_t(r[0]) * uint64_t(io.period)) >> 32);
+  }
+  auto exo = [&](auto I) {   // load or generator potential I of the drawn state, MW
+    if constexpr (UNI) return x[I];
+    else return ser[I * io.period + aux];
+  };
+  static_for<0, T::SDIM>([&](auto I) { s0[I] = 0.0; });
+  s0[T::SDIM] = double(aux);
   static_for<0, T::ND>([&](auto Di) {
     constexpr int d = Di;
     constexpr int typ = T::DEV_TYPE[d];
     if constexpr (typ == DEV_LOAD) {
-      s0[d] = x[T::DEV_SLOT[d]];
+      s0[d] = exo(std::integral_constant<int, T::DEV_SLOT[d]>{});
     } else if constexpr (typ == DEV_CLASSICAL || typ == DEV_RENEWABLE) {
       constexpr int g = T::DEV_SLOT[d];
-      constexpr int u = g;
       cptr_t sd = C + L::SETDEV + SD_SIZE * T::DEV_SET[d];
-      uint32_t q[4];
-      Philox::generate(io.rng_seed, env, epoch, 1u + u / 2, q);
-      const double uu = Philox::u01(q[2 * (u % 2)], q[2 * (u % 2) + 1]);
-      s0[d] = x[T::NLOAD + g];
-      s0[2 * T::ND + T::NDES + g] = x[T::NLOAD + g];
+      const double uu = Philox::unit_u01(io.rng_seed, env, epoch, g);
+      const double pm = exo(std::integral_constant<int, T::NLOAD + g>{});
+      s0[d] = pm;
+      s0[2 * T::ND + T::NDES + g] = pm;
       s0[T::ND + d] = sd[SD_QMIN] + (sd[SD_QMAX] - sd[SD_QMIN]) * uu;
     } else if constexpr (typ == DEV_STORAGE) {
-      constexpr int u = T::NGEN + T::DEV_SLOT[d];
       cptr_t sd = C + L::SETDEV + SD_SIZE * T::DEV_SET[d];
-      uint32_t q[4];
-      Philox::generate(io.rng_seed, env, epoch, 1u + u / 2, q);
-      const double uu = Philox::u01(q[2 * (u % 2)], q[2 * (u % 2) + 1]);
+      const double uu = Philox::unit_u01(io.rng_seed, env, epoch, T::NGEN + T::DEV_SLOT[d]);
       s0[2 * T::ND + T::DEV_SLOT[d]] = sd[SD_SOC_MIN] + (sd[SD_SOC_MAX] - sd[SD_SOC_MIN]) * uu;
     }
   });
-  return 0;
+  return aux;
+}
+
+// (the series-mode sampler under the name the host test double calls it by: tests/hostsim/hostsim.cpp)
+template <class T>
+ANM_HD int sample_series_init_state(cptr_t C, const EnvIO& io, int64_t e, uint32_t epoch, double (&s0)[T::SDIM + 1]) {
+  return sample_init_state<T>(C, io, e, epoch, s0);
 }
 
 template <class T, class JT, class S0>
@@ -447,19 +440,11 @@ ANM_HD void reset_from(cptr_t C, const EnvIO& io, SolverOpts so, int64_t e, cons
   inputs_from_init_state<T>(C, s0, w, P_load, P_pot, P_set, Q_set);
   {
     PFState<T> st;
-    int cap = so.max_iter;
-#if defined(__HIP_DEVICE_COMPILE__)
-    if constexpr (T::TREE != 0)
-      if (lds && so.handoff >= 0 && so.handoff < so.max_iter) cap = so.handoff;
-#endif
+    const int cap = handoff_cap<T>(so, lds);
     // (a lane that stores nothing -- masked out of a partial reset, or beyond the batch -- evaluates F once and iterates
     // no further: a redraw round of ANMEnv.reset must not wait for 63 solves nobody asked for)
     transition_begin<T, JT>(C, C, w, st, P_load, P_pot, P_set, Q_set, so.tol, so.max_iter, act ? cap : 0);
-#if defined(__HIP_DEVICE_COMPILE__)
-    if constexpr (T::TREE != 0)
-      if (cap < so.max_iter && ANM_WAVE_ANY(st.active && act))
-        group::continue_in_groups<T, JT>(C, w, st, st.active && act, so.tol, so.max_iter, lds);
-#endif
+    if (cap < so.max_iter) continue_handed_over<T, JT>(C, w, st, act, so, lds);
     transition_end<T>(C, w, st, so.tol);
   }
   if (!act) return;
@@ -485,8 +470,8 @@ ANM_HD void op_reset(cptr_t C, const EnvIO& io, SolverOpts so, int64_t slot, con
     reset_from<T, JT>(C, io, so, e, io.init_state + e * (v.w_state > 0 ? v.w_state : T::SDIM + io.K), v, act, lds);
   } else {              // device sampler (series or uniform mode, K = 1): same draws as the autoreset path, kept in registers
     double s0_drawn[T::SDIM + 1];
-    if (io.exo_mode) sample_uniform_init_state<T>(C, io, e, uint32_t(io.reset_count[e]), s0_drawn);
-    else sample_series_init_state<T>(C, io, e, uint32_t(io.reset_count[e]), s0_drawn);
+    if (io.exo_mode) sample_init_state<T, true>(C, io, e, uint32_t(io.reset_count[e]), s0_drawn);
+    else sample_init_state<T>(C, io, e, uint32_t(io.reset_count[e]), s0_drawn);
     if (act) io.reset_count[e] += 1;
     reset_from<T, JT>(C, io, so, e, s0_drawn, v, act, lds);
   }
@@ -561,8 +546,8 @@ ANM_HD void step_begin(cptr_t C, CD Cd, const EnvIO& io, SolverOpts so, int64_t 
   int aux = 0;
   if (ctx.resetting) {
     double s0[T::SDIM + 1];  // sampled initial state (K == 1 in series mode)
-    if (UNI && io.exo_mode) aux = sample_uniform_init_state<T>(C, io, e, uint32_t(in.reset_count), s0);
-    else aux = sample_series_init_state<T>(C, io, e, uint32_t(in.reset_count), s0, ser);
+    if (UNI && io.exo_mode) aux = sample_init_state<T, true>(C, io, e, uint32_t(in.reset_count), s0);
+    else aux = sample_init_state<T, false>(C, io, e, uint32_t(in.reset_count), s0, ser);
     static_for<0, T::NDES>([&](auto I) { ctx.soc_req[I] = s0[2 * T::ND + I]; });
     inputs_from_init_state<T>(C, s0, w, P_load, P_pot, P_set, Q_set);
   } else {
@@ -701,16 +686,17 @@ ANM_HD void step_compute(cptr_t C, const EnvIO& io, SolverOpts so, int64_t e, co
 // EP: the caller serves the episode time limit and statistics (io.ep, a wave-uniform runtime switch); off, they are not in
 // the code at all (the fast path of the step keeps its instruction stream: k_step_rows / k_step_rows_ep)
 // IOM: the float32 I/O of the reward (IO_F64 | IO_F32 | IO_RT); the statistics above accumulate the double either way
+// have_ts: the caller already read timestep[e]; w_des: row stride of soc (a batch view pads the rows)
 template <class T, int KCAP, bool EP = false, int IOM = IO_F64>
-ANM_HD void store_step_scalars(const EnvIO& io, int64_t e, const StepFlags<T>& o, bool have_ts = false,
-                               int32_t ts_prev = 0) {  // have_ts: the caller already read timestep[e]
+ANM_HD void store_step_scalars(const EnvIO& io, int64_t e, const StepFlags<T>& o, bool have_ts = false, int32_t ts_prev = 0,
+                               int w_des = T::NDES) {
   if constexpr (EP) {
     if (io.ep.on) {   // (needs timestep: the C ABI refuses the feature without it)
       if (o.timestep_op == 1) episode_clear(io.ep, e);
       else if (o.timestep_op == 2) episode_step(io.ep, e, o.reward, o.terminated == 1, (have_ts ? ts_prev : io.timestep[e]) + 1);
     }
   }
-  if (o.write_soc) static_for<0, T::NDES>([&](auto I) { io.soc[e * T::NDES + I] = o.soc[I]; });
+  if (o.write_soc) static_for<0, T::NDES>([&](auto I) { io.soc[e * w_des + I] = o.soc[I]; });
   if (o.terminated >= 0) io.terminated[e] = uint8_t(o.terminated);
   if constexpr (IOM == IO_F64) io.reward[e] = o.reward;
   else io_store(io.reward, e, o.reward, IOM == IO_F32 || io.io32 != 0);
@@ -724,6 +710,18 @@ ANM_HD void store_step_scalars(const EnvIO& io, int64_t e, const StepFlags<T>& o
     else if (o.timestep_op == 2) io.timestep[e] = (have_ts ? ts_prev : io.timestep[e]) + 1;
   }
   if (o.inc_reset) io.reset_count[e] += 1;
+}
+
+// the state / obs rows of one environment, stored by its own lane (layers 1 and 1b); width: the entries of a row
+template <class T, int KCAP>
+ANM_HD void store_step_rows(const StepOut<T, KCAP>& out, double* state, double* obs, int width) {
+  static_for<0, T::SDIM + KCAP>([&](auto Kc) {
+    constexpr int k = Kc;
+    if (k < width) {
+      if (out.write_state) state[k] = out.state[k];
+      if (out.write_obs) obs[k] = out.obs[k];
+    }
+  });
 }
 
 // I/O layer 1: plain per-environment loads and stores (host test double, generic mode, `full` dumps)
@@ -742,15 +740,7 @@ ANM_HD void op_step(cptr_t C, const EnvIO& io, SolverOpts so, int64_t e) {
   in.aux_prev = io.exo ? 0.0 : io.state[e * S + T::SDIM];
   in.reset_count = (io.autoreset && io.reset_count) ? io.reset_count[e] : 0;
   step_compute<T, JT, Layout<T>::KMAX>(C, io, so, e, in, out, w);
-  double* state = io.state + e * S;
-  double* obs = io.obs + e * S;
-  static_for<0, T::SDIM + Layout<T>::KMAX>([&](auto Kc) {
-    constexpr int k = Kc;
-    if (k < S) {
-      if (out.write_state) state[k] = out.state[k];
-      if (out.write_obs) obs[k] = out.obs[k];
-    }
-  });
+  store_step_rows<T>(out, io.state + e * S, io.obs + e * S, S);
   store_step_scalars<T, Layout<T>::KMAX, true>(io, e, out);
   if (io.full && out.write_state) write_full_state<T>(w, io.full + e * FullState<T>::SIZE);
   ANM_PHASE(6);
@@ -881,7 +871,6 @@ __device__ __forceinline__ void epilogue_stores(const EnvIO& io, int64_t e0, int
 template <class T, class JT>
 __device__ void op_step_view(cptr_t C, const EnvIO& io, SolverOpts so, int64_t n, const View& v, double* lds) {
   typedef Dims<T> D;
-  constexpr int S1 = T::SDIM + 1;
   const int lane = threadIdx.x;
   const int64_t slot = int64_t(blockIdx.x) * 64 + lane;
   const bool valid = slot < n;
@@ -904,39 +893,13 @@ __device__ void op_step_view(cptr_t C, const EnvIO& io, SolverOpts so, int64_t n
   const int32_t ts_prev = io.timestep ? io.timestep[e] : 0;
 
   step_begin<T, JT>(C, C, io, so, e, in, ctx, w, st, -1);
-  constexpr bool CAN_GROUP = T::TREE != 0;
-  const int handoff = (CAN_GROUP && so.handoff >= 0 && so.handoff < so.max_iter) ? so.handoff : -1;
-  pf_iterate<T, JT>(C, w, st, so.tol, so.max_iter, handoff >= 0 ? handoff : so.max_iter);
-  if constexpr (CAN_GROUP) {
-    if (handoff >= 0 && ANM_WAVE_ANY(st.active && valid))
-      group::continue_in_groups<T, JT>(C, w, st, st.active && valid, so.tol, so.max_iter, lds);
-  }
+  const int cap = handoff_cap<T>(so, lds);
+  pf_iterate<T, JT>(C, w, st, so.tol, so.max_iter, cap);
+  if (cap < so.max_iter) continue_handed_over<T, JT>(C, w, st, valid, so, lds);
   step_end<T, 1>(C, io, so, e, ctx, w, st, out);
   if (!valid) return;
-  // stores (store_step_scalars with the view's strides)
-  if (out.write_soc) static_for<0, T::NDES>([&](auto I) { io.soc[e * WD + I] = out.soc[I]; });
-  if (out.terminated >= 0) io.terminated[e] = uint8_t(out.terminated);
-  io.reward[e] = out.reward;
-  if (out.write_costs) {
-    io.e_loss[e] = out.e_loss;
-    io.penalty[e] = out.penalty;
-  }
-  if (io.nr_iters) io.nr_iters[e] = out.n_iter;
-  if (io.timestep) {
-    if (out.timestep_op == 1) io.timestep[e] = 0;
-    else if (out.timestep_op == 2) io.timestep[e] = ts_prev + 1;
-  }
-  if (out.inc_reset) io.reset_count[e] += 1;
-  const int SK = T::SDIM + io.K;   // (K <= 1)
-  double* state = io.state + e * WS;
-  double* obs = io.obs + e * WS;
-  static_for<0, S1>([&](auto Kc) {
-    constexpr int k = Kc;
-    if (k < SK) {
-      if (out.write_state) state[k] = out.state[k];
-      if (out.write_obs) obs[k] = out.obs[k];
-    }
-  });
+  store_step_scalars<T, 1, false, IO_F64>(io, e, out, true, ts_prev, WD);
+  store_step_rows<T>(out, io.state + e * WS, io.obs + e * WS, T::SDIM + io.K);   // (K <= 1)
   if (io.full && out.write_state) write_full_state<T>(w, io.full + e * WF);
 }
 
@@ -990,6 +953,7 @@ __device__ void op_step_rows(cptr_t C, const EnvIO& io, SolverOpts so, int64_t n
   if constexpr (EP) in.was_term = in.was_term || (io.autoreset && episode_timed_out(io.ep, ts_prev));
 
   // ---- coalesced loads: 64 x ADIM doubles (IO32: floats) of actions
+  // (written out here and in op_step_general: as a function shared by the two, k_step_rows* lose their instruction stream)
   {
     typedef std::conditional_t<IO32, float, double> AT;
     const AT* g = reinterpret_cast<const AT*>(io.action) + e0 * D::ADIM;
@@ -1060,6 +1024,7 @@ __device__ void op_step_rows(cptr_t C, const EnvIO& io, SolverOpts so, int64_t n
     if (overflow_to_groups || !ANM_WAVE_ANY(st.active)) break;  // else: record space exhausted (or a padding lane)
   }
   if constexpr (CAN_GROUP) {
+    // (continue_handed_over, written out: through the function k_step_rows* lose their instruction stream)
     if ((handoff >= 0 || overflow_to_groups) && ANM_WAVE_ANY(st.active && valid))
       group::continue_in_groups<T, JT>(C, w, st, st.active && valid, so.tol, so.max_iter, lds);
   }
@@ -1154,6 +1119,8 @@ __device__ void op_step_general(cptr_t C, const EnvIO& io, SolverOpts so, int64_
   if (io.ep.on) in.was_term = in.was_term || (io.autoreset && episode_timed_out(io.ep, ts_prev));
 
   step_begin<T, JT, cptr_t, const double*, true>(C, C, io, so, ec, in, ctx, w, st, -1);
+  // (handoff_cap / continue_handed_over, written out: through the functions the 30-bus k_step_general<float> takes 16 bytes
+  // of scratch more)
   constexpr bool CAN_GROUP = T::TREE != 0;
   const int handoff = (CAN_GROUP && so.handoff >= 0 && so.handoff < so.max_iter) ? so.handoff : -1;
   pf_iterate<T, JT>(C, w, st, so.tol, so.max_iter, handoff >= 0 ? handoff : so.max_iter);

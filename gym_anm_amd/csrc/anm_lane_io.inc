@@ -81,17 +81,11 @@
       cptr_t sd = C + d.off_dev + l * SD_SIZE;
       if (typ == DEV_LOAD) s0_p = uni ? drawn : io.e.series[slot * io.e.period + aux];
       else if (typ == DEV_CLASSICAL || typ == DEV_RENEWABLE) {
-        const int u = slot;
-        uint32_t qd[4];
-        Philox::generate(io.e.rng_seed, io.e.env_offset + uint64_t(ee), epoch, 1u + u / 2, qd);
-        const double uu = Philox::u01_of(qd, u);
+        const double uu = Philox::unit_u01(io.e.rng_seed, io.e.env_offset + uint64_t(ee), epoch, slot);
         s0_p = s0_pm = uni ? drawn : io.e.series[(d.NLOAD + slot) * io.e.period + aux];
         s0_q = sd[SD_QMIN] + (sd[SD_QMAX] - sd[SD_QMIN]) * uu;
       } else if (typ == DEV_STORAGE) {
-        const int u = d.NGEN + slot;
-        uint32_t qd[4];
-        Philox::generate(io.e.rng_seed, io.e.env_offset + uint64_t(ee), epoch, 1u + u / 2, qd);
-        const double uu = Philox::u01_of(qd, u);
+        const double uu = Philox::unit_u01(io.e.rng_seed, io.e.env_offset + uint64_t(ee), epoch, d.NGEN + slot);
         soc_req = sd[SD_SOC_MIN] + (sd[SD_SOC_MAX] - sd[SD_SOC_MIN]) * uu;
       }
     }
