@@ -54,7 +54,7 @@ class EnvConfig(C.Structure):
     ]  # fmt: skip
 
 
-ENV_TAIL_NONE, ENV_TAIL_EPISODE = 0, 1   # anm_env_config.tail
+ENV_TAIL_NONE, ENV_TAIL_EPISODE, ENV_TAIL_NOISE = 0, 1, 2   # anm_env_config.tail
 
 
 class EnvConfigEpisode(EnvConfig):
@@ -65,6 +65,15 @@ class EnvConfigEpisode(EnvConfig):
     def __init__(self, *a, **kw):
         super().__init__(*a, **kw)
         C.c_int32.from_address(C.addressof(self) + EnvConfig.K.offset + 4).value = ENV_TAIL_EPISODE
+
+
+class EnvConfigNoise(EnvConfigEpisode):
+    """anm_env_config up to exo_noise (tail = ANM_ENV_TAIL_NOISE): the amplitude table of the series-noise mode."""
+    _fields_ = [("exo_noise", c_double_p)]
+
+    def __init__(self, *a, **kw):
+        super().__init__(*a, **kw)
+        C.c_int32.from_address(C.addressof(self) + EnvConfig.K.offset + 4).value = ENV_TAIL_NOISE
 
 
 class StepWs(C.Structure):
@@ -99,7 +108,7 @@ class FullLayout(C.Structure):
 
 
 SOLVE_F64, SOLVE_F32 = 0, 1
-EXO_HOST, EXO_UNIFORM = 0, 1   # anm_env_config.exo_mode
+EXO_HOST, EXO_UNIFORM, EXO_SERIES_NOISE = 0, 1, 2   # anm_env_config.exo_mode
 IO_F64, IO_F32 = 0, 1   # anm_model_set_io
 IMPL_THREAD, IMPL_RADIAL, IMPL_MESH = 0, 1, 2
 HANDOFF_NEVER, HANDOFF_AUTO = -1, -2

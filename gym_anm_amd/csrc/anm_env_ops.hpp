@@ -289,6 +289,9 @@ struct EnvIO {
   int exo_mode;
   const double* exo_lo;     // [NEXO] MW (device)
   const double* exo_hi;     // [NEXO] MW (device)
+  // noisy time series (exo_mode 2): `series` and `period` as in series mode, the aux variable is the table index, the
+  // draws are keyed by the step index of the episode (`timestep`, mandatory) and clipped to [exo_lo, exo_hi] (ExoNoise)
+  const double* exo_noise;  // [NEXO, period] MW amplitudes (device)
   EpisodeIO ep;             // episode time limit and statistics (all zero: off)
   int io32;                 // float32 policy-facing I/O (anm_model_set_io; 0 = off): action, obs and reward point at floats
 };
@@ -358,17 +361,26 @@ ANM_HD void finish_reset(cptr_t C, EnvWork<T>& w, const S0& s0, int K, double* s
   });
 }
 
-// Uniform exogenous mode: the loads and generator potentials of step t of the episode with key `key` (ExoUniform)
+// The in-kernel drawing modes: the loads and generator potentials of step index t of the episode with key `key` -- uniform
+// over [exo_lo, exo_hi] (ExoUniform), or, `noisy`, the series at table index aux plus bounded noise, clipped (ExoNoise).  One
+// function for both: the Philox blocks are the bulk of the code, the mode (wave-uniform) only chooses the map
 template <class T>
-ANM_HD void exo_uniform_draws(const EnvIO& io, uint64_t key, uint32_t t, double (&x)[Dims<T>::NEXO > 0 ? Dims<T>::NEXO : 1]) {
+ANM_HD void exo_draws(const EnvIO& io, bool noisy, uint64_t key, uint32_t t, int aux, double (&x)[Dims<T>::NEXO > 0 ? Dims<T>::NEXO : 1]) {
   constexpr int NEXO = Dims<T>::NEXO;
   static_for<0, (NEXO + 1) / 2>([&](auto J) {
     constexpr int j = J;
     uint32_t q[4];
     ExoUniform::block(key, t, uint32_t(j), q);
-    x[2 * j] = ExoUniform::map(io.exo_lo[2 * j], io.exo_hi[2 * j], Philox::u01(q[0], q[1]));
-    if constexpr (2 * j + 1 < NEXO)
-      x[2 * j + 1] = ExoUniform::map(io.exo_lo[2 * j + 1], io.exo_hi[2 * j + 1], Philox::u01(q[2], q[3]));
+    static_for<0, 2>([&](auto H) {
+      constexpr int i = 2 * j + H;
+      if constexpr (i < NEXO) {
+        if (noisy)
+          x[i] = ExoNoise::map(io.exo_noise[i * io.period + aux], ExoNoise::factor(q, i), io.series[i * io.period + aux],
+                               io.exo_lo[i], io.exo_hi[i]);
+        else
+          x[i] = ExoUniform::map(io.exo_lo[i], io.exo_hi[i], Philox::u01_of(q, i));
+      }
+    });
   });
 }
 
@@ -379,7 +391,9 @@ ANM_HD void exo_uniform_draws(const EnvIO& io, uint64_t key, uint32_t t, double 
 // index, unit u of the generators and storage units its own uniform (Philox::unit_u01).
 // UNI: the initial state of the uniform exogenous mode instead (rng.py: uniform_init_state) -- step index 0, loads and
 // generator P / P_max from the step stream at index 0, generator Q and storage SoC as above (same blocks, same quirks);
-// block 0 is not used.
+// block 0 is not used.  Or, io.exo_mode == 2 (a wave-uniform run-time branch inside that instantiation), of the noisy
+// time series (rng.py: series_noise_init_state): the time index from block 0 as in series mode, loads and generator
+// P / P_max by ExoNoise at that index and step index 0.
 // SER: where the exogenous series are read from -- io.series (global memory; the default) or a copy in LDS
 template <class T, bool UNI = false, class SER = const double*>
 ANM_HD int sample_init_state(cptr_t C, const EnvIO& io, int64_t e, uint32_t epoch, double (&s0)[T::SDIM + 1], SER ser = nullptr) {
@@ -387,14 +401,16 @@ ANM_HD int sample_init_state(cptr_t C, const EnvIO& io, int64_t e, uint32_t epoc
   const uint64_t env = io.env_offset + uint64_t(e);
   int aux = 0;
   double x[Dims<T>::NEXO > 0 ? Dims<T>::NEXO : 1];   // UNI: the draws of step 0
-  if constexpr (UNI) {
-    exo_uniform_draws<T>(io, ExoUniform::episode_key(io.rng_seed, env, epoch), 0u, x);
-  } else {
+  bool noisy = false;   // UNI serves both in-kernel modes: io.exo_mode (wave-uniform) says which
+  if constexpr (UNI) noisy = io.exo_mode == 2;
+  if (!UNI || noisy) {   // (uniform mode: the aux variable is the step index, 0, and block 0 is not used)
     if constexpr (std::is_same<SER, const double*>::value) { if (!ser) ser = io.series; }
     uint32_t r[4];
     Philox::generate(io.rng_seed, env, epoch, 0u, r);
     aux = int((uint64_t(r[0]) * uint64_t(io.period)) >> 32);
   }
+  // the units at step index 0 (noisy time series: at the table index just drawn)
+  if constexpr (UNI) exo_draws<T>(io, noisy, ExoUniform::episode_key(io.rng_seed, env, epoch), 0u, aux, x);
   auto exo = [&](auto I) {   // load or generator potential I of the drawn state, MW
     if constexpr (UNI) return x[I];
     else return ser[I * io.period + aux];
@@ -491,6 +507,7 @@ struct StepIn {
   double aux_prev;                                       // series mode: time index before the step
   int aux_next = -1;                                     // ... or, >= 0, the next one, already formed (integer callers)
   int reset_count;
+  int step_index = 0;                                    // noisy time series: timestep before the step (keys the draws)
 };
 
 // what a step decides besides the state / observation rows
@@ -526,7 +543,7 @@ struct StepCtx {
 };
 
 // first half of a step: inputs -> device maps, bus sums, up to `iter_cap` Newton iterations
-// UNI: the caller serves the uniform exogenous mode (io.exo_mode, a wave-uniform runtime branch); off, the mode is not in the
+// UNI: the caller serves the in-kernel drawing modes -- uniform and noisy time series (io.exo_mode, a wave-uniform runtime branch); off, the mode is not in the
 // code at all -- the coalesced-row kernels keep their instruction stream
 template <class T, class JT, class CD, class SER = const double*, bool UNI = false>
 ANM_HD void step_begin(cptr_t C, CD Cd, const EnvIO& io, SolverOpts so, int64_t e, const StepIn<T>& in, StepCtx<T>& ctx,
@@ -552,12 +569,19 @@ ANM_HD void step_begin(cptr_t C, CD Cd, const EnvIO& io, SolverOpts so, int64_t 
     inputs_from_init_state<T>(C, s0, w, P_load, P_pot, P_set, Q_set);
   } else {
     // 1. exogenous variables (next_vars, anm6_easy.py:54-65 in series mode)
-    if (UNI && io.exo_mode) {   // the step index of the episode; the draws of a step are keyed by the NEW index
-      aux = int(in.aux_prev) + 1;
+    if (UNI && io.exo_mode) {   // the draws of a step are keyed by the NEW step index of the episode
+      const bool noisy = io.exo_mode == 2;
+      uint32_t step;
+      if (noisy) {   // the aux variable is the table index, as in series mode; the step index is timestep + 1
+        aux = int(fmod(in.aux_prev + 1.0, double(io.period)));
+        step = uint32_t(in.step_index) + 1u;
+      } else {       // the aux variable is that step index
+        aux = int(in.aux_prev) + 1;
+        step = uint32_t(aux);
+      }
       double x[Dims<T>::NEXO > 0 ? Dims<T>::NEXO : 1];
       // (the episode began at epoch reset_count - 1: every reset leaves the count one above the epoch it drew with)
-      exo_uniform_draws<T>(io, ExoUniform::episode_key(io.rng_seed, io.env_offset + uint64_t(e), uint32_t(in.reset_count) - 1u),
-                           uint32_t(aux), x);
+      exo_draws<T>(io, noisy, ExoUniform::episode_key(io.rng_seed, io.env_offset + uint64_t(e), uint32_t(in.reset_count) - 1u), step, aux, x);
       static_for<0, T::NLOAD>([&](auto I) { P_load[I] = x[I]; });
       static_for<0, T::NGEN>([&](auto I) { P_pot[I] = x[T::NLOAD + I]; });
     } else if (series) {
@@ -1116,6 +1140,7 @@ __device__ void op_step_general(cptr_t C, const EnvIO& io, SolverOpts so, int64_
   // (uniform mode: the reset epoch is part of the key of every step's draws, autoreset or not)
   in.reset_count = ((io.autoreset || io.exo_mode) && io.reset_count) ? io.reset_count[ec] : 0;
   const int32_t ts_prev = io.timestep ? io.timestep[ec] : 0;
+  in.step_index = ts_prev;
   if (io.ep.on) in.was_term = in.was_term || (io.autoreset && episode_timed_out(io.ep, ts_prev));
 
   step_begin<T, JT, cptr_t, const double*, true>(C, C, io, so, ec, in, ctx, w, st, -1);

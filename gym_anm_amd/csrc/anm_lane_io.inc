@@ -56,12 +56,22 @@
     sampled = resetting && !(mode == 1 && io.e.init_state);
     // uniform exogenous mode (io.e.exo_mode, wave-uniform): every load / generator lane draws its own unit from the step
     // stream of its environment's episode -- the episode key plus one block (ExoUniform, anm_device.hpp)
-    const bool uni = io.e.exo_mode != 0;
+    // noisy time series (the third value of io.e.exo_mode): the table index moves as in series mode, the draws are keyed by
+    // the step index of the episode (io.e.timestep) and shaped by the two table entries at the NEW index (ExoNoise)
+    const bool uni = io.e.exo_mode == 1;
+    const bool noisy = io.e.exo_mode == 2;
     const bool exo_unit = typ == DEV_LOAD || typ == DEV_CLASSICAL || typ == DEV_RENEWABLE;
-    auto exo_draw = [&](uint32_t epoch, uint32_t step) {
+    // (one site draws for both modes -- the Philox blocks are the bulk of the code -- and the mode only chooses the map;
+    // `at`: the table index of the noisy series)
+    auto exo_draw = [&](uint32_t epoch, uint32_t step, int at) {
       const int unit = typ == DEV_LOAD ? slot : d.NLOAD + slot;
       const uint64_t key = ExoUniform::episode_key(io.e.rng_seed, io.e.env_offset + uint64_t(ee), epoch);
-      return ExoUniform::draw(key, step, unit, io.e.exo_lo[unit], io.e.exo_hi[unit]);
+      uint32_t q[4];
+      ExoUniform::block(key, step, uint32_t(unit) >> 1, q);
+      if (noisy)
+        return ExoNoise::map(io.e.exo_noise[unit * io.e.period + at], ExoNoise::factor(q, unit), io.e.series[unit * io.e.period + at],
+                             io.e.exo_lo[unit], io.e.exo_hi[unit]);
+      return ExoUniform::map(io.e.exo_lo[unit], io.e.exo_hi[unit], Philox::u01_of(q, unit));
     };
     if (mode == 1 && io.e.init_state) {
       const double* s0 = io.e.init_state + ee * W_ST;
@@ -71,18 +81,19 @@
     } else if (resetting) {  // autoreset: ANM6Easy.init_state with the counter-based RNG
       const uint32_t epoch = uint32_t(io.e.reset_count[ee]);
       double drawn = 0.0;
-      if (uni) {   // step index 0, loads and generator P / P_max from the step stream at index 0
-        if (exo_unit) drawn = exo_draw(epoch, 0u);
-      } else {
+      const bool have = uni || noisy;
+      if (!uni) {   // (uniform mode: the aux variable is the step index, 0)
         uint32_t r[4];
         Philox::generate(io.e.rng_seed, io.e.env_offset + uint64_t(ee), epoch, 0u, r);
         aux = int((uint64_t(r[0]) * uint64_t(io.e.period)) >> 32);
       }
+      // step index 0: loads and generator P / P_max from the step stream at index 0 (noisy series: at the drawn table index)
+      if (have && exo_unit) drawn = exo_draw(epoch, 0u, aux);
       cptr_t sd = C + d.off_dev + l * SD_SIZE;
-      if (typ == DEV_LOAD) s0_p = uni ? drawn : io.e.series[slot * io.e.period + aux];
+      if (typ == DEV_LOAD) s0_p = have ? drawn : io.e.series[slot * io.e.period + aux];
       else if (typ == DEV_CLASSICAL || typ == DEV_RENEWABLE) {
         const double uu = Philox::unit_u01(io.e.rng_seed, io.e.env_offset + uint64_t(ee), epoch, slot);
-        s0_p = s0_pm = uni ? drawn : io.e.series[(d.NLOAD + slot) * io.e.period + aux];
+        s0_p = s0_pm = have ? drawn : io.e.series[(d.NLOAD + slot) * io.e.period + aux];
         s0_q = sd[SD_QMIN] + (sd[SD_QMAX] - sd[SD_QMIN]) * uu;
       } else if (typ == DEV_STORAGE) {
         const double uu = Philox::unit_u01(io.e.rng_seed, io.e.env_offset + uint64_t(ee), epoch, d.NGEN + slot);
@@ -97,10 +108,18 @@
       }
     } else if (!skip) {
       const double* a = io.e.action + ee * W_ACT;
-      if (uni) {   // the step index of the episode; the draws are keyed by the NEW index and the episode's epoch
-        aux = int(io.e.state[ee * W_ST + d.SDIM]) + 1;
+      if (uni || noisy) {   // the draws are keyed by the NEW step index of the episode and the episode's epoch
+        const double av = io.e.state[ee * W_ST + d.SDIM];
+        uint32_t step;
+        if (uni) {          // the aux variable is that step index
+          aux = int(av) + 1;
+          step = uint32_t(aux);
+        } else {            // the aux variable is the table index, as in series mode; the step index is timestep + 1
+          aux = int(fmod(av + 1.0, double(io.e.period)));
+          step = uint32_t(io.e.timestep[ee]) + 1u;
+        }
         if (exo_unit) {
-          const double x = exo_draw(uint32_t(io.e.reset_count[ee]) - 1u, uint32_t(aux));
+          const double x = exo_draw(uint32_t(io.e.reset_count[ee]) - 1u, step, aux);
           if (typ == DEV_LOAD) in_p = x;
           else in_pot = x;
         }

@@ -96,7 +96,7 @@ class BatchedANMEnv(GymEnv):
     def __init__(self, network, observation, K, delta_t, gamma, lamb, aux_bounds=None, costs_clipping=None, seed=None,
                  num_envs=1, device="cuda", tol=1e-5, max_iter=100, precision="f64", autoreset=False, series=None,
                  env_offset=0, impl=None, straggler_after="auto", straggler_mid="auto", handoff_after="auto", track_full=False,
-                 fuse_observation=True, variants=None, env_variant=None, exogenous=None, exo_low=None, exo_high=None,
+                 fuse_observation=True, variants=None, env_variant=None, exogenous=None, exo_low=None, exo_high=None, exo_noise=None,
                  max_episode_steps=None, episode_stats=False, io_dtype=None, _backend=None):  # fmt: skip
         GymEnv.reset(self, seed=seed)
         self.K, self.gamma, self.lamb, self.delta_t = K, gamma, lamb, delta_t
@@ -214,11 +214,18 @@ class BatchedANMEnv(GymEnv):
         # P_i ~ U(exo_low[i], exo_high[i]) MW (units: loads by device id, then non-slack generators; defaults: loads
         # [p_min, 0], generators [0, p_max]) from the counter-based RNG -- the stream layout is rng.py's (exo_uniform).
         # K = 1: the aux variable is the step index of the episode.  step() is one launch and never calls next_vars().
-        if exogenous not in (None, "host", "uniform"):
-            raise E.ArgsError("The argument exogenous is %r but should be None, 'host' or 'uniform'." % (exogenous,))
-        self.exogenous = "uniform" if exogenous == "uniform" else "host"
+        # exogenous="series_noise": series mode plus bounded noise drawn INSIDE the step kernels, clipped to
+        # [exo_low, exo_high] -- P_i = clip(series[i, aux'] + exo_noise[i, aux'] (2 u_i - 1)) MW, keyed by the step index of
+        # the episode (rng.py: exo_series_noise).  K = 1: the aux variable is the table index, as in series mode.
+        if exogenous not in (None, "host", "uniform", "series_noise"):
+            raise E.ArgsError("The argument exogenous is %r but should be None, 'host', 'uniform' or 'series_noise'." % (exogenous,))
+        self.exogenous = exogenous if exogenous in ("uniform", "series_noise") else "host"
         self._uniform = self.exogenous == "uniform"
-        self.exo_low = self.exo_high = None
+        self._noisy = self.exogenous == "series_noise"
+        self._drawn = self._uniform or self._noisy   # P_load / P_pot come from the kernels' RNG: next_vars() is never called
+        self.exo_low = self.exo_high = self.exo_noise = None
+        if exo_noise is not None and not self._noisy:
+            raise E.ArgsError("exo_noise needs exogenous='series_noise'")
         if self._uniform:
             from .. import rng as _rng
 
@@ -239,6 +246,40 @@ class BatchedANMEnv(GymEnv):
                 raise E.ArgsError("exo_low / exo_high must have %d entries (loads, then non-slack generators)" % n_exo)
             if not (np.isfinite(self.exo_low).all() and np.isfinite(self.exo_high).all() and (self.exo_low <= self.exo_high).all()):
                 raise E.ArgsError("exo_low / exo_high must be finite with exo_low <= exo_high")
+        elif self._noisy:
+            from .. import rng as _rng
+
+            if self._series is None:
+                raise E.EnvInitializationError("exogenous='series_noise' needs series= (the table the noise is added to)")
+            if K != 1:
+                raise E.EnvInitializationError("exogenous='series_noise' needs K = 1 (the aux variable is the table index)")
+            if variants is not None or env_variant is not None:
+                raise E.EnvInitializationError("exogenous='series_noise' does not take parameter classes (variants=)")
+            if sim.backend.device_type != "cuda":
+                # (a backend that ignores the mode would run a different task without saying so)
+                raise E.EnvInitializationError("exogenous='series_noise' needs the GPU library: this backend does not draw in its kernels")
+            n_exo = sim.N_load + sim.N_non_slack_gen
+            if self._series.ndim != 2 or self._series.shape[0] != n_exo:
+                raise E.ArgsError("series must have %d rows (loads, then non-slack generators)" % n_exo)
+            if exo_noise is None:
+                raise E.ArgsError("exogenous='series_noise' needs exo_noise (a scalar, [n_exo] or [n_exo, period], MW)")
+            amp = np.asarray(exo_noise, dtype=np.float64)
+            if amp.ndim == 1:
+                amp = amp[:, None]
+            try:
+                amp = np.ascontiguousarray(np.broadcast_to(amp, self._series.shape))
+            except ValueError:
+                raise E.ArgsError("exo_noise must be a scalar, [%d] or [%d, %d]" % (n_exo, n_exo, self._series.shape[1])) from None
+            if not (np.isfinite(amp).all() and (amp >= 0).all()):
+                raise E.ArgsError("exo_noise must be finite and >= 0")
+            self.exo_noise = amp
+            d_lo, d_hi = _rng.default_exo_bounds(sim.model)
+            self.exo_low = d_lo if exo_low is None else np.ascontiguousarray(exo_low, dtype=np.float64)
+            self.exo_high = d_hi if exo_high is None else np.ascontiguousarray(exo_high, dtype=np.float64)
+            if self.exo_low.shape != (n_exo,) or self.exo_high.shape != (n_exo,):
+                raise E.ArgsError("exo_low / exo_high must have %d entries (loads, then non-slack generators)" % n_exo)
+            if not (self.exo_low <= self.exo_high).all():   # (NaN fails the comparison; infinite ends mean "no clip")
+                raise E.ArgsError("exo_low / exo_high must not be NaN, with exo_low <= exo_high")
         elif exo_low is not None or exo_high is not None:
             raise E.ArgsError("exo_low / exo_high need exogenous='uniform'")
         slo, shi = self._state_bounds_vectors()
@@ -248,14 +289,16 @@ class BatchedANMEnv(GymEnv):
         ep_kw = {}
         if self._episode_bufs is not None:
             ep_kw = dict(max_episode_steps=self.max_episode_steps or 0, episode=C.pointer(self._episode_bufs))
-        cfg = (_lib.EnvConfigEpisode if ep_kw else _lib.EnvConfig)(
+        if self._noisy:
+            ep_kw["exo_noise"] = self.exo_noise.ctypes.data_as(_lib.c_double_p)
+        cfg = (_lib.EnvConfigNoise if self._noisy else _lib.EnvConfigEpisode if ep_kw else _lib.EnvConfig)(
             K=K, gamma=float(gamma), clip_e_loss=float(c1), clip_penalty=float(c2),
             obs_low=_lib.as_c(slo, np.float64)[1], obs_high=_lib.as_c(shi, np.float64)[1],
             series=None if self._series is None else self._series.ctypes.data_as(_lib.c_double_p),
             period=0 if self._series is None else int(self._series.shape[1]),
-            exo_mode=_lib.EXO_UNIFORM if self._uniform else _lib.EXO_HOST,
-            exo_low=self.exo_low.ctypes.data_as(_lib.c_double_p) if self._uniform else None,
-            exo_high=self.exo_high.ctypes.data_as(_lib.c_double_p) if self._uniform else None,
+            exo_mode=_lib.EXO_UNIFORM if self._uniform else _lib.EXO_SERIES_NOISE if self._noisy else _lib.EXO_HOST,
+            exo_low=self.exo_low.ctypes.data_as(_lib.c_double_p) if self._drawn else None,
+            exo_high=self.exo_high.ctypes.data_as(_lib.c_double_p) if self._drawn else None,
             **ep_kw,
         )  # fmt: skip
         self._cfg_keep = (slo, shi)
@@ -317,7 +360,8 @@ class BatchedANMEnv(GymEnv):
         # compact time index next to `state` (series mode, thread-per-environment family): enables the
         # coalesced-row step kernel
         self._aux_index = None
-        if self._series is not None and K == 1 and sim.impl == "thread":
+        # (series-noise mode: the general step kernel serves it; no compact index, no state_same, no two-launch workspace)
+        if self._series is not None and K == 1 and sim.impl == "thread" and not self._noisy:
             self._aux_index = torch.zeros(E_, dtype=torch.int32, device=self.device)
         self._aux_index_ptr = None if self._aux_index is None else self._aux_index.data_ptr()
         # "state" observation on the fast path: obs = clip(state) is the state itself unless a bound bites, so
@@ -582,9 +626,10 @@ class BatchedANMEnv(GymEnv):
         if seed is not None:
             self.rng_seed = int(seed)
         options = options or {}
-        # (uniform mode: plain reset() draws on the device unless the task brings an init_state() of its own)
-        if options.get("sampler") == "device" or (
-                self._uniform and options.get("init_state") is None and type(self).init_state is BatchedANMEnv.init_state):
+        # (uniform mode: plain reset() draws on the device unless the task brings an init_state() of its own; series-noise
+        # mode: always -- a host init_state() of the task, ANM6EasyVec's for one, knows nothing of the noise)
+        if options.get("sampler") == "device" or (options.get("init_state") is None and (
+                self._noisy or (self._uniform and type(self).init_state is BatchedANMEnv.init_state))):
             return self._reset_on_device(options.get("mask"))
         mask = options.get("mask")
         mask_u8 = None
@@ -604,7 +649,7 @@ class BatchedANMEnv(GymEnv):
                     "Expected size of initial state s0 is %d but actual is %d" % (self.state_N, s0.shape[1])
                 )
             self._launch_reset(s0.contiguous(), todo)
-            if self._uniform:
+            if self._drawn:
                 # a new episode for every environment this reset touched, whoever supplied the rows: one environment
                 # never uses a step stream twice (the epoch is part of its key)
                 self._reset_count += todo.to(torch.int32)

@@ -164,6 +164,66 @@ def exo_pairs(seed, env, epoch, t, n_exo):
     return pairs
 
 
+# ---------------------------------------------------------------------------------------------------------------------
+# Noisy time series (``BatchedANMEnv(exogenous="series_noise")``, anm_env_config.exo_mode = ANM_EXO_SERIES_NOISE).
+#
+# Every step each load and non-slack generator takes its table value plus bounded noise, clipped to an interval.  NORMATIVE:
+#
+# * K = 1.  Inputs: the table ``series[n_exo, period]`` of series mode (MW; rows: loads by device id, then the non-slack
+#   generators), an amplitude table ``noise[n_exo, period]`` (MW, finite, >= 0) and clip ends ``low``, ``high`` ``[n_exo]``
+#   (MW, low <= high, no NaN; an infinite end means "no clip" on that side; defaults: ``default_exo_bounds``).
+# * The aux variable is the table index, exactly as in series mode: aux' = int(fmod(aux + 1, period)).  Observations keep
+#   ANM6Easy's layout and meaning.
+# * Because aux wraps it cannot key the stream.  The step index of the episode does: t' = timestep + 1 on a real step, 0
+#   for the initial state (``timestep`` is therefore a mandatory argument of a step in this mode).  Consequence: (state
+#   row, timestep, reset count) replays the stream; the state row alone does not -- a ``next_vars(state)`` of this task
+#   has to read ``self.timestep`` too.
+# * Stream: the step stream of the uniform mode, unchanged -- ``episode_key``, ``exo_block``, the same tag; unit i takes
+#   words 2 (i % 2), 2 (i % 2) + 1 of block i // 2 of step t'; the epoch is reset_count - 1 during an episode.  A model has
+#   ONE exogenous mode, so the two modes never draw for the same task: sharing the stream is safe.
+# * Map, with u = u01(words):
+#       w   = fma(2.0, u, -1.0)          exact: u = k 2^-53, so 2u - 1 = (k - 2^52) 2^-52 with |k - 2^52| <= 2^52
+#       x   = fma(noise[i, aux'], w, series[i, aux'])                                          the ONE rounding
+#       P_i = x < low_i ? low_i : (x > high_i ? high_i : x)
+#   Compares and selects, not min / max: the sign of a zero and infinite ends then mean the same on the device and here.
+# * Initial state (autoreset, reset() without rows, sample_init_state()): t0 from word 0 of block 0 of the init sampler,
+#   exactly as in series mode; loads and generator P / P_max are the map above at aux' = t0, step index 0, epoch = the
+#   reset count the draw is made with; generator Q and storage SoC from the init sampler's units, quirks included.  A
+#   reset from rows the caller brings uses them as they are and still advances the reset count, as in the uniform mode.
+# * Anchor: with noise == 0 and ends that do not bite, fma(0, w, s) = s -- every draw, the initial state and therefore
+#   every output equals series mode's bit for bit.
+# ---------------------------------------------------------------------------------------------------------------------
+def noise_clip(x: float, low: float, high: float) -> float:
+    """The select-form clip of the mode."""
+    return low if x < low else (high if x > high else x)
+
+
+def exo_series_noise(seed, env, epoch, t, aux, series, noise, low, high):
+    """P_load / P_pot (MW, ``[n_load + n_gen]``) of step index ``t`` of the episode (seed, env, epoch) at table index ``aux``."""
+    series, noise = np.asarray(series, dtype=np.float64), np.asarray(noise, dtype=np.float64)
+    low, high = np.asarray(low, dtype=np.float64), np.asarray(high, dtype=np.float64)
+    key = episode_key(seed, env, epoch)
+    out = np.empty(series.shape[0])
+    for i in range(series.shape[0]):
+        q = exo_block(key, t, i // 2)
+        w = fma(2.0, u01(q[2 * (i % 2)], q[2 * (i % 2) + 1]), -1.0)
+        out[i] = noise_clip(fma(float(noise[i, aux]), w, float(series[i, aux])), float(low[i]), float(high[i]))
+    return out
+
+
+def series_noise_init_state(model, series, noise, low, high, seed, env, epoch):
+    """Initial state the kernels draw for environment ``env`` at its ``epoch``-th reset in the series-noise mode."""
+    s0 = series_init_state(model, series, seed, env, epoch)
+    D, nd = model.N_device, model.N_des
+    x = exo_series_noise(seed, env, epoch, 0, int(s0[-1]), series, noise, low, high)
+    for s, k in enumerate(model.load_idx):
+        s0[k] = x[s]
+    for g, k in enumerate(model.gen_idx):
+        s0[k] = x[model.N_load + g]
+        s0[2 * D + nd + g] = x[model.N_load + g]
+    return s0
+
+
 # ---- vectorised forms (uint64 arithmetic), for batch-sized checks --------------------------------------------------
 def philox4x32_v(seed, env, epoch, draw):
     """``philox4x32`` over arrays (broadcast): returns ``uint64 [..., 4]`` holding the four 32-bit words."""
@@ -208,6 +268,53 @@ def uniform_init_state_v(model, seed, env, epoch, low, high):
     s0 = np.zeros(env.shape + (2 * D + nd + ng + 1,))
     x = exo_uniform_v(seed, env, epoch, 0, low, high)
     sd = np.uint64(seed & 0xFFFFFFFFFFFFFFFF)
+
+    def uniform(u):
+        q = philox4x32_v(sd, env, epoch, np.uint64(1 + u // 2))
+        return u01_v(q[..., 2 * (u % 2)], q[..., 2 * (u % 2) + 1])
+
+    for s, k in enumerate(model.load_idx):
+        s0[..., k] = x[..., s]
+    for g, k in enumerate(model.gen_idx):
+        s0[..., k] = x[..., model.N_load + g]
+        s0[..., 2 * D + nd + g] = x[..., model.N_load + g]
+        s0[..., D + k] = model.dev_q_min[k] + (model.dev_q_max[k] - model.dev_q_min[k]) * uniform(g)
+    for e, k in enumerate(model.des_idx):
+        s0[..., 2 * D + e] = model.dev_soc_min[k] + (model.dev_soc_max[k] - model.dev_soc_min[k]) * uniform(ng + e)
+    return s0
+
+
+def exo_series_noise_v(seed, env, epoch, t, aux, series, noise, low, high):
+    """``exo_series_noise`` for arrays of env / epoch / t / aux (broadcast): ``[..., n_load + n_gen]``.  The map is plain
+    arithmetic here, series + noise (2 u - 1): up to one rounding off the fused one (before the clip)."""
+    series, noise = np.asarray(series, dtype=np.float64), np.asarray(noise, dtype=np.float64)
+    low, high = np.asarray(low, dtype=np.float64), np.asarray(high, dtype=np.float64)
+    env, epoch, t, aux = np.broadcast_arrays(*(np.asarray(a, dtype=np.uint64) for a in (env, epoch, t, aux)))
+    aux = aux.astype(np.int64)
+    kw = philox4x32_v(np.uint64(seed & 0xFFFFFFFFFFFFFFFF), env, epoch, np.uint64(EXO_KEY_DRAW))
+    key = kw[..., 0] | (kw[..., 1] << np.uint64(32))
+    n = series.shape[0]
+    out = np.empty(env.shape + (n,))
+    for j in range((n + 1) // 2):
+        q = philox4x32_v(key, (t & np.uint64(MASK)) | (np.uint64(j) << np.uint64(32)), np.uint64(0), np.uint64(EXO_TAG))
+        for h in range(2):
+            i = 2 * j + h
+            if i < n:
+                x = series[i][aux] + noise[i][aux] * (2.0 * u01_v(q[..., 2 * h], q[..., 2 * h + 1]) - 1.0)
+                out[..., i] = np.where(x < low[i], low[i], np.where(x > high[i], high[i], x))
+    return out
+
+
+def series_noise_init_state_v(model, series, noise, low, high, seed, env, epoch):
+    """``series_noise_init_state`` for arrays of env / epoch: ``[n, state_N]`` (maps in plain arithmetic)."""
+    env, epoch = np.broadcast_arrays(np.asarray(env, dtype=np.uint64), np.asarray(epoch, dtype=np.uint64))
+    series = np.asarray(series, dtype=np.float64)
+    D, nd, ng = model.N_device, model.N_des, model.N_non_slack_gen
+    sd = np.uint64(seed & 0xFFFFFFFFFFFFFFFF)
+    s0 = np.zeros(env.shape + (2 * D + nd + ng + 1,))
+    aux = (philox4x32_v(sd, env, epoch, np.uint64(0))[..., 0] * np.uint64(series.shape[1])) >> np.uint64(32)
+    s0[..., -1] = aux
+    x = exo_series_noise_v(seed, env, epoch, 0, aux, series, noise, low, high)
 
     def uniform(u):
         q = philox4x32_v(sd, env, epoch, np.uint64(1 + u // 2))

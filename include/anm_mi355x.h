@@ -108,7 +108,9 @@ typedef struct anm_episode_buffers {
 typedef struct anm_env_config {
   int32_t K;          /* number of auxiliary variables at the tail of the state vector */
   int32_t tail;       /* which fields behind exo_high the caller's struct HAS (this slot was alignment padding: zero-filled
-                         structs of callers that end at exo_high say 0): ANM_ENV_TAIL_NONE or ANM_ENV_TAIL_EPISODE */
+                         structs of callers that end at exo_high say 0): ANM_ENV_TAIL_NONE, ANM_ENV_TAIL_EPISODE (up to `episode`)
+                         or ANM_ENV_TAIL_NOISE (the struct is an
+                         anm_env_config_noise: `exo_noise` follows `episode`) */
   double gamma;       /* discount factor (terminal reward -c2/(1-gamma), anm_env.py:430) */
   double clip_e_loss; /* costs_clipping[0] (+inf = none) */
   double clip_penalty;/* costs_clipping[1] (+inf = none) */
@@ -125,7 +127,17 @@ typedef struct anm_env_config {
    * (rng_seed, env_offset + env, reset_count[env], step index, i): the stream layout is gym_anm_amd/rng.py's (exo_uniform).
    * Needs K = 1 (the aux variable is the step index of the episode) and no series.
    * exo_low / exo_high: host arrays [n_load + n_gen] in MW, finite, low <= high; NULL = the defaults, loads
-   * [p_min, 0], generators [0, p_max] (MW). */
+   * [p_min, 0], generators [0, p_max] (MW).
+   * ANM_EXO_SERIES_NOISE: a noisy time series -- the table of series mode plus bounded noise, clipped.  With aux' =
+   * (aux + 1) mod period the table index (the aux variable, exactly as in series mode) and t' = timestep + 1 the step
+   * index of the episode (0 for an initial state), unit i gets
+   *     w = fma(2, u_i, -1),  x = fma(exo_noise[i][aux'], w, series[i][aux']),
+   *     P_i = x < exo_low[i] ? exo_low[i] : (x > exo_high[i] ? exo_high[i] : x)   MW
+   * with u_i the uniform mode's draw of (rng_seed, env_offset + env, reset_count[env] - 1, t', i): gym_anm_amd/rng.py
+   * (exo_series_noise) is the specification.  Needs K = 1, `series`, an anm_env_config_noise (tail = ANM_ENV_TAIL_NOISE) with exo_noise, and
+   * `timestep` in anm_step_f64.  exo_low / exo_high are the clip ends here: no NaN, low <= high, infinite = no clip on
+   * that side, NULL = the defaults above.  Zero amplitudes and ends that do not bite give series mode bit for bit.
+   * Both drawing modes go with neither parameter classes nor a batch view. */
   int32_t exo_mode;
   const double* exo_low;
   const double* exo_high;
@@ -139,10 +151,21 @@ typedef struct anm_env_config {
   int32_t max_episode_steps;
   const anm_episode_buffers* episode;
 } anm_env_config;
+/* anm_env_config grown at its tail by the amplitude table of ANM_EXO_SERIES_NOISE: what a caller passes to
+ * anm_model_set_env (cast to anm_env_config*) with cfg.tail = ANM_ENV_TAIL_NOISE.  `cfg` is a prefix, exo_noise follows
+ * `episode` directly; nothing behind `episode` is read when tail < ANM_ENV_TAIL_NOISE.
+ * exo_noise: HOST array [(n_load+n_gen)][period] of noise amplitudes in MW, laid out like `series`; finite and >= 0
+ * (copied by anm_model_set_env).  Ignored in the other modes. */
+typedef struct anm_env_config_noise {
+  anm_env_config cfg;
+  const double* exo_noise;
+} anm_env_config_noise;
 #define ANM_ENV_TAIL_NONE 0
 #define ANM_ENV_TAIL_EPISODE 1
+#define ANM_ENV_TAIL_NOISE 2
 #define ANM_EXO_HOST 0
 #define ANM_EXO_UNIFORM 1
+#define ANM_EXO_SERIES_NOISE 2
 
 const char* anm_last_error(void);
 const char* anm_topology_name(void);  /* name of the topology this library was compiled for */
@@ -307,7 +330,10 @@ int anm_transition_f64(anm_model* m, int64_t num_envs, const double* p_load, con
  * (rng_seed, env_offset + env, reset_count[env]); reset_count[env] is then incremented.
  * init_state == NULL, ANM_EXO_UNIFORM: step index 0, loads and generator potentials from the step stream at index 0,
  * generator Q and storage SoC as in series mode (rng.py: uniform_init_state); reset_count[env] is incremented.
- * (The mode goes with neither parameter classes nor a batch view: refused.)
+ * init_state == NULL, ANM_EXO_SERIES_NOISE: the time index t_0 as in series mode, loads and generator potentials by the
+ * mode's map at table index t_0 and step index 0, generator Q and storage SoC as in series mode (rng.py:
+ * series_noise_init_state); reset_count[env] is incremented.
+ * (The two drawing modes go with neither parameter classes nor a batch view: refused.)
  * Episode buffers (anm_env_config.episode): truncated is cleared and ep_return, ep_disc_return, ep_discount are set to
  * 0, 0, 1 for the environments the call touches; last_* and episodes_done are left alone.
  * ANM_IO_F32 (anm_model_set_io): `obs` points at float [E, state_base_dim + K]; not through a batch view. */
@@ -327,7 +353,9 @@ int anm_reset_f64(anm_model* m, int64_t num_envs, const double* init_state, cons
  * storage unit u - n_gen).  Pinned by tests to the Random123 known answers, to gym_anm_amd/rng.py, to the kernels' own
  * in-line samplers (bit for bit) and to the distribution of the reference's init_state().  Rows are contiguous (no view).
  * ANM_EXO_UNIFORM: the rows of that mode instead (aux = 0, loads / generator P and P_max from the step stream at index 0,
- * Q and SoC from blocks 1 + u / 2 as above; block 0 is unused); raw, if given, still holds the init sampler's blocks. */
+ * Q and SoC from blocks 1 + u / 2 as above; block 0 is unused); raw, if given, still holds the init sampler's blocks.
+ * ANM_EXO_SERIES_NOISE: the rows of that mode (t_0 from block 0, loads / generator P and P_max by the mode's map at table
+ * index t_0 and step index 0, Q and SoC as above); raw as above. */
 int anm_sample_init_state_f64(anm_model* m, int64_t num_envs, uint64_t rng_seed, uint64_t env_offset,
                               const int32_t* reset_count, double* init_state, uint32_t* raw, void* stream);
 
@@ -358,17 +386,20 @@ int anm_step_ws_record_doubles(void);
  *   in : action [E, action_dim];  exo [E, n_load+n_gen] MW and aux_next [E, K] (the output of
  *        next_vars), or both NULL in series mode (aux = (aux+1) mod period, table lookup) and in the uniform
  *        mode (anm_env_config.exo_mode = ANM_EXO_UNIFORM: aux = aux + 1, the step index of the episode; P_load /
- *        P_pot drawn in the kernel, keyed by the NEW index; `exo` given in that mode is an error)
+ *        P_pot drawn in the kernel, keyed by the NEW index; `exo` given in that mode is an error) and in the
+ *        series-noise mode (ANM_EXO_SERIES_NOISE: aux as in series mode, P_load / P_pot = table + noise, clipped, keyed
+ *        by timestep + 1; `exo` / `aux_next` given, or `timestep` or `reset_count` NULL, is an error)
  *   io : soc [E, n_des], state [E, state_base_dim+K], terminated [E], timestep [E] (nullable)
  *   out: obs [E, state_base_dim+K] = clip(state, obs_low, obs_high), reward/e_loss/penalty [E]
  *        (clipped like anm_env.py:423-432), nr_iters (nullable), full (nullable)
- *   autoreset (series mode and uniform mode): an environment that is terminated on entry is re-initialised
+ *   autoreset (series mode, uniform mode and series-noise mode): an environment that is terminated on entry is re-initialised
  *        instead of stepped (Gymnasium "next step" autoreset): its initial state is drawn like
  *        ANM6Easy.init_state (anm6_easy.py:25-52) from a counter-based RNG keyed by
  *        (rng_seed, env_offset + env index, reset_count[e]); reward 0, terminated 0.  env_offset is
  *        the global index of this batch's first environment, so a batch sharded over several GPUs
- *        draws exactly what the unsharded batch would.  (Uniform mode: the initial state of that mode, see
- *        anm_reset_f64.)
+ *        draws exactly what the unsharded batch would.  (Uniform and series-noise mode: the initial state of that
+ *        mode, see anm_reset_f64.  The series-noise mode always runs the general step kernel of the
+ *        thread-per-environment family, never the coalesced-row one.)
  *   episode time limit and statistics (anm_env_config.max_episode_steps / .episode; `timestep` must be given): with
  *        autoreset, "terminated on entry" above reads "terminated, or timestep >= max_episode_steps, on entry".  A real
  *        step writes truncated = (timestep after >= limit) and updates the statistics; the re-initialising call
