@@ -241,7 +241,7 @@ struct Shape {
 };
 
 // 2x2 inverse with ONE Newton step on v_rcp_f64 (measured on MI355X: rcp 24.4 bits, one step 48.7 bits = 2.2e-15
-// relative, two steps 52.2 bits).  An inexact inverse perturbs a Newton STEP by that much and nothing else -- the
+// relative, two steps 52.0 bits).  An inexact inverse perturbs a Newton STEP by that much and nothing else -- the
 // fixed point is set by F, evaluated in full precision -- so the lane-group path, which only ever serves
 // diverging solves and the rare 7- or 8-iteration ones, trades the second step for a shorter dependent chain;
 // the thread-per-environment path keeps two steps (its iterates are pinned bit for bit by round-1 tests).
