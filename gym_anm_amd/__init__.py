@@ -10,6 +10,8 @@ _TOP_LEVEL = {  # the names gym_anm exports at top level (gym_anm/__init__.py:5-
     "ANMEnv": ("gym_anm_amd.envs", "ANMEnv"),
     "MPCAgentPerfect": ("gym_anm_amd.agents", "MPCAgentPerfect"),
     "MPCAgentConstant": ("gym_anm_amd.agents", "MPCAgentConstant"),
+    # (this package's own: the perfect forecast of the tasks drawn inside the step kernels)
+    "MPCAgentPerfectStream": ("gym_anm_amd.agents", "MPCAgentPerfectStream"),
 }
 
 

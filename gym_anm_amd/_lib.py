@@ -95,6 +95,12 @@ class MpcOpts(C.Structure):
     _fields_ = [("tol", C.c_double), ("max_iter", C.c_int32), ("trace", C.c_void_p), ("angle_rows", C.c_int32)]
 
 
+class MpcStream(C.Structure):
+    """anm_mpc_stream: what anm_mpc_act_stream_f64 takes on top of anm_mpc_act_f64 (every pointer a device pointer)"""
+    _fields_ = [("exo_mode", C.c_int32), ("rng_seed", C.c_uint64), ("env_offset", C.c_uint64), ("timestep", C.c_void_p),
+                ("reset_count", C.c_void_p), ("exo_low", C.c_void_p), ("exo_high", C.c_void_p), ("exo_noise", C.c_void_p)]
+
+
 class SolverOpts(C.Structure):
     _fields_ = [("tol", C.c_double), ("max_iter", C.c_int32), ("precision", C.c_int32), ("handoff_after", C.c_int32)]
 
@@ -154,6 +160,8 @@ ABI = {
     "anm_mpc_solve_f64": (C.c_int, [C.c_void_p, C.c_int64] + [_P] * 8 + [C.POINTER(MpcOpts), _P]),
     "anm_mpc_act_f64": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, _P, _P, _P, C.c_int32, _P, _P, C.c_int32] + [_P] * 8
                         + [C.POINTER(MpcOpts), _P]),
+    "anm_mpc_act_stream_f64": (C.c_int, [C.c_void_p, C.c_int64, _P, _P, _P, C.c_int32, _P, _P, C.c_int32] + [_P] * 8
+                               + [C.POINTER(MpcOpts), C.POINTER(MpcStream), _P]),
     "anm_gather_obs_f64": (C.c_int, [C.c_int64, C.c_int32, _P, C.c_int32, C.c_int32, _P, _P, C.c_int32, _P, _P, _P, _P, _P,
                                      _P]),
     "anm_time_step_launches": (C.c_int, [C.c_void_p, C.c_int64] + [_P] * 9 + [C.c_int32, C.c_uint64, C.c_uint64, _P, _P,
@@ -165,7 +173,7 @@ ABI = {
 
 # entry points of modes that live in the GPU kernels alone: a backend that is not the GPU library (the host test double)
 # may lack them -- the host layer refuses those modes on such a backend before it would call them
-GPU_ONLY = ("anm_model_set_io",)
+GPU_ONLY = ("anm_model_set_io", "anm_mpc_act_stream_f64")
 
 
 def bind(cdll, optional=()):
@@ -271,8 +279,8 @@ def load_for_topology(topo, impl=None) -> Backend:
 
 
 MPC_ABI = ("anm_last_error", "anm_topology_signature", "anm_mpc_create", "anm_mpc_destroy", "anm_mpc_dims_of", "anm_mpc_get_tables",
-           "anm_mpc_solve_f64", "anm_mpc_act_f64")
-MPC_FORECAST_CONSTANT, MPC_FORECAST_PERFECT = 1, 2
+           "anm_mpc_solve_f64", "anm_mpc_act_f64", "anm_mpc_act_stream_f64")
+MPC_FORECAST_CONSTANT, MPC_FORECAST_PERFECT, MPC_FORECAST_STREAM = 1, 2, 3
 
 
 class MpcBackend:

@@ -11,6 +11,9 @@ of charge (``mpc.py:390-417``).  So here
 * :class:`MPCAgent` / :class:`MPCAgentConstant` / :class:`MPCAgentPerfect` keep the reference's names,
   constructor arguments and ``act(env)`` contract (``mpc.py:321-346``, ``mpc_constant.py``, ``mpc_perfect.py``)
   on a :class:`~gym_anm_amd.envs.anm_env.BatchedANMEnv`;
+* :class:`MPCAgentPerfectStream` is the perfect-forecast agent of the tasks whose exogenous variables are drawn inside
+  the step kernels (``exogenous="uniform"`` / ``"series_noise"``): its forecast is the tasks' own random stream,
+  evaluated ahead;
 * :class:`DCOPFProgram` spells the reference's program out row by row (``min q.x, l <= A x <= u``); nothing in
   the solve uses it -- it is what the tests check a solution's feasibility against.
 
@@ -27,6 +30,7 @@ import ctypes as C
 import numpy as np
 import torch
 
+from .. import errors as E_
 from ..model import CLASSICAL, LOAD, RENEWABLE, SLACK, STORAGE
 
 INF = np.inf
@@ -230,15 +234,16 @@ class BatchedDCOPF:
 
     def act(self, forecast, env, act_low, act_high):
         """``MPCAgent.act`` as ONE launch (``anm_mpc_act_f64``): the forecasts are gathered inside the kernel -- ``forecast``
-        1: constant, from the state rows of ``env``; 2: perfect, from its periodic tables -- and the first stage's
-        set-points come back as the clipped MW action rows ``[E, 2 n_gen + 2 n_des]`` (a persistent buffer)."""
+        1: constant, from the state rows of ``env``; 2: perfect, from its periodic tables; 3: the stream of a task drawn
+        inside the step kernels, evaluated ahead (``anm_mpc_act_stream_f64``) -- and the first stage's set-points come back
+        as the clipped MW action rows ``[E, 2 n_gen + 2 n_des]`` (a persistent buffer)."""
         d = self.dims
         E = int(env.num_envs)
         self._buffers(E)
         if getattr(self, "_action", None) is None or self._action.shape[0] != E:
             self._action = torch.zeros((E, 2 * d.n_gen + 2 * d.n_des), dtype=torch.float64, device=self.device)
         series_ptr, period = None, 0
-        if forecast == 2:
+        if forecast == 2 or (forecast == 3 and env._series is not None):
             if getattr(self, "_series_src", None) is not env._series:
                 self._series_src = env._series
                 self._series_dev = torch.as_tensor(env._series, dtype=torch.float64, device=self.device).contiguous()
@@ -246,6 +251,8 @@ class BatchedDCOPF:
         same = env._state_same
         aux = None   # the time index is read from the last column of the state row (what `forecast()` does)
         soc = env.simulator.soc
+        if forecast == 3:
+            return self._act_stream(env, E, same, aux, series_ptr, period, soc, act_low, act_high)
         with self._device_ctx():
             rc = self.backend.lib.anm_mpc_act_f64(
                 self._handle, E, int(forecast), env._state_buf.data_ptr(), None if same is None else env._state_obs.data_ptr(),
@@ -254,6 +261,29 @@ class BatchedDCOPF:
                 self.u0.data_ptr(), self.objective.data_ptr(), self.iters.data_ptr(), self.info.data_ptr(), C.byref(self.opts),
                 self._stream_ptr())
         self.backend.check(rc, "anm_mpc_act_f64")
+        return self._action
+
+    def _act_stream(self, env, E, same, aux, series_ptr, period, soc, act_low, act_high):
+        from .. import _lib
+
+        if not getattr(env, "_drawn", False):
+            raise E_.ArgsError("the stream forecast needs an environment with exogenous='uniform' or 'series_noise'")
+        # device copies of the ends and of the amplitude table (host arrays of the environment), cached per environment
+        if getattr(self, "_exo_src", None) is not env:
+            dev = lambda a: None if a is None else torch.as_tensor(a, dtype=torch.float64, device=self.device).contiguous()  # noqa: E731
+            self._exo_src, self._exo_dev = env, (dev(env.exo_low), dev(env.exo_high), dev(env.exo_noise))
+        lo, hi, amp = self._exo_dev
+        st = _lib.MpcStream(exo_mode=_lib.EXO_SERIES_NOISE if env._noisy else _lib.EXO_UNIFORM, rng_seed=int(env.rng_seed),
+                            env_offset=int(env.env_offset), timestep=env.timestep.data_ptr(), reset_count=env._reset_count.data_ptr(),
+                            exo_low=lo.data_ptr(), exo_high=hi.data_ptr(), exo_noise=None if amp is None else amp.data_ptr())
+        with self._device_ctx():
+            rc = self.backend.lib.anm_mpc_act_stream_f64(
+                self._handle, E, env._state_buf.data_ptr(), None if same is None else env._state_obs.data_ptr(),
+                None if same is None else same.data_ptr(), int(env._state_buf.shape[1]), None if aux is None else aux.data_ptr(),
+                series_ptr, period, soc.data_ptr(), act_low.data_ptr(), act_high.data_ptr(), self._action.data_ptr(),
+                self.u0.data_ptr(), self.objective.data_ptr(), self.iters.data_ptr(), self.info.data_ptr(), C.byref(self.opts),
+                C.byref(st), self._stream_ptr())
+        self.backend.check(rc, "anm_mpc_act_stream_f64")
         return self._action
 
     @property
@@ -323,12 +353,16 @@ class MPCAgent:
         """The whole of act() can run as one launch: a stock forecast (not overridden by a subclass), the stock solve and
         state of charge, a batched environment of this package that has what the kernel reads."""
         cls = type(self)
-        stock = {1: MPCAgentConstant, 2: MPCAgentPerfect}.get(self.FUSED_FORECAST)
+        mode = self.FUSED_FORECAST
+        stock = {1: MPCAgentConstant, 2: MPCAgentPerfect, 3: MPCAgentPerfectStream}.get(mode)
+        symbol = "anm_mpc_act_stream_f64" if mode == 3 else "anm_mpc_act_f64"
+        # what the kernel reads: the tables (2), a drawn mode (3); the time index in the last column where a table is indexed
+        has = {1: True, 2: getattr(env, "_series", None) is not None, 3: bool(getattr(env, "_drawn", False))}.get(mode, False)
+        indexed = mode == 2 or (mode == 3 and getattr(env, "_noisy", False))
         return (stock is not None and cls.forecast is stock.forecast and cls.solve is MPCAgent.solve and cls._soc is MPCAgent._soc
-                and hasattr(self.solver.backend.lib, "anm_mpc_act_f64") and hasattr(env, "_state_buf")
-                and (self.FUSED_FORECAST == 1 or getattr(env, "_series", None) is not None)
+                and hasattr(self.solver.backend.lib, symbol) and hasattr(env, "_state_buf") and has
                 and env._state_buf.shape[1] >= 2 * env.simulator.model.N_device + env.simulator.model.N_des
-                + env.simulator.model.N_non_slack_gen + (1 if self.FUSED_FORECAST == 2 else 0))
+                + env.simulator.model.N_non_slack_gen + (1 if indexed else 0))
 
     warn_unconverged = True   # False: act() neither synchronises nor launches anything but the solve (last_converged stays lazy)
     # False (default): act() returns a tensor of its own, like the reference's fresh array and like the unfused path --
@@ -392,11 +426,19 @@ class MPCAgentConstant(MPCAgent):
 
 class MPCAgentPerfect(MPCAgent):
     """Perfect forecasts for series-mode tasks (ANM6Easy): the next N columns of the task's periodic tables
-    (``mpc_perfect.py:24-40``)."""
+    (``mpc_perfect.py:24-40``).
+
+    On a ``exogenous="series_noise"`` task this is the PROFILE forecast -- the noise-free table the noise is added to --
+    not a perfect one: the agent that knows the draws too is :class:`MPCAgentPerfectStream`.  A task without tables
+    (``exogenous="uniform"``, a host hook) has no such forecast: ``ArgsError``."""
 
     FUSED_FORECAST = 2
 
     def forecast(self, env):
+        if getattr(env, "_series", None) is None:
+            raise E_.ArgsError("MPCAgentPerfect forecasts from the periodic tables of a series-mode task and this environment has "
+                               "none; for a task drawn inside the step kernels (exogenous='uniform' / 'series_noise') use "
+                               "MPCAgentPerfectStream")
         tab = torch.as_tensor(env._series, dtype=torch.float64, device=self.device)  # [n_load + n_gen, period]
         period = tab.shape[1]
         t0 = env.state[:, -1].long() + 1
@@ -404,3 +446,48 @@ class MPCAgentPerfect(MPCAgent):
         cols = tab[:, idx]  # [n, E, N]
         nl = env.simulator.N_load
         return cols[:nl].permute(1, 0, 2) / self._base_t, cols[nl:].permute(1, 0, 2) / self._base_t
+
+
+class MPCAgentPerfectStream(MPCAgent):
+    """Perfect forecasts for the tasks whose loads and generator potentials are drawn INSIDE the step kernels
+    (``exogenous="uniform"``, ``exogenous="series_noise"``): stage ``i`` is the task's own draw of step index
+    ``timestep + 1 + i`` of the running episode -- a pure function of (seed, global environment index, reset epoch, step
+    index, unit), so the lanes of the solve evaluate the Philox stream ahead themselves (``rng.exo_forecast`` is the
+    specification; ``anm_mpc_act_stream_f64``, still ONE launch per ``act``).  This is the upper bound a learned policy is
+    measured against on these tasks, what :class:`MPCAgentPerfect` is on a series-mode task.
+
+    The forecast of an environment that is terminated or past its episode limit is the same pure function (the step that
+    follows resets it and ignores the action); the horizon is not cut at ``max_episode_steps`` -- the reference's perfect
+    agent looks past episode ends too."""
+
+    FUSED_FORECAST = 3
+
+    def __init__(self, simulator, *args, **kw):
+        if getattr(simulator, "exogenous", None) not in ("uniform", "series_noise"):
+            raise E_.ArgsError("MPCAgentPerfectStream needs the simulator of an environment with exogenous='uniform' or "
+                               "'series_noise' (the modes drawn inside the step kernels); this one is in mode %r"
+                               % (getattr(simulator, "exogenous", None),))
+        super().__init__(simulator, *args, **kw)
+
+    def _drawn_env(self, env):
+        if not getattr(env, "_drawn", False):
+            raise E_.ArgsError("MPCAgentPerfectStream needs an environment with exogenous='uniform' or 'series_noise'")
+
+    def act(self, env):
+        if not hasattr(env, "vec"):
+            self._drawn_env(env)
+        return super().act(env)
+
+    def forecast(self, env):
+        """The unfused path: the specification itself (``rng.exo_forecast_v``, exact) on the host."""
+        from .. import rng
+
+        self._drawn_env(env)
+        noisy = bool(env._noisy)
+        f = rng.exo_forecast_v(
+            env.rng_seed, env.env_offset, env._reset_count.cpu().numpy(), env.timestep.cpu().numpy(), self.planning_steps,
+            env.exo_low, env.exo_high, series=env._series if noisy else None, noise=env.exo_noise if noisy else None,
+            aux=env.state[:, -1].cpu().numpy().astype(np.int64) if noisy else None)
+        f = torch.as_tensor(f, dtype=torch.float64, device=self.device)   # [E, n_load + n_gen, N] MW
+        nl = env.simulator.N_load
+        return f[:, :nl] / self._base_t, f[:, nl:] / self._base_t

@@ -120,7 +120,7 @@ struct Opts {
 // from the state row, mpc_constant.py:24-35; perfect: from the task's periodic tables, mpc_perfect.py:24-40) and the
 // first stage's set-points leave as the clipped MW action row -- no forecast tensors, no permute / scale / cat / clip launches.
 struct Act {
-  int mode;                   // 0: off (forecast arrays given); 1: constant forecast; 2: perfect forecast
+  int mode;                   // 0: off (forecast arrays given); 1: constant forecast; 2: perfect forecast; 3: the stream (below)
   const double* state;        // [E][state_dim] state rows, MW: dev_p of the loads, gen_p_max; the time index in the last column
   const double* state_alt;    // rows to read where state_same[e] != 0 (the observation rows: anm_model_bind_state_same), or null
   const uint8_t* state_same;  // [E] or null
@@ -134,7 +134,53 @@ struct Act {
   const double* act_hi;
   short load_col[32];         // size classes: column of each load's dev_p in a state row (a topology knows them at compile time)
   int gen_col0;               // ... and the first column of gen_p_max
+  // mode 3 (ANM_MPC_FORECAST_STREAM, anm_mpc_act_stream_f64): the tasks whose loads and generator potentials are drawn inside
+  // the step kernels.  Stage i is the task's own draw of step index timestep + 1 + i of the running episode -- the same
+  // Philox stream, evaluated ahead (anm_device.hpp: ExoUniform, ExoNoise; specification: rng.py, exo_forecast).
+  // `series` / `period` above are the table of the series-noise mode, the table index is found as in mode 2.
+  int exo_mode;               // ANM_EXO_UNIFORM or ANM_EXO_SERIES_NOISE
+  uint64_t seed;              // key of the step kernels' sampler
+  uint64_t env_offset;        // global index of environment 0
+  const int32_t* timestep;    // [E] step index of the episode
+  const int32_t* reset_count; // [E] the episode's epoch is reset_count - 1
+  const double* exo_low;      // [NL + NG] MW: ends of the uniform draw / of the clip
+  const double* exo_high;
+  const double* exo_noise;    // [NL + NG][period] MW amplitudes (series-noise mode)
 };
+
+// Stream forecast: what a stage's draws are keyed by.  The episode key and the step index are those of the step kernels
+// (epoch = reset_count - 1 during an episode, step index t + 1 + i for stage i); the table index of the series-noise mode
+// is series mode's update applied i + 1 times.  A pure function of the arguments: an environment that is terminated or
+// past its limit gets the same forecast (the step that follows resets it and ignores the action).
+struct StreamAt {
+  uint64_t key;
+  uint32_t t;
+  int aux;
+};
+ANM_HD StreamAt act_stream_at(const Act& a, int64_t env, int stage) {
+  StreamAt s;
+  s.key = ExoUniform::episode_key(a.seed, a.env_offset + uint64_t(env), uint32_t(a.reset_count[env]) - 1u);
+  s.t = uint32_t(a.timestep[env]) + 1u + uint32_t(stage);
+  s.aux = 0;
+  if (a.exo_mode == ANM_EXO_SERIES_NOISE) {
+    const double* row = ((a.state_same && a.state_same[env]) ? a.state_alt : a.state) + env * a.state_dim;
+    const int t0 = (a.aux_index ? int(a.aux_index[env]) : int(row[a.state_dim - 1])) + 1;
+    s.aux = (t0 + stage) % a.period;
+  }
+  return s;
+}
+// unit: loads by slot, then the non-slack generators (nl + k, with the network's own nl); p.u.
+ANM_HD double act_stream_value(const Act& a, const StreamAt& s, int unit) {
+  const double lo = a.exo_low[unit], hi = a.exo_high[unit];
+  double v;
+  if (a.exo_mode == ANM_EXO_SERIES_NOISE) {
+    const int64_t at = int64_t(unit) * a.period + s.aux;
+    v = ExoNoise::draw(s.key, s.t, unit, a.exo_noise[at], a.series[at], lo, hi);
+  } else {
+    v = ExoUniform::draw(s.key, s.t, unit, lo, hi);
+  }
+  return v / a.base;
+}
 
 // column of the k-th load's dev_p in a state row = its device index (anm_env.py:139-147: dev_p of every device first)
 template <class T>
@@ -148,8 +194,13 @@ constexpr int load_device(int k) {
   }
 }
 // nl: the network's own number of loads (the rows of `series` before the generators')
-template <class T>
+// STREAM: mode 3 is compiled in (the instantiations behind anm_mpc_act_stream_f64 alone: the others keep their
+// instruction streams)
+template <class T, bool STREAM = false>
 ANM_HD double act_forecast(const Act& a, int64_t env, int stage, bool gen, int k, int col_load, int nl) {
+  if constexpr (STREAM) {
+    if (a.mode == ANM_MPC_FORECAST_STREAM) return act_stream_value(a, act_stream_at(a, env, stage), gen ? nl + k : k);
+  }
   const double* row = ((a.state_same && a.state_same[env]) ? a.state_alt : a.state) + env * a.state_dim;
   double v;
   if (a.mode == 1) {
@@ -651,8 +702,9 @@ struct Step {
   }
 };
 
-// One lane's run of the whole solve.
-template <class T, class X>
+// One lane's run of the whole solve.  STREAM: the forecasts are the stream's (Act, mode 3), drawn by the lane in the
+// prologue -- the episode key once, then the units; nothing of the draws lives on into the iterations.
+template <class T, bool STREAM = false, class X>
 ANM_HD void solve(cptr_t C, const IO& io, const Opts& opt, int64_t env, bool valid, int N, X& x, double* lane_lds = nullptr) {
   typedef Sz<T> S;
   typedef Lane<T> L;
@@ -676,12 +728,22 @@ ANM_HD void solve(cptr_t C, const IO& io, const Opts& opt, int64_t env, bool val
     double pl[pos(NL)];
     constexpr bool PAD = is_padded<T>::value;
     const int nl = PAD ? io.nl : NL, ng = PAD ? io.ng : NG;   // (a topology's kernel: compile-time constants)
-    ANM_UFOR (int l = 0; l < NL; ++l)
-      pl[l] = (!on || l >= nl) ? 0.0 : (io.act.mode ? act_forecast<T>(io.act, env, i, false, l, load_device<T>(l), nl)
-                                                    : io.p_load[(env * N + i) * nl + l]);
-    ANM_UFOR (int g = 0; g < NG; ++g) {
-      const double fc = (!on || g >= ng) ? 0.0 : (io.act.mode ? act_forecast<T>(io.act, env, i, true, g, 0, nl) : io.p_gen[(env * N + i) * ng + g]);
-      ln.wd[g] = fmax(fmin(C[S::T_GPMAX + g], fc) - C[S::T_GPMIN + g], 0.0);
+    if constexpr (STREAM) {
+      StreamAt at{0, 0, 0};
+      if (on) at = act_stream_at(io.act, env, i);
+      ANM_UFOR (int l = 0; l < NL; ++l) pl[l] = (!on || l >= nl) ? 0.0 : act_stream_value(io.act, at, l);
+      ANM_UFOR (int g = 0; g < NG; ++g) {
+        const double fc = (!on || g >= ng) ? 0.0 : act_stream_value(io.act, at, nl + g);
+        ln.wd[g] = fmax(fmin(C[S::T_GPMAX + g], fc) - C[S::T_GPMIN + g], 0.0);
+      }
+    } else {
+      ANM_UFOR (int l = 0; l < NL; ++l)
+        pl[l] = (!on || l >= nl) ? 0.0 : (io.act.mode ? act_forecast<T>(io.act, env, i, false, l, load_device<T>(l), nl)
+                                                      : io.p_load[(env * N + i) * nl + l]);
+      ANM_UFOR (int g = 0; g < NG; ++g) {
+        const double fc = (!on || g >= ng) ? 0.0 : (io.act.mode ? act_forecast<T>(io.act, env, i, true, g, 0, nl) : io.p_gen[(env * N + i) * ng + g]);
+        ln.wd[g] = fmax(fmin(C[S::T_GPMAX + g], fc) - C[S::T_GPMIN + g], 0.0);
+      }
     }
     ANM_UFOR (int j = 0; j < NS; ++j) {  // (a state of charge outside its window -- not a state the simulator produces -- is moved onto it)
       const double raw = valid ? io.soc0[env * NS + j] : 0.5 * (C[S::T_SOCMIN + j] + C[S::T_SOCMAX + j]);
@@ -1063,14 +1125,15 @@ struct WaveGroup {
   __device__ bool all_done(bool d) const { return __all(d); }
 };
 
-template <class T, int MODE>
+// STREAM: the instantiations of anm_mpc_act_stream_f64 (solve: the lanes draw their forecasts from the tasks' stream)
+template <class T, int MODE, bool STREAM = false>
 __global__ __launch_bounds__(64) void k_mpc(cptr_t C, IO io, Opts opt, int64_t n_envs, int N, int G) {
   if constexpr (Sz<T>::FITS) {
     const int lane = threadIdx.x;
     const int64_t env = int64_t(blockIdx.x) * (64 / G) + lane / G;
     WaveGroup<MODE> x{G, lane % G, lane};
     extern __shared__ double mpc_lds[];   // [2 NR][64]: 1/s and the predictor's ds*dz of every row of every lane
-    solve<T>(C, io, opt, env, env < n_envs, N, x, mpc_lds + lane);
+    solve<T, STREAM>(C, io, opt, env, env < n_envs, N, x, mpc_lds + lane);
   }
 }
 #endif

@@ -9,19 +9,23 @@ bool mpc_lds_attribute() {   // above the default per-workgroup limit: ask for t
   if (mpc::Sz<TT>::LDS_BYTES <= 64 * 1024) return true;
   return hipFuncSetAttribute((const void*)mpc::k_mpc<TT, 0>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) == hipSuccess &&
          hipFuncSetAttribute((const void*)mpc::k_mpc<TT, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) == hipSuccess &&
-         hipFuncSetAttribute((const void*)mpc::k_mpc<TT, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) == hipSuccess;
+         hipFuncSetAttribute((const void*)mpc::k_mpc<TT, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) == hipSuccess &&
+         hipFuncSetAttribute((const void*)mpc::k_mpc<TT, 0, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) == hipSuccess &&
+         hipFuncSetAttribute((const void*)mpc::k_mpc<TT, 1, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) == hipSuccess &&
+         hipFuncSetAttribute((const void*)mpc::k_mpc<TT, 2, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) == hipSuccess;
 }
 
 // one group of G lanes per environment: one thread (N = 1), a part of a DPP row (N <= 16), half or all of a wavefront
-extern "C++" template <class TT>
+// STREAM: the instantiations whose lanes draw the forecasts from the tasks' stream (anm_mpc_act_stream_f64)
+extern "C++" template <class TT, bool STREAM = false>
 void launch_mpc(unsigned grid, hipStream_t s, anm_mpc* m, const mpc::IO& io, const mpc::Opts& o, int64_t num_envs, int G) {
   const size_t lds_bytes = mpc::Sz<TT>::LDS_BYTES;
   if (G == 1)
-    hipLaunchKernelGGL((mpc::k_mpc<TT, 0>), dim3(grid), dim3(64), lds_bytes, s, (cptr_t)m->d_tab, io, o, num_envs, m->N, G);
+    hipLaunchKernelGGL((mpc::k_mpc<TT, 0, STREAM>), dim3(grid), dim3(64), lds_bytes, s, (cptr_t)m->d_tab, io, o, num_envs, m->N, G);
   else if (G <= 16)
-    hipLaunchKernelGGL((mpc::k_mpc<TT, 1>), dim3(grid), dim3(64), lds_bytes, s, (cptr_t)m->d_tab, io, o, num_envs, m->N, G);
+    hipLaunchKernelGGL((mpc::k_mpc<TT, 1, STREAM>), dim3(grid), dim3(64), lds_bytes, s, (cptr_t)m->d_tab, io, o, num_envs, m->N, G);
   else
-    hipLaunchKernelGGL((mpc::k_mpc<TT, 2>), dim3(grid), dim3(64), lds_bytes, s, (cptr_t)m->d_tab, io, o, num_envs, m->N, G);
+    hipLaunchKernelGGL((mpc::k_mpc<TT, 2, STREAM>), dim3(grid), dim3(64), lds_bytes, s, (cptr_t)m->d_tab, io, o, num_envs, m->N, G);
 }
 
 int anm_mpc_create(const anm_network_desc* desc, double gamma, double safety_margin, int32_t planning_steps, anm_mpc** out) {
@@ -118,6 +122,7 @@ int anm_mpc_get_tables(const anm_mpc* m, double* out) {
 }
 
 static int mpc_launch(anm_mpc* m, int64_t num_envs, mpc::IO io, const anm_mpc_opts* opts, void* stream, const char* who) {
+  const bool drawn = io.act.mode == ANM_MPC_FORECAST_STREAM;
   typedef mpc::Sz<Topo> S;
   mpc::Opts o{1e-11, 40};
   if (opts) {
@@ -136,8 +141,12 @@ static int mpc_launch(anm_mpc* m, int64_t num_envs, mpc::IO io, const anm_mpc_op
   const unsigned grid = unsigned((num_envs + per_wave - 1) / per_wave);
   hipStream_t s = static_cast<hipStream_t>(stream);
   if (full) {
-    if constexpr (S::FITS) launch_mpc<Topo>(grid, s, m, io, o, num_envs, G);
-    else { g_err = std::string(who) + ": with its angle rows this network has too many rows per stage for the MPC kernel"; return -1; }
+    if constexpr (S::FITS) {
+      if (drawn) launch_mpc<Topo, true>(grid, s, m, io, o, num_envs, G);
+      else launch_mpc<Topo>(grid, s, m, io, o, num_envs, G);
+    } else { g_err = std::string(who) + ": with its angle rows this network has too many rows per stage for the MPC kernel"; return -1; }
+  } else if (drawn) {
+    launch_mpc<TopoNoTheta, true>(grid, s, m, io, o, num_envs, G);
   } else {
     launch_mpc<TopoNoTheta>(grid, s, m, io, o, num_envs, G);
   }
@@ -158,27 +167,66 @@ int anm_mpc_solve_f64(anm_mpc* m, int64_t num_envs, const double* p_load_forecas
   return mpc_launch(m, num_envs, io, opts, stream, "anm_mpc_solve_f64");
 }
 
-int anm_mpc_act_f64(anm_mpc* m, int64_t num_envs, int32_t forecast, const double* state, const double* state_alt,
-                    const uint8_t* state_same, int32_t state_dim, const int32_t* aux_index, const double* series,
-                    int32_t period, const double* soc, const double* act_low, const double* act_high, double* action,
-                    double* u0, double* objective, int32_t* iters, double* info, const anm_mpc_opts* opts, void* stream) {
+// what anm_mpc_act_f64 and anm_mpc_act_stream_f64 share: the checks of the common arguments, the Act, the launch
+static int mpc_act(anm_mpc* m, int64_t num_envs, int32_t forecast, const double* state, const double* state_alt,
+                   const uint8_t* state_same, int32_t state_dim, const int32_t* aux_index, const double* series,
+                   int32_t period, const double* soc, const double* act_low, const double* act_high, double* action,
+                   double* u0, double* objective, int32_t* iters, double* info, const anm_mpc_opts* opts,
+                   const anm_mpc_stream* exo, void* stream, const char* who) {
   typedef mpc::Sz<Topo> S;
+  const std::string w(who);
   if (!m || !state || !action || !act_low || !act_high || (m->ng + m->ns > 0 && !u0) || !objective || !iters)
-    return fail("anm_mpc_act_f64: null argument");
-  if (forecast != ANM_MPC_FORECAST_CONSTANT && forecast != ANM_MPC_FORECAST_PERFECT) return fail("anm_mpc_act_f64: unknown forecast");
-  if (S::NS > 0 && !soc) return fail("anm_mpc_act_f64: the state-of-charge array is missing");
-  if (state_same && !state_alt) return fail("anm_mpc_act_f64: state_same given without the rows to read instead");
+    return fail((w + ": null argument").c_str());
+  if (S::NS > 0 && !soc) return fail((w + ": the state-of-charge array is missing").c_str());
+  if (state_same && !state_alt) return fail((w + ": state_same given without the rows to read instead").c_str());
   const int sdim = 2 * m->nd + m->ns + m->ng;
-  if (state_dim < sdim) return fail("anm_mpc_act_f64: state_dim is smaller than the state vector");
-  if (forecast == ANM_MPC_FORECAST_PERFECT) {
-    if (!series || period <= 0) return fail("anm_mpc_act_f64: a perfect forecast needs the task's periodic tables");
-    if (!aux_index && state_dim < sdim + 1)
-      return fail("anm_mpc_act_f64: a perfect forecast needs the time index (aux_index, or the last column of the state)");
+  if (state_dim < sdim) return fail((w + ": state_dim is smaller than the state vector").c_str());
+  const bool table = forecast == ANM_MPC_FORECAST_PERFECT || (exo && exo->exo_mode == ANM_EXO_SERIES_NOISE);
+  if (forecast == ANM_MPC_FORECAST_PERFECT && (!series || period <= 0))
+    return fail((w + ": a perfect forecast needs the task's periodic tables").c_str());
+  if (exo) {
+    if (exo->exo_mode != ANM_EXO_UNIFORM && exo->exo_mode != ANM_EXO_SERIES_NOISE)
+      return fail((w + ": exo_mode must be ANM_EXO_UNIFORM or ANM_EXO_SERIES_NOISE (the modes drawn inside the step kernels)").c_str());
+    if (!exo->timestep || !exo->reset_count) return fail((w + ": the stream forecast needs timestep and reset_count").c_str());
+    if (!exo->exo_low || !exo->exo_high) return fail((w + ": the stream forecast needs exo_low and exo_high (device arrays)").c_str());
+    if (table && (!series || period <= 0 || !exo->exo_noise))
+      return fail((w + ": the series-noise mode needs the task's table (series, period) and its amplitudes (exo_noise)").c_str());
   }
+  if (table && !aux_index && state_dim < sdim + 1)
+    return fail((w + (exo ? ": the series-noise mode" : ": a perfect forecast") + " needs the time index (aux_index, or the last column of the state)").c_str());
   if (num_envs <= 0) return 0;
   mpc::Act a{forecast, state, state_alt, state_same, state_dim, aux_index, series, period, m->base_mva, action, act_low, act_high, {0}, 0};
   for (int l = 0; l < m->nl && l < 32; ++l) a.load_col[l] = m->load_col[l];
   a.gen_col0 = 2 * m->nd + m->ns;
+  if (exo) {
+    a.exo_mode = exo->exo_mode;
+    a.seed = exo->rng_seed;
+    a.env_offset = exo->env_offset;
+    a.timestep = exo->timestep;
+    a.reset_count = exo->reset_count;
+    a.exo_low = exo->exo_low;
+    a.exo_high = exo->exo_high;
+    a.exo_noise = exo->exo_noise;
+  }
   mpc::IO io{nullptr, nullptr, soc, u0, objective, iters, info, nullptr, nullptr, a, 0, 0};
-  return mpc_launch(m, num_envs, io, opts, stream, "anm_mpc_act_f64");
+  return mpc_launch(m, num_envs, io, opts, stream, who);
+}
+
+int anm_mpc_act_f64(anm_mpc* m, int64_t num_envs, int32_t forecast, const double* state, const double* state_alt,
+                    const uint8_t* state_same, int32_t state_dim, const int32_t* aux_index, const double* series,
+                    int32_t period, const double* soc, const double* act_low, const double* act_high, double* action,
+                    double* u0, double* objective, int32_t* iters, double* info, const anm_mpc_opts* opts, void* stream) {
+  if (forecast != ANM_MPC_FORECAST_CONSTANT && forecast != ANM_MPC_FORECAST_PERFECT) return fail("anm_mpc_act_f64: unknown forecast");
+  return mpc_act(m, num_envs, forecast, state, state_alt, state_same, state_dim, aux_index, series, period, soc, act_low, act_high,
+                 action, u0, objective, iters, info, opts, nullptr, stream, "anm_mpc_act_f64");
+}
+
+int anm_mpc_act_stream_f64(anm_mpc* m, int64_t num_envs, const double* state, const double* state_alt,
+                           const uint8_t* state_same, int32_t state_dim, const int32_t* aux_index, const double* series,
+                           int32_t period, const double* soc, const double* act_low, const double* act_high, double* action,
+                           double* u0, double* objective, int32_t* iters, double* info, const anm_mpc_opts* opts,
+                           const anm_mpc_stream* exo, void* stream) {
+  if (!exo) return fail("anm_mpc_act_stream_f64: null argument (anm_mpc_stream)");
+  return mpc_act(m, num_envs, ANM_MPC_FORECAST_STREAM, state, state_alt, state_same, state_dim, aux_index, series, period, soc,
+                 act_low, act_high, action, u0, objective, iters, info, opts, exo, stream, "anm_mpc_act_stream_f64");
 }

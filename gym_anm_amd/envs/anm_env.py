@@ -223,6 +223,7 @@ class BatchedANMEnv(GymEnv):
         self._uniform = self.exogenous == "uniform"
         self._noisy = self.exogenous == "series_noise"
         self._drawn = self._uniform or self._noisy   # P_load / P_pot come from the kernels' RNG: next_vars() is never called
+        sim.exogenous = self.exogenous   # (what an agent built from the simulator alone can know of the task: agents/mpc.py)
         self.exo_low = self.exo_high = self.exo_noise = None
         if exo_noise is not None and not self._noisy:
             raise E.ArgsError("exo_noise needs exogenous='series_noise'")

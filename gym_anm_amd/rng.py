@@ -329,3 +329,108 @@ def series_noise_init_state_v(model, series, noise, low, high, seed, env, epoch)
     for e, k in enumerate(model.des_idx):
         s0[..., 2 * D + e] = model.dev_soc_min[k] + (model.dev_soc_max[k] - model.dev_soc_min[k]) * uniform(ng + e)
     return s0
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# Perfect forecast of the drawn modes (``MPCAgentPerfectStream``, anm_mpc_act_stream_f64; csrc/anm_mpc.hpp, Act mode 3).
+#
+# The draws of step index t of an episode are a pure function of (seed, global environment index, epoch, t, unit), so the
+# future of a running episode is the stream evaluated ahead.  NORMATIVE, for an environment with global index env,
+# epoch = uint32(reset_count - 1), current step index t (``timestep``) and, in series-noise mode, current table index aux:
+#
+# * stage i in [0, N) has step index t_i = uint32(t + 1 + i) and table index aux_i = (aux + 1 + i) % period (series
+#   mode's update applied i + 1 times);
+# * uniform mode:       unit u of stage i is ``exo_uniform(seed, env, epoch, t_i, low, high)[u]``;
+# * series-noise mode:  unit u of stage i is ``exo_series_noise(seed, env, epoch, t_i, aux_i, series, noise, low, high)[u]``;
+# * units: loads by slot, then the non-slack generators; values in MW (the program takes value / baseMVA, a true division);
+# * the same function for an environment that is terminated or past its episode limit (the step that follows resets it
+#   and ignores the action); the horizon is not cut at ``max_episode_steps``.
+# ---------------------------------------------------------------------------------------------------------------------
+def exo_forecast(seed, env, epoch, t, N, low, high, series=None, noise=None, aux=None):
+    """Loads / generator potentials (MW, ``[n_load + n_gen, N]``) of the N steps after step index ``t`` of the episode
+    (seed, env, epoch): uniform mode, or -- with ``series``, ``noise`` and the current table index ``aux`` -- series-noise mode."""
+    n = len(low)
+    out = np.empty((n, int(N)))
+    for i in range(int(N)):
+        ti = (int(t) + 1 + i) & MASK
+        if series is None:
+            out[:, i] = exo_uniform(seed, env, epoch, ti, low, high)
+        else:
+            period = np.asarray(series).shape[1]
+            out[:, i] = exo_series_noise(seed, env, epoch, ti, (int(aux) + 1 + i) % period, series, noise, low, high)
+    return out
+
+
+def _two_sum(a, b):
+    s = a + b
+    bb = s - a
+    return s, (a - (s - bb)) + (b - bb)
+
+
+def fma_v(a, b, c):
+    """``fma`` over arrays (broadcast), correctly rounded: the product and the sum are kept as exact two-term expansions and
+    the low parts are added with rounding to odd before the one rounding to nearest (Boldo and Melquiond, "Emulation of a FMA
+    and correctly rounded sums: proved algorithms using rounding to odd", IEEE TC 57(4), 2008).  The expansions are exact away
+    from overflow and underflow only: elements whose product is not comfortably inside the normal range go through ``fma``."""
+    a, b, c = np.broadcast_arrays(*(np.asarray(x, dtype=np.float64) for x in (a, b, c)))
+    with np.errstate(all="ignore"):
+        p = a * b
+
+        def split(x):
+            g = 134217729.0 * x          # 2^27 + 1 (Veltkamp)
+            h = g - (g - x)
+            return h, x - h
+
+        ah, al = split(a)
+        bh, bl = split(b)
+        pl = ((ah * bh - p) + ah * bl + al * bh) + al * bl          # a b = p + pl
+        th, tl = _two_sum(c, p)                                      # c + p = th + tl
+        s, e = _two_sum(tl, pl)
+        # round tl + pl to odd: an inexact sum goes to the neighbour with the odd significand
+        even = (s.view(np.int64) & 1) == 0
+        s = np.where((e != 0) & even, np.nextafter(s, np.where(e > 0, np.inf, -np.inf)), s)
+        z = th + s
+    # an exact zero: the sign IEEE gives (see ``fma``)
+    z = np.where(z == 0, np.where((np.signbit(a) != np.signbit(b)) & np.signbit(c), -0.0, 0.0), z)
+    ap = np.abs(p)
+    odd = ~np.isfinite(p) | ~np.isfinite(c) | ((ap != 0) & ((ap < 1e-200) | (ap > 1e200))) | (np.abs(c) > 1e200) | \
+        ((p == 0) & (a != 0) & (b != 0))
+    if odd.any():
+        z = z.copy()
+        for k in zip(*np.nonzero(odd)):
+            z[k] = fma(float(a[k]), float(b[k]), float(c[k]))
+    return z
+
+
+def exo_forecast_v(seed, env_offset, reset_count, timestep, N, low, high, series=None, noise=None, aux=None):
+    """``exo_forecast`` for the environments of a batch: ``[E, n_load + n_gen, N]`` MW from the per-environment arrays
+    ``reset_count``, ``timestep`` (and ``aux``, series-noise mode); environment e has global index ``env_offset + e``.
+    Unlike the other vectorised forms this one is EXACT (``fma_v``): it is what the unfused path of the agent feeds the
+    solver, which has to see the bits the fused kernel draws."""
+    low, high = np.asarray(low, dtype=np.float64), np.asarray(high, dtype=np.float64)
+    N = int(N)
+    rc = np.asarray(reset_count).astype(np.int64).reshape(-1)
+    E, n = rc.shape[0], len(low)
+    m = np.uint64(MASK)
+    epoch = ((rc - 1) & MASK).astype(np.uint64)[:, None]
+    env = (np.uint64(int(env_offset) & 0xFFFFFFFFFFFFFFFF) + np.arange(E, dtype=np.uint64))[:, None]
+    ti = ((np.asarray(timestep).astype(np.int64).reshape(-1)[:, None] + 1 + np.arange(N)[None, :]) & MASK).astype(np.uint64)  # [E, N]
+    kw = philox4x32_v(np.uint64(int(seed) & 0xFFFFFFFFFFFFFFFF), env, epoch, np.uint64(EXO_KEY_DRAW))
+    key = kw[..., 0] | (kw[..., 1] << np.uint64(32))   # [E, 1]
+    if series is not None:
+        series, noise = np.asarray(series, dtype=np.float64), np.asarray(noise, dtype=np.float64)
+        auxi = (np.asarray(aux).astype(np.int64).reshape(-1)[:, None] + 1 + np.arange(N)[None, :]) % series.shape[1]   # [E, N]
+    out = np.empty((E, n, N))
+    for j in range((n + 1) // 2):
+        q = philox4x32_v(key, (ti & m) | (np.uint64(j) << np.uint64(32)), np.uint64(0), np.uint64(EXO_TAG))   # [E, N, 4]
+        for h in range(2):
+            i = 2 * j + h
+            if i >= n:
+                continue
+            u = u01_v(q[..., 2 * h], q[..., 2 * h + 1])
+            if series is None:
+                out[:, i, :] = fma_v(high[i] - low[i], u, low[i])
+            else:
+                x = fma_v(noise[i][auxi], 2.0 * u - 1.0, series[i][auxi])   # (2 u - 1: exact, see the mode's map)
+                out[:, i, :] = np.where(x < low[i], low[i], np.where(x > high[i], high[i], x))
+    return out

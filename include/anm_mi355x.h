@@ -522,6 +522,35 @@ int anm_mpc_act_f64(anm_mpc* m, int64_t num_envs, int32_t forecast, const double
                     int32_t period, const double* soc, const double* act_low, const double* act_high, double* action,
                     double* u0, double* objective, int32_t* iters, double* info, const anm_mpc_opts* opts, void* stream);
 
+/* The perfect forecast of the tasks whose loads and generator potentials are drawn INSIDE the step kernels
+ * (anm_env_config.exo_mode = ANM_EXO_UNIFORM or ANM_EXO_SERIES_NOISE): stage i of environment e is the task's own draw of
+ * step index timestep[e] + 1 + i of the running episode -- the stream of (rng_seed, env_offset + e, reset_count[e] - 1),
+ * evaluated ahead by the lanes of the solve (no forecast arrays, still ONE launch).  Series-noise mode: at table index
+ * (t + 1 + i) mod period, t found as for ANM_MPC_FORECAST_PERFECT.  The forecast is the same pure function for an
+ * environment that is terminated or past its episode limit (the step that follows resets it and ignores the action), and
+ * the horizon is not cut at the limit.  gym_anm_amd/rng.py (exo_forecast) is the specification.
+ * Every pointer is a DEVICE pointer (the tables anm_env_config takes are host arrays: the caller keeps device copies). */
+typedef struct anm_mpc_stream {
+  int32_t exo_mode;           /* ANM_EXO_UNIFORM or ANM_EXO_SERIES_NOISE: the mode of the environment's model */
+  uint64_t rng_seed;          /* as passed to anm_step_f64 */
+  uint64_t env_offset;
+  const int32_t* timestep;    /* [num_envs] */
+  const int32_t* reset_count; /* [num_envs] */
+  const double* exo_low;      /* [n_load + n_gen] MW: ends of the uniform draw / of the clip (anm_env_config.exo_low, .exo_high) */
+  const double* exo_high;
+  const double* exo_noise;    /* [n_load + n_gen][period] MW: amplitudes (series-noise mode; NULL otherwise) */
+} anm_mpc_stream;
+#define ANM_MPC_FORECAST_STREAM 3
+/* anm_mpc_act_f64 with that forecast (anm_mpc_act_f64 itself keeps refusing 3 as unknown).  `series` / `period`: the table
+ * of the series-noise mode (ignored in uniform mode), `aux_index` as for ANM_MPC_FORECAST_PERFECT.  Refused: an exo_mode
+ * that is neither of the two; timestep, reset_count, exo_low or exo_high NULL; series-noise mode without series, period,
+ * exo_noise or a time index.  num_envs <= 0 returns 0. */
+int anm_mpc_act_stream_f64(anm_mpc* m, int64_t num_envs, const double* state, const double* state_alt,
+                           const uint8_t* state_same, int32_t state_dim, const int32_t* aux_index, const double* series,
+                           int32_t period, const double* soc, const double* act_low, const double* act_high, double* action,
+                           double* u0, double* objective, int32_t* iters, double* info, const anm_mpc_opts* opts,
+                           const anm_mpc_stream* exo, void* stream);
+
 /* Offsets of each quantity inside one row of `full` (p.u. / rad), in the order of the reference's
  * STATE_VARIABLES (constants.py:31-48): bus_p, bus_q, bus_v_magn, bus_v_ang, bus_i_magn,
  * bus_i_ang [n_bus each], dev_p, dev_q [n_dev each], des_soc [n_des], gen_p_max [n_gen],
