@@ -54,7 +54,7 @@ class EnvConfig(C.Structure):
     ]  # fmt: skip
 
 
-ENV_TAIL_NONE, ENV_TAIL_EPISODE, ENV_TAIL_NOISE = 0, 1, 2   # anm_env_config.tail
+ENV_TAIL_NONE, ENV_TAIL_EPISODE, ENV_TAIL_NOISE, ENV_TAIL_CORR = 0, 1, 2, 3   # anm_env_config.tail
 
 
 class EnvConfigEpisode(EnvConfig):
@@ -74,6 +74,16 @@ class EnvConfigNoise(EnvConfigEpisode):
     def __init__(self, *a, **kw):
         super().__init__(*a, **kw)
         C.c_int32.from_address(C.addressof(self) + EnvConfig.K.offset + 4).value = ENV_TAIL_NOISE
+
+
+class EnvConfigCorr(EnvConfigNoise):
+    """anm_env_config_corr (tail = ANM_ENV_TAIL_CORR): the AR(1) tables of the correlated series-noise mode (host) and the
+    noise states of every environment (device, ``[E, n_exo]``)."""
+    _fields_ = [("exo_rho", c_double_p), ("exo_innov", c_double_p), ("exo_z", C.c_void_p)]
+
+    def __init__(self, *a, **kw):
+        super().__init__(*a, **kw)
+        C.c_int32.from_address(C.addressof(self) + EnvConfig.K.offset + 4).value = ENV_TAIL_CORR
 
 
 class StepWs(C.Structure):

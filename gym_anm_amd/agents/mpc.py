@@ -268,6 +268,9 @@ class BatchedDCOPF:
 
         if not getattr(env, "_drawn", False):
             raise E_.ArgsError("the stream forecast needs an environment with exogenous='uniform' or 'series_noise'")
+        if getattr(env, "exo_corr", None) is not None:
+            raise E_.ArgsError("the stream forecast is a function of the step index alone: it does not serve a task with "
+                               "correlated noise (exo_corr=)")
         # device copies of the ends and of the amplitude table (host arrays of the environment), cached per environment
         if getattr(self, "_exo_src", None) is not env:
             dev = lambda a: None if a is None else torch.as_tensor(a, dtype=torch.float64, device=self.device).contiguous()  # noqa: E731
@@ -458,20 +461,31 @@ class MPCAgentPerfectStream(MPCAgent):
 
     The forecast of an environment that is terminated or past its episode limit is the same pure function (the step that
     follows resets it and ignores the action); the horizon is not cut at ``max_episode_steps`` -- the reference's perfect
-    agent looks past episode ends too."""
+    agent looks past episode ends too.
+
+    A task with correlated noise (``exo_corr=``) is refused, ``ArgsError``: its draws depend on the noise state of every
+    unit, not on the step index alone, and this agent's forecast is a pure function of the step index.  (Rolling the
+    chain forward from ``exo_z`` inside the solve is the follow-up; :class:`MPCAgentPerfect`, the profile forecast, and
+    :class:`MPCAgentConstant` read only state and tables and work on such a task.)"""
 
     FUSED_FORECAST = 3
+    _CORR_REFUSAL = ("MPCAgentPerfectStream has no forecast for a task with correlated noise (exo_corr=): the draws depend "
+                     "on the noise state exo_z, not on the step index alone")
 
     def __init__(self, simulator, *args, **kw):
         if getattr(simulator, "exogenous", None) not in ("uniform", "series_noise"):
             raise E_.ArgsError("MPCAgentPerfectStream needs the simulator of an environment with exogenous='uniform' or "
                                "'series_noise' (the modes drawn inside the step kernels); this one is in mode %r"
                                % (getattr(simulator, "exogenous", None),))
+        if getattr(simulator, "exo_corr", None) is not None:
+            raise E_.ArgsError(self._CORR_REFUSAL)
         super().__init__(simulator, *args, **kw)
 
     def _drawn_env(self, env):
         if not getattr(env, "_drawn", False):
             raise E_.ArgsError("MPCAgentPerfectStream needs an environment with exogenous='uniform' or 'series_noise'")
+        if getattr(env, "exo_corr", None) is not None:
+            raise E_.ArgsError(self._CORR_REFUSAL)
 
     def act(self, env):
         if not hasattr(env, "vec"):

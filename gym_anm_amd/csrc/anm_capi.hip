@@ -288,6 +288,8 @@ struct anm_model {
   std::vector<double> exo_default;            // [2][n_load + n_gen] MW: loads [p_min, 0], generators [0, p_max]
   double* d_exo = nullptr;                    // [2][n_load + n_gen] MW: low, high of every unit
   double* d_noise = nullptr;                  // noisy time series: [n_load + n_gen][period] MW amplitudes
+  double* d_corr = nullptr;                   // ... correlated (anm_env_config_corr): [2][n_load + n_gen] rho, then sqrt(1 - rho^2)
+  double* exo_z = nullptr;                    // ... the caller's noise states [E][n_load + n_gen] (device; not owned)
   EpisodeIO ep{};                             // episode time limit and statistics (anm_env_config.max_episode_steps / .episode)
   int io_mode = ANM_IO_F64;                   // anm_model_set_io: float32 action / obs / reward arrays
   std::vector<cplx> ybus;
@@ -636,6 +638,7 @@ void anm_model_destroy(anm_model* m) {
   if (m->d_samp) hipFree(m->d_samp);
   if (m->d_exo) hipFree(m->d_exo);
   if (m->d_noise) hipFree(m->d_noise);
+  if (m->d_corr) hipFree(m->d_corr);
   if (m->d_obs_index) hipFree(m->d_obs_index);
   if (m->d_obs_tab) hipFree(m->d_obs_tab);
   delete m;
@@ -689,8 +692,16 @@ int anm_model_set_env(anm_model* m, const anm_env_config* cfg) {
     hipFree(m->d_noise);
     m->d_noise = nullptr;
   }
-  if (cfg->tail != ANM_ENV_TAIL_NONE && cfg->tail != ANM_ENV_TAIL_EPISODE && cfg->tail != ANM_ENV_TAIL_NOISE)
+  if (m->d_corr) {
+    hipFree(m->d_corr);
+    m->d_corr = nullptr;
+  }
+  m->exo_z = nullptr;
+  if (cfg->tail != ANM_ENV_TAIL_NONE && cfg->tail != ANM_ENV_TAIL_EPISODE && cfg->tail != ANM_ENV_TAIL_NOISE &&
+      cfg->tail != ANM_ENV_TAIL_CORR)
     return fail("anm_model_set_env: unknown value of tail");
+  if (cfg->tail == ANM_ENV_TAIL_CORR && cfg->exo_mode != ANM_EXO_SERIES_NOISE)
+    return fail("anm_model_set_env: correlated noise (tail = ANM_ENV_TAIL_CORR, an anm_env_config_corr) needs exo_mode = ANM_EXO_SERIES_NOISE");
   if (cfg->exo_mode == ANM_EXO_SERIES_NOISE) {
     // noisy time series: the series of series mode, an amplitude table beside it and clip ends (gym_anm_amd/rng.py)
     if (cfg->K != 1) return fail("anm_model_set_env: the series-noise mode needs exactly K = 1 auxiliary variable (the time index)");
@@ -721,6 +732,25 @@ int anm_model_set_env(anm_model* m, const anm_env_config* cfg) {
     if (e != hipSuccess) return fail_hip(e, "hipMalloc(exo noise)");
     e = hipMemcpy(m->d_noise, amp, sizeof(double) * cells, hipMemcpyHostToDevice);
     if (e != hipSuccess) return fail_hip(e, "hipMemcpy(exo noise)");
+    if (cfg->tail == ANM_ENV_TAIL_CORR) {
+      // correlated noise: the AR(1) tables, both from the host (the kernels take no square root), and the caller's states
+      const anm_env_config_corr* cc = reinterpret_cast<const anm_env_config_corr*>(cfg);
+      if (!cc->exo_rho || !cc->exo_innov || !cc->exo_z)
+        return fail("anm_model_set_env: correlated noise needs exo_rho, exo_innov and exo_z (anm_env_config_corr): none may be NULL");
+      std::vector<double> tab(size_t(2 * nexo));
+      for (int k = 0; k < nexo; ++k) {
+        const double r = cc->exo_rho[k], c = cc->exo_innov[k];
+        if (!std::isfinite(r) || !(r >= 0.0 && r < 1.0)) return fail("anm_model_set_env: exo_rho must be finite and in [0, 1)");
+        if (!std::isfinite(c) || !(c > 0.0 && c <= 1.0)) return fail("anm_model_set_env: exo_innov must be finite and in (0, 1]");
+        tab[k] = r;
+        tab[nexo + k] = c;
+      }
+      e = hipMalloc(&m->d_corr, sizeof(double) * tab.size() + 8);
+      if (e != hipSuccess) return fail_hip(e, "hipMalloc(exo corr)");
+      e = hipMemcpy(m->d_corr, tab.data(), sizeof(double) * tab.size(), hipMemcpyHostToDevice);
+      if (e != hipSuccess) return fail_hip(e, "hipMemcpy(exo corr)");
+      m->exo_z = cc->exo_z;
+    }
     m->exo_mode = ANM_EXO_SERIES_NOISE;
   } else if (cfg->exo_mode != ANM_EXO_HOST) {
     if (cfg->exo_mode != ANM_EXO_UNIFORM) return fail("anm_model_set_env: unknown exo_mode");
@@ -1080,6 +1110,11 @@ static int env_io_of_model(const anm_model* m, const char* who, EnvIO& io) {
   io.exo_lo = m->d_exo;
   io.exo_hi = m->exo_mode != ANM_EXO_HOST ? m->d_exo + (m->dims.n_load + m->dims.n_gen) : nullptr;
   io.exo_noise = m->exo_mode == ANM_EXO_SERIES_NOISE ? m->d_noise : nullptr;
+  if (m->exo_mode == ANM_EXO_SERIES_NOISE && m->d_corr) {
+    io.exo_rho = m->d_corr;
+    io.exo_innov = m->d_corr + (m->dims.n_load + m->dims.n_gen);
+    io.exo_z = m->exo_z;
+  }
   io.series = m->d_series;
   io.period = m->period;
   io.ep = m->ep;
@@ -1107,6 +1142,8 @@ int anm_reset_f64(anm_model* m, int64_t n, const double* init_state, const uint8
     return fail("anm_reset_f64: the uniform exogenous mode goes with neither a batch view nor parameter classes");
   if (m->exo_mode == ANM_EXO_SERIES_NOISE && (m->has_view || m->d_env_class))
     return fail("anm_reset_f64: the series-noise mode goes with neither a batch view nor parameter classes");
+  if (m->exo_mode == ANM_EXO_SERIES_NOISE && m->d_corr && !reset_count)
+    return fail("anm_reset_f64: correlated noise needs reset_count (the epoch keys the noise state every reset stores)");
   EnvIO io;
   if (int rc = env_io_of_model(m, "anm_reset_f64", io)) return rc;
   io.init_state = init_state;

@@ -294,6 +294,11 @@ struct EnvIO {
   const double* exo_noise;  // [NEXO, period] MW amplitudes (device)
   EpisodeIO ep;             // episode time limit and statistics (all zero: off)
   int io32;                 // float32 policy-facing I/O (anm_model_set_io; 0 = off): action, obs and reward point at floats
+  // correlated noise of the noisy time series (anm_env_config_corr; all null: off, wave-uniform): the AR(1) tables and the
+  // noise state of every unit of every environment, read, advanced and stored by the lane that OWNS the environment only
+  const double* exo_rho;    // [NEXO] (device)
+  const double* exo_innov;  // [NEXO] sqrt(1 - rho^2), formed on the host (device)
+  double* exo_z;            // [E, NEXO]
 };
 
 // Float32 policy-facing I/O (ANM_IO_F32; gym_anm_amd/io_dtype.py is the specification): the arrays behind EnvIO::action,
@@ -364,9 +369,14 @@ ANM_HD void finish_reset(cptr_t C, EnvWork<T>& w, const S0& s0, int K, double* s
 // The in-kernel drawing modes: the loads and generator potentials of step index t of the episode with key `key` -- uniform
 // over [exo_lo, exo_hi] (ExoUniform), or, `noisy`, the series at table index aux plus bounded noise, clipped (ExoNoise).  One
 // function for both: the Philox blocks are the bulk of the code, the mode (wave-uniform) only chooses the map
+// Correlated noise (io.exo_z bound, wave-uniform): the factor drives the unit's noise state and the state is mapped.  `z`:
+// the row of exo_z of the environment the lane OWNS, or null for a lane that computes along on a clamped index -- it reads
+// and stores nothing, or the environment it borrows would be advanced twice.  `first`: step index 0 of an episode, z = w.
 template <class T>
-ANM_HD void exo_draws(const EnvIO& io, bool noisy, uint64_t key, uint32_t t, int aux, double (&x)[Dims<T>::NEXO > 0 ? Dims<T>::NEXO : 1]) {
+ANM_HD void exo_draws(const EnvIO& io, bool noisy, uint64_t key, uint32_t t, int aux, double (&x)[Dims<T>::NEXO > 0 ? Dims<T>::NEXO : 1],
+                      double* z = nullptr, bool first = false) {
   constexpr int NEXO = Dims<T>::NEXO;
+  const bool corr = noisy && io.exo_z != nullptr;
   static_for<0, (NEXO + 1) / 2>([&](auto J) {
     constexpr int j = J;
     uint32_t q[4];
@@ -374,13 +384,31 @@ ANM_HD void exo_draws(const EnvIO& io, bool noisy, uint64_t key, uint32_t t, int
     static_for<0, 2>([&](auto H) {
       constexpr int i = 2 * j + H;
       if constexpr (i < NEXO) {
-        if (noisy)
-          x[i] = ExoNoise::map(io.exo_noise[i * io.period + aux], ExoNoise::factor(q, i), io.series[i * io.period + aux],
-                               io.exo_lo[i], io.exo_hi[i]);
-        else
+        if (noisy) {
+          double v = ExoNoise::factor(q, i);   // the factor itself or, correlated, the noise state it drives
+          if (corr) {
+            if (!first) v = ExoNoise::advance(io.exo_rho[i], io.exo_innov[i], z ? z[i] : 0.0, v);
+            if (z) z[i] = v;
+          }
+          x[i] = ExoNoise::map_state(io.exo_noise[i * io.period + aux], v, io.series[i * io.period + aux], io.exo_lo[i], io.exo_hi[i]);
+        } else
           x[i] = ExoUniform::map(io.exo_lo[i], io.exo_hi[i], Philox::u01_of(q, i));
       }
     });
+  });
+}
+
+// Correlated noise: the noise state an episode with key `key` starts from -- the factors of step index 0 (rng.py:
+// series_corr_init_z) -- for a reset that keeps the caller's rows and draws nothing else
+template <class T>
+ANM_HD void exo_state_init(uint64_t key, double* z) {
+  constexpr int NEXO = Dims<T>::NEXO;
+  static_for<0, (NEXO + 1) / 2>([&](auto J) {
+    constexpr int j = J;
+    uint32_t q[4];
+    ExoUniform::block(key, 0u, uint32_t(j), q);
+    z[2 * j] = ExoNoise::factor(q, 2 * j);
+    if constexpr (2 * j + 1 < NEXO) z[2 * j + 1] = ExoNoise::factor(q, 2 * j + 1);
   });
 }
 
@@ -393,10 +421,12 @@ ANM_HD void exo_draws(const EnvIO& io, bool noisy, uint64_t key, uint32_t t, int
 // generator P / P_max from the step stream at index 0, generator Q and storage SoC as above (same blocks, same quirks);
 // block 0 is not used.  Or, io.exo_mode == 2 (a wave-uniform run-time branch inside that instantiation), of the noisy
 // time series (rng.py: series_noise_init_state): the time index from block 0 as in series mode, loads and generator
-// P / P_max by ExoNoise at that index and step index 0.
+// P / P_max by ExoNoise at that index and step index 0.  (Correlated noise: the same row -- the first noise state of an
+// episode is the factor of step index 0 -- and that state stored through `z`.)
 // SER: where the exogenous series are read from -- io.series (global memory; the default) or a copy in LDS
 template <class T, bool UNI = false, class SER = const double*>
-ANM_HD int sample_init_state(cptr_t C, const EnvIO& io, int64_t e, uint32_t epoch, double (&s0)[T::SDIM + 1], SER ser = nullptr) {
+ANM_HD int sample_init_state(cptr_t C, const EnvIO& io, int64_t e, uint32_t epoch, double (&s0)[T::SDIM + 1], SER ser = nullptr,
+                             double* z = nullptr) {   // z (UNI, correlated noise): see exo_draws -- the drawn episode's first noise state
   typedef Layout<T> L;
   const uint64_t env = io.env_offset + uint64_t(e);
   int aux = 0;
@@ -410,7 +440,7 @@ ANM_HD int sample_init_state(cptr_t C, const EnvIO& io, int64_t e, uint32_t epoc
     aux = int((uint64_t(r[0]) * uint64_t(io.period)) >> 32);
   }
   // the units at step index 0 (noisy time series: at the table index just drawn)
-  if constexpr (UNI) exo_draws<T>(io, noisy, ExoUniform::episode_key(io.rng_seed, env, epoch), 0u, aux, x);
+  if constexpr (UNI) exo_draws<T>(io, noisy, ExoUniform::episode_key(io.rng_seed, env, epoch), 0u, aux, x, z, true);
   auto exo = [&](auto I) {   // load or generator potential I of the drawn state, MW
     if constexpr (UNI) return x[I];
     else return ser[I * io.period + aux];
@@ -464,6 +494,11 @@ ANM_HD void reset_from(cptr_t C, const EnvIO& io, SolverOpts so, int64_t e, cons
     transition_end<T>(C, w, st, so.tol);
   }
   if (!act) return;
+  // correlated noise, rows the caller brings: the rows are kept, the noise state starts where a drawn episode's does -- at
+  // the factors of step index 0 of the epoch, which is the reset count as it stands (the caller advances it afterwards)
+  if (io.exo_z && io.init_state)
+    exo_state_init<T>(ExoUniform::episode_key(io.rng_seed, io.env_offset + uint64_t(e), uint32_t(io.reset_count[e])),
+                      io.exo_z + e * Dims<T>::NEXO);
   RowPtrs rows{io.state + e * S, io.obs + e * S};
   if (io.io32) rows.obs32 = reinterpret_cast<float*>(io.obs) + e * S;
   finish_reset<T, Layout<T>::KMAX, S0>(C, w, s0, io.K, io.soc + e * WD, rows);
@@ -486,7 +521,9 @@ ANM_HD void op_reset(cptr_t C, const EnvIO& io, SolverOpts so, int64_t slot, con
     reset_from<T, JT>(C, io, so, e, io.init_state + e * (v.w_state > 0 ? v.w_state : T::SDIM + io.K), v, act, lds);
   } else {              // device sampler (series or uniform mode, K = 1): same draws as the autoreset path, kept in registers
     double s0_drawn[T::SDIM + 1];
-    if (io.exo_mode) sample_init_state<T, true>(C, io, e, uint32_t(io.reset_count[e]), s0_drawn);
+    if (io.exo_mode)
+      sample_init_state<T, true>(C, io, e, uint32_t(io.reset_count[e]), s0_drawn, nullptr,
+                                 (io.exo_z && act) ? io.exo_z + e * Dims<T>::NEXO : nullptr);
     else sample_init_state<T>(C, io, e, uint32_t(io.reset_count[e]), s0_drawn);
     if (act) io.reset_count[e] += 1;
     reset_from<T, JT>(C, io, so, e, s0_drawn, v, act, lds);
@@ -508,6 +545,8 @@ struct StepIn {
   int aux_next = -1;                                     // ... or, >= 0, the next one, already formed (integer callers)
   int reset_count;
   int step_index = 0;                                    // noisy time series: timestep before the step (keys the draws)
+  double* exo_z = nullptr;                               // correlated noise: the row of EnvIO::exo_z of the environment the
+                                                         // lane owns; null for a lane on a clamped index (see exo_draws)
 };
 
 // what a step decides besides the state / observation rows
@@ -563,7 +602,7 @@ ANM_HD void step_begin(cptr_t C, CD Cd, const EnvIO& io, SolverOpts so, int64_t 
   int aux = 0;
   if (ctx.resetting) {
     double s0[T::SDIM + 1];  // sampled initial state (K == 1 in series mode)
-    if (UNI && io.exo_mode) aux = sample_init_state<T, true>(C, io, e, uint32_t(in.reset_count), s0);
+    if (UNI && io.exo_mode) aux = sample_init_state<T, true>(C, io, e, uint32_t(in.reset_count), s0, nullptr, in.exo_z);
     else aux = sample_init_state<T, false>(C, io, e, uint32_t(in.reset_count), s0, ser);
     static_for<0, T::NDES>([&](auto I) { ctx.soc_req[I] = s0[2 * T::ND + I]; });
     inputs_from_init_state<T>(C, s0, w, P_load, P_pot, P_set, Q_set);
@@ -581,7 +620,8 @@ ANM_HD void step_begin(cptr_t C, CD Cd, const EnvIO& io, SolverOpts so, int64_t 
       }
       double x[Dims<T>::NEXO > 0 ? Dims<T>::NEXO : 1];
       // (the episode began at epoch reset_count - 1: every reset leaves the count one above the epoch it drew with)
-      exo_draws<T>(io, noisy, ExoUniform::episode_key(io.rng_seed, io.env_offset + uint64_t(e), uint32_t(in.reset_count) - 1u), step, aux, x);
+      exo_draws<T>(io, noisy, ExoUniform::episode_key(io.rng_seed, io.env_offset + uint64_t(e), uint32_t(in.reset_count) - 1u), step, aux, x,
+                   in.exo_z);
       static_for<0, T::NLOAD>([&](auto I) { P_load[I] = x[I]; });
       static_for<0, T::NGEN>([&](auto I) { P_pot[I] = x[T::NLOAD + I]; });
     } else if (series) {
@@ -1141,6 +1181,7 @@ __device__ void op_step_general(cptr_t C, const EnvIO& io, SolverOpts so, int64_
   in.reset_count = ((io.autoreset || io.exo_mode) && io.reset_count) ? io.reset_count[ec] : 0;
   const int32_t ts_prev = io.timestep ? io.timestep[ec] : 0;
   in.step_index = ts_prev;
+  in.exo_z = (io.exo_z && valid) ? io.exo_z + e * D::NEXO : nullptr;   // (under `valid`: ec is another lane's environment)
   if (io.ep.on) in.was_term = in.was_term || (io.autoreset && episode_timed_out(io.ep, ts_prev));
 
   step_begin<T, JT, cptr_t, const double*, true>(C, C, io, so, ec, in, ctx, w, st, -1);

@@ -12,8 +12,10 @@
 // Names the including kernel has in scope (all parts): d (its Dims), io, mode, K = io.e.K, typ / slot / sset (the device
 // lane l plays), l, G, C (the constants of the environment's parameter class), rd, base, the row strides W_LOAD, W_GEN,
 // W_SET, W_DES, W_ACT, W_ST, W_EXO, W_AUX (the network's widths or those of a bound view).
-//   1  inputs: ee (the environment index, valid for an idle lane too).  Declares skip, resetting, sampled, aux, in_p,
-//      in_q, in_pot, soc, s0_q, soc_req.
+//   1  inputs: ee (the environment index, valid for an idle lane too) and env_ok (the lane's slot is inside the batch: ee
+//      is its OWN environment).  Declares skip, resetting, sampled, aux, in_p, in_q, in_pot, soc, s0_q, soc_req.  Stores the
+//      noise states of the correlated series-noise mode (io.e.exo_z), the one output that is read, advanced and written
+//      at the draw site, under env_ok.
 //   2  the stores of mode 0; inside the kernel's do { } while (false), which it leaves with `dump` set.  Needs e, reward,
 //      e_loss, penalty, converged, it, nr_diff, fdiff, dump.
 //   3  declares state, list, ON, OW and the sinks put_obs / put_reward / put; inside a generic lambda whose
@@ -63,14 +65,28 @@
     const bool exo_unit = typ == DEV_LOAD || typ == DEV_CLASSICAL || typ == DEV_RENEWABLE;
     // (one site draws for both modes -- the Philox blocks are the bulk of the code -- and the mode only chooses the map;
     // `at`: the table index of the noisy series)
-    auto exo_draw = [&](uint32_t epoch, uint32_t step, int at) {
+    // correlated noise (io.e.exo_z bound, wave-uniform; rng.py: exo_series_corr): the factor drives the unit's noise state
+    // and the state is mapped.  `first`: step index 0 of an episode, z = w.  `keep`: rows the caller brings -- only the
+    // state is stored.  The read-modify-write is the lane's own unit of its OWN environment: an idle lane (ee clamped to
+    // a valid index) touches nothing, or that environment would be advanced twice; nor does a lane masked out of a reset.
+    const bool corr = noisy && io.e.exo_z != nullptr;
+    const bool own = env_ok && !skip;
+    auto exo_draw = [&](uint32_t epoch, uint32_t step, int at, bool first, bool keep = false) {
       const int unit = typ == DEV_LOAD ? slot : d.NLOAD + slot;
       const uint64_t key = ExoUniform::episode_key(io.e.rng_seed, io.e.env_offset + uint64_t(ee), epoch);
       uint32_t q[4];
       ExoUniform::block(key, step, uint32_t(unit) >> 1, q);
-      if (noisy)
-        return ExoNoise::map(io.e.exo_noise[unit * io.e.period + at], ExoNoise::factor(q, unit), io.e.series[unit * io.e.period + at],
-                             io.e.exo_lo[unit], io.e.exo_hi[unit]);
+      if (noisy) {
+        double v = ExoNoise::factor(q, unit);
+        if (corr) {
+          double* z = io.e.exo_z + ee * (d.NLOAD + d.NGEN) + unit;
+          if (!first) v = ExoNoise::advance(io.e.exo_rho[unit], io.e.exo_innov[unit], own ? *z : 0.0, v);
+          if (own) *z = v;
+        }
+        if (keep) return 0.0;
+        return ExoNoise::map_state(io.e.exo_noise[unit * io.e.period + at], v, io.e.series[unit * io.e.period + at],
+                                   io.e.exo_lo[unit], io.e.exo_hi[unit]);
+      }
       return ExoUniform::map(io.e.exo_lo[unit], io.e.exo_hi[unit], Philox::u01_of(q, unit));
     };
     if (mode == 1 && io.e.init_state) {
@@ -78,6 +94,9 @@
       if (typ != DEV_NONE) { s0_p = s0[l]; s0_q = s0[d.ND + l]; }
       if (typ == DEV_CLASSICAL || typ == DEV_RENEWABLE) s0_pm = s0[2 * d.ND + d.NDES + slot];
       if (typ == DEV_STORAGE) soc_req = s0[2 * d.ND + slot];
+      // (correlated noise: the noise state starts where a drawn episode's does, at the factors of step index 0 of the
+      // epoch -- the reset count as it stands, which the caller advances afterwards)
+      if (corr && exo_unit) exo_draw(uint32_t(io.e.reset_count[ee]), 0u, 0, true, true);
     } else if (resetting) {  // autoreset: ANM6Easy.init_state with the counter-based RNG
       const uint32_t epoch = uint32_t(io.e.reset_count[ee]);
       double drawn = 0.0;
@@ -88,7 +107,7 @@
         aux = int((uint64_t(r[0]) * uint64_t(io.e.period)) >> 32);
       }
       // step index 0: loads and generator P / P_max from the step stream at index 0 (noisy series: at the drawn table index)
-      if (have && exo_unit) drawn = exo_draw(epoch, 0u, aux);
+      if (have && exo_unit) drawn = exo_draw(epoch, 0u, aux, true);
       cptr_t sd = C + d.off_dev + l * SD_SIZE;
       if (typ == DEV_LOAD) s0_p = have ? drawn : io.e.series[slot * io.e.period + aux];
       else if (typ == DEV_CLASSICAL || typ == DEV_RENEWABLE) {
@@ -119,7 +138,7 @@
           step = uint32_t(io.e.timestep[ee]) + 1u;
         }
         if (exo_unit) {
-          const double x = exo_draw(uint32_t(io.e.reset_count[ee]) - 1u, step, aux);
+          const double x = exo_draw(uint32_t(io.e.reset_count[ee]) - 1u, step, aux, false);
           if (typ == DEV_LOAD) in_p = x;
           else in_pot = x;
         }

@@ -97,6 +97,7 @@ class BatchedANMEnv(GymEnv):
                  num_envs=1, device="cuda", tol=1e-5, max_iter=100, precision="f64", autoreset=False, series=None,
                  env_offset=0, impl=None, straggler_after="auto", straggler_mid="auto", handoff_after="auto", track_full=False,
                  fuse_observation=True, variants=None, env_variant=None, exogenous=None, exo_low=None, exo_high=None, exo_noise=None,
+                 exo_corr=None,
                  max_episode_steps=None, episode_stats=False, io_dtype=None, _backend=None):  # fmt: skip
         GymEnv.reset(self, seed=seed)
         self.K, self.gamma, self.lamb, self.delta_t = K, gamma, lamb, delta_t
@@ -227,6 +228,27 @@ class BatchedANMEnv(GymEnv):
         self.exo_low = self.exo_high = self.exo_noise = None
         if exo_noise is not None and not self._noisy:
             raise E.ArgsError("exo_noise needs exogenous='series_noise'")
+        # exo_corr=rho (series-noise mode; a scalar or [n_exo], every entry finite and in [0, 1)): the noise is an AR(1)
+        # chain instead of white -- every unit keeps a noise state z in `exo_z` ([num_envs, n_exo], float64, read-only for
+        # the caller), z' = fma(rho, z, sqrt(1 - rho^2) w), and z' takes the place of the factor w (rng.py:
+        # exo_series_corr).  None: the mode as it was, no buffer; 0.0: the new path, which then equals it bit for bit.
+        self.exo_corr = self.exo_z = self._exo_innov = None
+        if exo_corr is not None:
+            if not self._noisy:
+                raise E.ArgsError("exo_corr needs exogenous='series_noise'")
+            n_exo = sim.N_load + sim.N_non_slack_gen
+            try:
+                rho = np.ascontiguousarray(np.broadcast_to(np.asarray(exo_corr, dtype=np.float64), (n_exo,)))
+            except ValueError:
+                raise E.ArgsError("exo_corr must be a scalar or have %d entries (loads, then non-slack generators)" % n_exo) from None
+            if not (np.isfinite(rho).all() and (rho >= 0).all() and (rho < 1).all()):
+                raise E.ArgsError("exo_corr must be finite and in [0, 1)")
+            self.exo_corr = rho
+            # (formed here, once, and handed to the library beside rho: the kernels take no square root)
+            from .. import rng as _rng
+
+            self._exo_innov = np.ascontiguousarray(_rng.exo_innovation(rho))
+        sim.exo_corr = self.exo_corr   # (tells the agents, like sim.exogenous above)
         if self._uniform:
             from .. import rng as _rng
 
@@ -292,7 +314,11 @@ class BatchedANMEnv(GymEnv):
             ep_kw = dict(max_episode_steps=self.max_episode_steps or 0, episode=C.pointer(self._episode_bufs))
         if self._noisy:
             ep_kw["exo_noise"] = self.exo_noise.ctypes.data_as(_lib.c_double_p)
-        cfg = (_lib.EnvConfigNoise if self._noisy else _lib.EnvConfigEpisode if ep_kw else _lib.EnvConfig)(
+        if self.exo_corr is not None:
+            self.exo_z = torch.zeros((E_, len(self.exo_corr)), dtype=torch.float64, device=self.device)
+            ep_kw.update(exo_rho=self.exo_corr.ctypes.data_as(_lib.c_double_p),
+                         exo_innov=self._exo_innov.ctypes.data_as(_lib.c_double_p), exo_z=self.exo_z.data_ptr())
+        cfg = (_lib.EnvConfigCorr if self.exo_corr is not None else _lib.EnvConfigNoise if self._noisy else _lib.EnvConfigEpisode if ep_kw else _lib.EnvConfig)(
             K=K, gamma=float(gamma), clip_e_loss=float(c1), clip_penalty=float(c2),
             obs_low=_lib.as_c(slo, np.float64)[1], obs_high=_lib.as_c(shi, np.float64)[1],
             series=None if self._series is None else self._series.ctypes.data_as(_lib.c_double_p),

@@ -91,7 +91,7 @@ class _Task(BatchedANMEnv):
         if callable(observation):
             raise E.ArgsError("MixedBatchedANMEnv: a task's observation is \"state\" or a list (a callable observation is a "
                               "function of the state the caller can apply to `state` itself)")
-        if spec.get("exogenous") not in (None, "host") or spec.get("exo_noise") is not None:
+        if spec.get("exogenous") not in (None, "host") or spec.get("exo_noise") is not None or spec.get("exo_corr") is not None:
             # (the modes that draw inside the step kernels are refused by the library behind a batch view)
             raise E.EnvInitializationError("MixedBatchedANMEnv steps through batch views, which take no exogenous mode drawn in "
                                            "the kernels (exogenous='uniform' / 'series_noise'): use BatchedANMEnv")

@@ -223,6 +223,76 @@ def series_noise_init_state(model, series, noise, low, high, seed, env, epoch):
         s0[2 * D + nd + g] = x[model.N_load + g]
     return s0
 
+# ---------------------------------------------------------------------------------------------------------------------
+# Correlated noise for the noisy time series (``BatchedANMEnv(exogenous="series_noise", exo_corr=rho)``; an
+# anm_env_config_corr, tail = ANM_ENV_TAIL_CORR).
+#
+# The noise of the mode above is independent from one step to the next; forecast errors of wind, sun and load are not.
+# With a correlation the factor w drives an AR(1) chain per unit and the chain's state takes w's place in the map.
+# NORMATIVE:
+#
+# * ``rho``: a scalar or ``[n_exo]`` (rows: loads by device id, then the non-slack generators), every entry finite and in
+#   [0, 1).  ``exo_corr=None`` is the mode above with no new buffer; an explicit 0.0 runs the path below.
+# * Per unit i the environment keeps a noise state z_i in a persistent tensor ``exo_z`` ``[num_envs, n_exo]`` (float64,
+#   allocated once).  The caller may read it and never writes it.
+# * c_i = math.sqrt(1.0 - rho_i * rho_i), computed ONCE on the host in Python; both tables travel to the library and the
+#   kernels take no square root.  The library refuses rho outside [0, 1) and c outside (0, 1].
+# * A real step, with w the mode's factor fma(2, u, -1) from the mode's block of the NEW step index t' and aux' the new
+#   table index:
+#       t   = c_i * w                      one rounded product, a statement of its own
+#       z'  = fma(rho_i, z_i, t)           one rounding; stored to exo_z
+#       x   = fma(noise[i, aux'], z', series[i, aux'])
+#       P_i = x < low_i ? low_i : (x > high_i ? high_i : x)
+#   Stream, key, tag, block layout and the table index update are those of the mode above, unchanged.  z' is stored
+#   whether or not the step's power flow converges.
+# * Initial state (autoreset, reset() without rows, a failed draw that is redrawn): z_i = w_i at step index 0 of the epoch
+#   the draw is made with -- the factor the mode already uses for the initial P, so ``series_noise_init_state`` gives the
+#   initial row for every rho.  The process is stationary from step 0: Var z = 1/3 at every step (rho^2 / 3 + c^2 / 3).
+# * A reset() from rows the caller brings keeps the rows, stores the same z_i = w_i(step 0) of its epoch -- the reset count
+#   as it stands before the call -- and advances the reset count as in the mode above.
+# * The step of a terminated environment without autoreset (the absorbing no-op) touches nothing, exo_z included.
+# * Consequences: (state row, timestep, reset count, exo_z row) replays the stream.  |z| is bounded by c / (1 - rho) + 1,
+#   not by 1 (|w| <= 1 and the geometric sum of the innovations, plus the rounding): the clip ends are what keeps P
+#   physical, and their defaults stay ``default_exo_bounds``.
+# * Anchor: rho = 0 gives c = 1, t = w, z' = fma(0, z, w) = w (w is never -0 and z is always finite): every draw, exo_z
+#   aside, equals the mode above bit for bit.
+# ---------------------------------------------------------------------------------------------------------------------
+def exo_factors(seed, env, epoch, t, n_exo):
+    """The factors w = fma(2, u, -1) of the ``n_exo`` units at step index ``t`` of the episode (seed, env, epoch)."""
+    key = episode_key(seed, env, epoch)
+    out = np.empty(n_exo)
+    for i in range(n_exo):
+        q = exo_block(key, t, i // 2)
+        out[i] = fma(2.0, u01(q[2 * (i % 2)], q[2 * (i % 2) + 1]), -1.0)
+    return out
+
+
+def series_corr_init_z(seed, env, epoch, n_exo):
+    """The noise states an episode starts from: the factors of step index 0 of its epoch."""
+    return exo_factors(seed, env, epoch, 0, n_exo)
+
+
+def exo_innovation(rho):
+    """c = sqrt(1 - rho^2) per unit, as the host forms it (``math.sqrt`` of the float64 expression, once)."""
+    import math
+
+    return np.array([math.sqrt(1.0 - float(r) * float(r)) for r in np.atleast_1d(np.asarray(rho, dtype=np.float64))])
+
+
+def exo_series_corr(seed, env, epoch, t, aux, z, series, noise, rho, innov, low, high):
+    """One real step of the correlated mode: ``(P, z')`` -- P_load / P_pot (MW, ``[n_load + n_gen]``) of step index ``t`` of
+    the episode (seed, env, epoch) at table index ``aux`` and the advanced noise states -- from the states ``z`` before it."""
+    series, noise = np.asarray(series, dtype=np.float64), np.asarray(noise, dtype=np.float64)
+    low, high = np.asarray(low, dtype=np.float64), np.asarray(high, dtype=np.float64)
+    n = series.shape[0]
+    w = exo_factors(seed, env, epoch, t, n)
+    P, z1 = np.empty(n), np.empty(n)
+    for i in range(n):
+        tt = float(innov[i]) * float(w[i])
+        z1[i] = fma(float(rho[i]), float(z[i]), tt)
+        P[i] = noise_clip(fma(float(noise[i, aux]), float(z1[i]), float(series[i, aux])), float(low[i]), float(high[i]))
+    return P, z1
+
 
 # ---- vectorised forms (uint64 arithmetic), for batch-sized checks --------------------------------------------------
 def philox4x32_v(seed, env, epoch, draw):
@@ -434,3 +504,41 @@ def exo_forecast_v(seed, env_offset, reset_count, timestep, N, low, high, series
                 x = fma_v(noise[i][auxi], 2.0 * u - 1.0, series[i][auxi])   # (2 u - 1: exact, see the mode's map)
                 out[:, i, :] = np.where(x < low[i], low[i], np.where(x > high[i], high[i], x))
     return out
+
+
+def exo_factors_v(seed, env, epoch, t, n_exo):
+    """``exo_factors`` for arrays of env / epoch / t (broadcast): ``[..., n_exo]`` (exact: 2 u - 1 does not round)."""
+    env, epoch, t = np.broadcast_arrays(*(np.asarray(a, dtype=np.uint64) for a in (env, epoch, t)))
+    kw = philox4x32_v(np.uint64(int(seed) & 0xFFFFFFFFFFFFFFFF), env, epoch, np.uint64(EXO_KEY_DRAW))
+    key = kw[..., 0] | (kw[..., 1] << np.uint64(32))
+    out = np.empty(env.shape + (n_exo,))
+    for j in range((n_exo + 1) // 2):
+        q = philox4x32_v(key, (t & np.uint64(MASK)) | (np.uint64(j) << np.uint64(32)), np.uint64(0), np.uint64(EXO_TAG))
+        for h in range(2):
+            if 2 * j + h < n_exo:
+                out[..., 2 * j + h] = 2.0 * u01_v(q[..., 2 * h], q[..., 2 * h + 1]) - 1.0
+    return out
+
+
+def series_corr_init_z_v(seed, env, epoch, n_exo):
+    """``series_corr_init_z`` for arrays of env / epoch: ``[..., n_exo]``."""
+    return exo_factors_v(seed, env, epoch, 0, n_exo)
+
+
+def exo_series_corr_v(seed, env, epoch, t, aux, z, series, noise, rho, innov, low, high):
+    """``exo_series_corr`` for arrays of env / epoch / t / aux (broadcast to ``[...]``) and states ``z`` ``[..., n_exo]``:
+    ``(P, z')``, both ``[..., n_exo]``.  EXACT like ``exo_forecast_v``: both fused operations go through ``fma_v``."""
+    series, noise = np.asarray(series, dtype=np.float64), np.asarray(noise, dtype=np.float64)
+    low, high = np.asarray(low, dtype=np.float64), np.asarray(high, dtype=np.float64)
+    rho, innov = np.asarray(rho, dtype=np.float64), np.asarray(innov, dtype=np.float64)
+    n = series.shape[0]
+    w = exo_factors_v(seed, env, epoch, t, n)
+    aux = np.broadcast_to(np.asarray(aux).astype(np.int64), w.shape[:-1])
+    z = np.broadcast_to(np.asarray(z, dtype=np.float64), w.shape)
+    tt = innov * w                                   # one rounded product per element
+    z1 = fma_v(rho, z, tt)
+    P = np.empty(w.shape)
+    for i in range(n):
+        x = fma_v(noise[i][aux], z1[..., i], series[i][aux])
+        P[..., i] = np.where(x < low[i], low[i], np.where(x > high[i], high[i], x))
+    return P, z1
