@@ -91,6 +91,7 @@ int main(void) {
   /* no generators besides the slack, no storage: p_pot / p_set / q_set / soc have width 0 */
   anm_solver_opts opts;
   opts.tol = 1e-8; opts.max_iter = 100; opts.precision = ANM_SOLVE_F64;
+  opts.handoff_after = ANM_HANDOFF_AUTO; opts.row_continuation = 0;
   CHECK_ANM(anm_transition_f64(m, E, p_load, NULL, NULL, NULL, NULL, full, reward, e_loss, penalty, conv, iters,
                                &opts, NULL));
   CHECK_HIP(hipDeviceSynchronize());

@@ -112,7 +112,8 @@ class MpcStream(C.Structure):
 
 
 class SolverOpts(C.Structure):
-    _fields_ = [("tol", C.c_double), ("max_iter", C.c_int32), ("precision", C.c_int32), ("handoff_after", C.c_int32)]
+    _fields_ = [("tol", C.c_double), ("max_iter", C.c_int32), ("precision", C.c_int32), ("handoff_after", C.c_int32),
+                ("row_continuation", C.c_int32)]
 
 
 FULL_FIELDS = ["bus_p", "bus_q", "bus_v_magn", "bus_v_ang", "bus_i_magn", "bus_i_ang", "dev_p", "dev_q", "des_soc",
@@ -174,6 +175,7 @@ ABI = {
                                + [C.POINTER(MpcOpts), C.POINTER(MpcStream), _P]),
     "anm_gather_obs_f64": (C.c_int, [C.c_int64, C.c_int32, _P, C.c_int32, C.c_int32, _P, _P, C.c_int32, _P, _P, _P, _P, _P,
                                      _P]),
+    "anm_test_row_dpp": (C.c_int, [_P, _P, _P, _P]),
     "anm_time_step_launches": (C.c_int, [C.c_void_p, C.c_int64] + [_P] * 9 + [C.c_int32, C.c_uint64, C.c_uint64, _P, _P,
                                                                               C.POINTER(StepWs), C.POINTER(SolverOpts), _P,
                                                                               C.c_int32,
@@ -183,7 +185,7 @@ ABI = {
 
 # entry points of modes that live in the GPU kernels alone: a backend that is not the GPU library (the host test double)
 # may lack them -- the host layer refuses those modes on such a backend before it would call them
-GPU_ONLY = ("anm_model_set_io", "anm_mpc_act_stream_f64")
+GPU_ONLY = ("anm_model_set_io", "anm_mpc_act_stream_f64", "anm_test_row_dpp")
 
 
 def bind(cdll, optional=()):

@@ -493,6 +493,58 @@ def lane_pack(n_bus, tt, lane_bus, pos, hy):
     return nw, 1 + nw_ch, 1 + nw_ch + nw_lq, out
 
 
+def row_plan(n_bus, tt):
+    """One solve per 16-lane DPP row, one lane per bus (csrc/anm_group.hpp: newton_rows): every hand-over of the Newton
+    trip is then ONE 64-bit instruction, `v_fmac_f64_dpp` / `v_mov_b64_dpp` with row_newbcast:N -- lane N of the row handed
+    to every lane of the banks (4 consecutive lanes) the bank mask names -- instead of two 32-bit row shifts per double plus
+    the addition that folds the moved value in.  The source is named by the instruction, so no lane has to hold a neutral
+    value; what the layout must provide is that the DESTINATION banks of an instruction hold nothing but its consumers:
+      (a) a bus with children (the destination of child sums and folds) has a bank to itself, its bank-mates are unused lanes;
+      (b) the leaves of one parent (the slack included) share a bank: they are destinations of their parent's broadcasts only;
+      (c) a bus attached to the slack keeps V = 1 + 0j as its parent's voltage and is never the destination of a parent broadcast;
+      (d) follows: a lane inside an instruction's destination banks is a consumer or unused.
+    Banks: the buses with children in bus order, then the leaf sets in the order of their parents.  More than 4 banks, or more
+    than 4 leaves of one parent: None (the topology keeps the lane-group loop).
+    Returns LANE (lane of each bus; bus 0: -1), LP (per lane: bus | height + 1 << 7 | depth + 1 << 14; 0: unused lane) and the
+    hand-overs as (source lane, bank mask) pairs:
+      PAR  parent -> its children, sorted by the children's depth dd (PAR_OFF[dd]: first pair of depth dd; the parent's
+           voltage for the W products, the parent's Newton step for the back substitution);
+      CH   child -> its parent, sorted by (elimination level = height of the child + 1, parent, child class)
+           (CH_OFF[h]: first pair of level h; Schur complement and reduced right-hand side);
+      WS   the same pairs sorted by (parent, child class): the order in which a bus sums its children's W products."""
+    parent, maxch, height, depth = tt["PARENT"], tt["MAXCH"], tt["HEIGHT"], tt["DEPTH"]
+    ch = {b: [c for c in tt["CH"][b * maxch:(b + 1) * maxch] if c > 0] for b in range(1, n_bus)}
+    inner = [b for b in range(1, n_bus) if ch[b]]
+    banks = [[b] for b in inner]
+    for p in [0] + inner:
+        leaves = [b for b in range(1, n_bus) if parent[b] == p and not ch[b]]
+        if len(leaves) > 4:
+            return None
+        if leaves:
+            banks.append(leaves)
+    if len(banks) > 4:
+        return None
+    lane, bank = [-1] * n_bus, [-1] * n_bus
+    for k, bs in enumerate(banks):
+        for j, b in enumerate(bs):
+            lane[b], bank[b] = 4 * k + j, k
+    lp = [0] * 16
+    for b in range(1, n_bus):
+        lp[lane[b]] = b | ((height[b] + 1) << 7) | ((depth[b] + 1) << 14)
+    par = sorted((depth[p] + 1, p) for p in inner)
+    chp = sorted((height[c] + 1, p, k) for p in inner for k, c in enumerate(ch[p]))
+    wsp = sorted((p, k) for p in inner for k, c in enumerate(ch[p]))
+    mask = lambda bs: sum(1 << k for k in sorted({bank[b] for b in bs}))  # noqa: E731
+    return dict(
+        LANE=lane, LP=lp, BANKS=banks,
+        PAR_D=[d for d, _ in par], PAR_SRC=[lane[p] for _, p in par], PAR_BANK=[mask(ch[p]) for _, p in par],
+        PAR_OFF=[sum(1 for d, _ in par if d < dd) for dd in range(tt["MAXD"] + 2)],
+        CH_H=[h for h, _, _ in chp], CH_SRC=[lane[ch[p][k]] for _, p, k in chp], CH_BANK=[1 << bank[p] for _, p, _ in chp],
+        CH_OFF=[sum(1 for h, _, _ in chp if h < hh) for hh in range(tt["MAXH"] + 2)],
+        WS_SRC=[lane[ch[p][k]] for p, k in wsp], WS_BANK=[1 << bank[p] for p, _ in wsp],
+    )  # fmt: skip
+
+
 def _arr(name, values, typ="int"):
     vals = list(values)
     body = ", ".join(str(int(v)) for v in vals) if vals else "0"
@@ -640,6 +692,18 @@ def emit_header(topo, name=None) -> str:
                 if k > 0:
                     cls_h[(tt["HEIGHT"][k] + 1) * maxch_ + c] = 1
         lines += [_arr("T_CLS_H", cls_h)]
+    rp = row_plan(n_bus, tt) if tt is not None else None
+    if rp is None:
+        rp = {k: [0] for k in ("LANE", "LP", "PAR_SRC", "PAR_BANK", "PAR_OFF", "CH_SRC", "CH_BANK", "CH_OFF", "WS_SRC", "WS_BANK")}
+        lines += ["  static constexpr int T_ROW = 0, T_ROW_PAR_N = 0, T_ROW_CH_N = 0;"]
+    else:
+        lines += ["  // one solve per 16-lane row, hand-overs by row_newbcast (codegen.row_plan): lane of each bus, packed row of each lane,",
+                  "  // (source lane, bank mask) of every hand-over",
+                  "  static constexpr int T_ROW = 1, T_ROW_PAR_N = %d, T_ROW_CH_N = %d;" % (len(rp["PAR_SRC"]), len(rp["CH_SRC"]))]
+    lines += [_arr("T_ROW_LANE", rp["LANE"]), _arr("T_ROW_LP", rp["LP"], "unsigned"),
+              _arr("T_ROW_PAR_SRC", rp["PAR_SRC"]), _arr("T_ROW_PAR_BANK", rp["PAR_BANK"]), _arr("T_ROW_PAR_OFF", rp["PAR_OFF"]),
+              _arr("T_ROW_CH_SRC", rp["CH_SRC"]), _arr("T_ROW_CH_BANK", rp["CH_BANK"]), _arr("T_ROW_CH_OFF", rp["CH_OFF"]),
+              _arr("T_ROW_WS_SRC", rp["WS_SRC"]), _arr("T_ROW_WS_BANK", rp["WS_BANK"])]
     lines += [
         "};",
         "}  // namespace",

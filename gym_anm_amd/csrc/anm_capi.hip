@@ -51,9 +51,7 @@ int fail_hip(hipError_t e, const char* where) {
 #ifndef ANM_HANDOFF_DEFAULT
 #define ANM_HANDOFF_DEFAULT 6
 #endif
-#ifndef ANM_MID_CAP_DEFAULT
-#define ANM_MID_CAP_DEFAULT 12  // where the first straggler launch leaves the solves still running to the second
-#endif
+// (ANM_MID_CAP_DEFAULT, where the first straggler launch leaves the solves still running to the second: anm_group.hpp)
 #ifndef ANM_ROWS_WAVES
 #define ANM_ROWS_WAVES 1  // min. waves per SIMD the step kernel is compiled for (register budget 512 / waves)
 #endif
@@ -150,6 +148,28 @@ __global__ __launch_bounds__(BLOCK) void k_step_stragglers(cptr_t C, EnvIO io, S
 }
 
 __global__ void k_step_scatter(EnvIO io) { op_step_scatter<Topo>(io); }
+
+// anm_test_row_dpp: the row hand-over helpers of anm_group.hpp on one wavefront, each result a row of 64 doubles
+__global__ __launch_bounds__(64) void k_test_row_dpp(const double* __restrict__ acc, const double* __restrict__ x,
+                                                     double* __restrict__ out) {
+  const int l = threadIdx.x;
+  const double a = acc[l], v = x[l];
+  double one = 1.0;
+  asm volatile("" : "+v"(one));
+  double s0 = a, s1 = a;
+  group::row_wsum<5, 0x5>(s0, s1, v, v, one);
+  double t0 = a, t1 = a;
+  group::row_wsum<0, 0x1, 7, 0x2, 15, 0xC>(t0, t1, v, v, one);
+  double m0 = a, m1 = a;
+  group::row_mov<12, 0xA>(m0, m1, v, v);
+  Blk<double> D{a, a, a, a};
+  double r0 = a, r1 = a;
+  group::row_fold<3, 0x8>(D, r0, r1, Blk<double>{v, v, v, v}, v, v, one);
+  double b0 = a, b1 = a;
+  group::row_fma<9, 0x3>(b0, b1, v, v, Blk<double>{2.0, 4.0, 16.0, 8.0});
+  out[l] = s0; out[64 + l] = s1; out[128 + l] = t1; out[192 + l] = m0; out[256 + l] = m1;
+  out[320 + l] = D.a; out[384 + l] = D.d; out[448 + l] = r1; out[512 + l] = b0; out[576 + l] = b1;
+}
 
 // obs[e, k] = clip(src(e, index[k]) * scale[k], low[k], high[k]); src is the `full` row for
 // index < full_dim and the aux tail of the state row beyond it; terminated environments observe 0
@@ -478,13 +498,14 @@ int launch_lane_groups(anm_model* m, int mode, const TransitionIO* t, const EnvI
 }
 
 SolverOpts solver(const anm_solver_opts* o, int& precision) {
-  SolverOpts s{1e-5, 100, ANM_HANDOFF_AUTO};
+  SolverOpts s{1e-5, 100, ANM_HANDOFF_AUTO, 0};
   precision = ANM_SOLVE_F64;
   if (o) {
     s.tol = o->tol;
     s.max_iter = o->max_iter;
     precision = o->precision;
     s.handoff = o->handoff_after;
+    s.rowc = o->row_continuation;
   }
   // default hand-over point: every converging solve seen so far needs <= 9 iterations at tol 1e-6, so after
   // ANM_HANDOFF_DEFAULT trips the lanes still iterating are (almost only) diverging solves
@@ -1413,6 +1434,11 @@ int anm_gather_obs_f64(int64_t n, int32_t full_dim, const double* full, int32_t 
   unsigned grid = unsigned(std::min<int64_t>((total + 255) / 256, 2048));
   return launch("launch k_gather_obs", k_gather_obs, grid, 256, 0, static_cast<hipStream_t>(stream), n, int(full_dim), full, int(state_dim),
                 int(K), state, terminated, int(n_obs), index, scale, low, high, obs);
+}
+
+int anm_test_row_dpp(const double* acc, const double* x, double* out, void* stream) {
+  if (!acc || !x || !out) return fail("anm_test_row_dpp: null argument");
+  return launch("launch k_test_row_dpp", k_test_row_dpp, 1, 64, 0, static_cast<hipStream_t>(stream), acc, x, out);
 }
 
 #ifdef ANM_PHASE_TIMING

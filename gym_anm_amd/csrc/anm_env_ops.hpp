@@ -48,6 +48,7 @@ struct SolverOpts {
   double tol;
   int max_iter;
   int handoff;  // >= 0: Newton iterations in thread mode before a running solve moves to a lane group; < 0: never
+  int rowc = 0; // handed-over solves one per 16-lane row or one per lane group (group::continue_collective): 0 policy, 1 rows, -1 groups
 };
 
 template <class T>
@@ -76,7 +77,8 @@ template <class T, class JT>
 ANM_HD void continue_handed_over(cptr_t C, EnvWork<T>& w, PFState<T>& st, bool valid, SolverOpts so, double* lds) {
 #if defined(__HIP_DEVICE_COMPILE__)
   if constexpr (T::TREE != 0)
-    if (ANM_WAVE_ANY(st.active && valid)) group::continue_in_groups<T, JT>(C, w, st, st.active && valid, so.tol, so.max_iter, lds);
+    if (ANM_WAVE_ANY(st.active && valid))
+      group::continue_collective<T, JT>(C, w, st, st.active && valid, so.tol, so.max_iter, so.rowc, lds);
 #endif
 }
 
@@ -1090,7 +1092,7 @@ __device__ void op_step_rows(cptr_t C, const EnvIO& io, SolverOpts so, int64_t n
   if constexpr (CAN_GROUP) {
     // (continue_handed_over, written out: through the function k_step_rows* lose their instruction stream)
     if ((handoff >= 0 || overflow_to_groups) && ANM_WAVE_ANY(st.active && valid))
-      group::continue_in_groups<T, JT>(C, w, st, st.active && valid, so.tol, so.max_iter, lds);
+      group::continue_collective<T, JT>(C, w, st, st.active && valid, so.tol, so.max_iter, so.rowc, lds);
   }
   step_end<T, 1>(C, io, so, ec, ctx, w, st, out);
   const bool store = valid && !pending;
@@ -1192,7 +1194,7 @@ __device__ void op_step_general(cptr_t C, const EnvIO& io, SolverOpts so, int64_
   pf_iterate<T, JT>(C, w, st, so.tol, so.max_iter, handoff >= 0 ? handoff : so.max_iter);
   if constexpr (CAN_GROUP) {
     if (handoff >= 0 && ANM_WAVE_ANY(st.active && valid))
-      group::continue_in_groups<T, JT>(C, w, st, st.active && valid, so.tol, so.max_iter, ldsB);
+      group::continue_collective<T, JT>(C, w, st, st.active && valid, so.tol, so.max_iter, so.rowc, ldsB);
   }
   if (!ctx.absorbing) transition_end<T>(C, w, st, so.tol);
 

@@ -27,6 +27,12 @@
 namespace anm {
 namespace group {
 
+// iteration up to which a wavefront with more handed-over solves than rows keeps them on groups (continue_collective), and
+// where the first straggler launch leaves the solves still running to the second (anm_capi.hip)
+#ifndef ANM_MID_CAP_DEFAULT
+#define ANM_MID_CAP_DEFAULT 12
+#endif
+
 constexpr int LDSX_FETCH = 3;   // child slots a parent lane fetches from LDS before folding them (LDS hand-overs)
 
 // llvm CmpInst predicate codes taken by __builtin_amdgcn_{fcmp,uicmp,sicmp}: they return the compare as a
@@ -225,6 +231,104 @@ constexpr bool child_moves_land_on_parents_or_zero() {
       if (((bank >> (l / 4)) & 1) == 0 || sl < 0 || sl >= T::GRP || T::T_LANE_BUS[sl] != ch) return false;
     }
   return true;
+}
+
+// ---------------------------------------------------------------------------------------------
+// Hand-overs inside a 16-lane row that holds ONE solve, one lane per bus (codegen.row_plan; newton_rows below): gfx950's
+// two 64-bit DPP forms,
+//     v_fmac_f64_dpp d, -s, m  row_newbcast:N row_mask:0xf bank_mask:B     d += -(s of lane N of my row) * m
+//     v_mov_b64_dpp  d,  s     row_newbcast:N row_mask:0xf bank_mask:B     d  =   s of lane N of my row
+// on the lanes of the banks (4 consecutive lanes) B names; every other lane keeps its d.  A hand-over and the operation
+// that folds the moved value in are one instruction: `D -= x_child` is fmac(D, -x, 1.0) -- the product by 1 is exact, one
+// rounding, the bits of the subtraction -- and `a = fma(-J, p_parent, a)` is fmac(a, -p, J), the same product.
+// Two rules these statements keep, because nothing else does:
+//   * the compiler inserts no wait states in front of inline-asm DPP (a VALU write of a register followed within two wait
+//     states by a DPP read of it is a hazard): every statement begins with its own `s_nop 1`, and no instruction of a
+//     statement reads through DPP what the statement itself wrote;
+//   * a source lane switched off by EXEC is not read: every lane of the wavefront executes them (asm volatile: not sunk
+//     into a divergent region).
+// One statement serves up to three (source lane, bank mask) pairs of one hand-over point -- they read the same registers --
+// so a point costs one `s_nop 1`, not one per pair.  (N1 / N2 < 0: no such pair.)
+// ---------------------------------------------------------------------------------------------
+#define ANM_ROW_CTL(n, b) " row_newbcast:%[" n "] row_mask:0xf bank_mask:%[" b "]\n"
+#define ANM_ROW_IMM [n0] "n"(N0), [b0] "n"(B0), [n1] "n"(N1 < 0 ? 0 : N1), [b1] "n"(B1), [n2] "n"(N2 < 0 ? 0 : N2), [b2] "n"(B2)
+#define ANM_ROW_UNPAR(...) __VA_ARGS__
+#define ANM_ROW_ASM(BODY, OUTS, INS)                                                                                          \
+  do {                                                                                                                        \
+    if constexpr (N1 < 0) asm volatile("s_nop 1\n" BODY("n0", "b0") : ANM_ROW_UNPAR OUTS : ANM_ROW_UNPAR INS, ANM_ROW_IMM);     \
+    else if constexpr (N2 < 0)                                                                                                \
+      asm volatile("s_nop 1\n" BODY("n0", "b0") BODY("n1", "b1") : ANM_ROW_UNPAR OUTS : ANM_ROW_UNPAR INS, ANM_ROW_IMM);        \
+    else                                                                                                                      \
+      asm volatile("s_nop 1\n" BODY("n0", "b0") BODY("n1", "b1") BODY("n2", "b2") : ANM_ROW_UNPAR OUTS : ANM_ROW_UNPAR INS,     \
+                   ANM_ROW_IMM);                                                                                              \
+  } while (0)
+#define ANM_ROW_MOV2(n, b) "v_mov_b64_dpp %[d0], %[s0]" ANM_ROW_CTL(n, b) "v_mov_b64_dpp %[d1], %[s1]" ANM_ROW_CTL(n, b)
+#define ANM_ROW_WSUM(n, b) "v_fmac_f64_dpp %[d0], %[s0], %[one]" ANM_ROW_CTL(n, b) "v_fmac_f64_dpp %[d1], -%[s1], %[one]" ANM_ROW_CTL(n, b)
+#define ANM_ROW_FOLD6(F, n, b)                                                                                       \
+  "v_fmac_" F "_dpp %[a], -%[sa], %[one]" ANM_ROW_CTL(n, b) "v_fmac_" F "_dpp %[b], -%[sb], %[one]" ANM_ROW_CTL(n, b)  \
+  "v_fmac_" F "_dpp %[c], -%[sc], %[one]" ANM_ROW_CTL(n, b) "v_fmac_" F "_dpp %[d], -%[sd], %[one]" ANM_ROW_CTL(n, b)  \
+  "v_fmac_" F "_dpp %[r0], -%[l0], %[one]" ANM_ROW_CTL(n, b) "v_fmac_" F "_dpp %[r1], -%[l1], %[one]" ANM_ROW_CTL(n, b)
+#define ANM_ROW_FOLD6_F64(n, b) ANM_ROW_FOLD6("f64", n, b)
+#define ANM_ROW_FOLD6_F32(n, b) ANM_ROW_FOLD6("f32", n, b)
+#define ANM_ROW_FMA4(F, n, b)                                                                                        \
+  "v_fmac_" F "_dpp %[a0], -%[p0], %[ja]" ANM_ROW_CTL(n, b) "v_fmac_" F "_dpp %[a1], -%[p0], %[jc]" ANM_ROW_CTL(n, b)  \
+  "v_fmac_" F "_dpp %[a0], -%[p1], %[jb]" ANM_ROW_CTL(n, b) "v_fmac_" F "_dpp %[a1], -%[p1], %[jd]" ANM_ROW_CTL(n, b)
+#define ANM_ROW_FMA4_F64(n, b) ANM_ROW_FMA4("f64", n, b)
+#define ANM_ROW_FMA4_F32(n, b) ANM_ROW_FMA4("f32", n, b)
+
+// (d0, d1) = (s0, s1) of lane N: the parent's voltage
+template <int N0, int B0, int N1 = -1, int B1 = 0, int N2 = -1, int B2 = 0>
+__device__ __forceinline__ void row_mov(double& d0, double& d1, double s0, double s1) {
+  ANM_ROW_ASM(ANM_ROW_MOV2, ([d0] "+v"(d0), [d1] "+v"(d1)), ([s0] "v"(s0), [s1] "v"(s1)));
+}
+// d0 += s0 of lane N, d1 -= s1 of lane N: a child's W product into its parent's sum (`one` holds 1.0)
+template <int N0, int B0, int N1 = -1, int B1 = 0, int N2 = -1, int B2 = 0>
+__device__ __forceinline__ void row_wsum(double& d0, double& d1, double s0, double s1, double one) {
+  ANM_ROW_ASM(ANM_ROW_WSUM, ([d0] "+v"(d0), [d1] "+v"(d1)), ([s0] "v"(s0), [s1] "v"(s1), [one] "v"(one)));
+}
+// D -= Sc of lane N, (r0, r1) -= (l0, l1) of lane N: a child's Schur complement and reduced right-hand side into its parent
+template <int N0, int B0, int N1 = -1, int B1 = 0, int N2 = -1, int B2 = 0>
+__device__ __forceinline__ void row_fold(Blk<double>& D, double& r0, double& r1, const Blk<double>& Sc, double l0, double l1, double one) {
+  ANM_ROW_ASM(ANM_ROW_FOLD6_F64, ([a] "+v"(D.a), [b] "+v"(D.b), [c] "+v"(D.c), [d] "+v"(D.d), [r0] "+v"(r0), [r1] "+v"(r1)),
+              ([sa] "v"(Sc.a), [sb] "v"(Sc.b), [sc] "v"(Sc.c), [sd] "v"(Sc.d), [l0] "v"(l0), [l1] "v"(l1), [one] "v"(one)));
+}
+template <int N0, int B0, int N1 = -1, int B1 = 0, int N2 = -1, int B2 = 0>
+__device__ __forceinline__ void row_fold(Blk<float>& D, float& r0, float& r1, const Blk<float>& Sc, float l0, float l1, float one) {
+  ANM_ROW_ASM(ANM_ROW_FOLD6_F32, ([a] "+v"(D.a), [b] "+v"(D.b), [c] "+v"(D.c), [d] "+v"(D.d), [r0] "+v"(r0), [r1] "+v"(r1)),
+              ([sa] "v"(Sc.a), [sb] "v"(Sc.b), [sc] "v"(Sc.c), [sd] "v"(Sc.d), [l0] "v"(l0), [l1] "v"(l1), [one] "v"(one)));
+}
+// a0 = fma(-J.b, p1 of lane N, fma(-J.a, p0 of lane N, a0)), a1 likewise with (J.c, J.d): the parent's Newton step into
+// the right-hand side of the back substitution
+template <int N0, int B0, int N1 = -1, int B1 = 0, int N2 = -1, int B2 = 0>
+__device__ __forceinline__ void row_fma(double& a0, double& a1, double p0, double p1, const Blk<double>& J) {
+  ANM_ROW_ASM(ANM_ROW_FMA4_F64, ([a0] "+v"(a0), [a1] "+v"(a1)),
+              ([p0] "v"(p0), [p1] "v"(p1), [ja] "v"(J.a), [jb] "v"(J.b), [jc] "v"(J.c), [jd] "v"(J.d)));
+}
+template <int N0, int B0, int N1 = -1, int B1 = 0, int N2 = -1, int B2 = 0>
+__device__ __forceinline__ void row_fma(float& a0, float& a1, float p0, float p1, const Blk<float>& J) {
+  ANM_ROW_ASM(ANM_ROW_FMA4_F32, ([a0] "+v"(a0), [a1] "+v"(a1)),
+              ([p0] "v"(p0), [p1] "v"(p1), [ja] "v"(J.a), [jb] "v"(J.b), [jc] "v"(J.c), [jd] "v"(J.d)));
+}
+// the pairs [lo, hi) of a hand-over table, three to a statement: f.template operator()<N0, B0, N1, B1, N2, B2>()
+// the tables of codegen.row_plan: PAR (parent -> children), CH (child -> parent, by level), WS (child -> parent, by parent)
+enum : int { ROW_PAR = 0, ROW_CH = 1, ROW_WS = 2 };
+template <class T, int W>
+constexpr int row_src(int i, int hi) {
+  return i >= hi ? -1 : (W == ROW_PAR ? T::T_ROW_PAR_SRC[i] : (W == ROW_CH ? T::T_ROW_CH_SRC[i] : T::T_ROW_WS_SRC[i]));
+}
+template <class T, int W>
+constexpr int row_bank(int i, int hi) {
+  return i >= hi ? 0 : (W == ROW_PAR ? T::T_ROW_PAR_BANK[i] : (W == ROW_CH ? T::T_ROW_CH_BANK[i] : T::T_ROW_WS_BANK[i]));
+}
+// the pairs [LO, HI) of table W, three to a statement: f(N0, B0, N1, B1, N2, B2) with integral constants
+template <class T, int W, int LO, int HI, class F>
+__device__ __forceinline__ void row_points(F&& f) {
+  static_for<0, (HI - LO + 2) / 3>([&](auto Q) {
+    constexpr int i = LO + 3 * int(Q);
+    f(std::integral_constant<int, row_src<T, W>(i, HI)>{}, std::integral_constant<int, row_bank<T, W>(i, HI)>{},
+      std::integral_constant<int, row_src<T, W>(i + 1, HI)>{}, std::integral_constant<int, row_bank<T, W>(i + 1, HI)>{},
+      std::integral_constant<int, row_src<T, W>(i + 2, HI)>{}, std::integral_constant<int, row_bank<T, W>(i + 2, HI)>{});
+  });
 }
 
 // LDS slot of one handed-over solve: 5 per-bus arrays + the iteration count / flags
@@ -791,9 +895,11 @@ __device__ __forceinline__ void newton_groups(const LaneView<T>& V, bool gvalid,
 // `lds`: >= NG * Slot<T>::SIZE doubles, private to this wavefront; every lane of the wave must call.
 // WFREE = false: the predicate-free child sums (four to eight loop-carried registers) left out -- the straggler launch, whose
 // budget is two wavefronts per SIMD.
+// keep (max_iter below the caller's real cap, see continue_collective): a solve that stops only because it reached max_iter
+// stays st.active with its iterate and count.
 template <class T, class JT, bool WFREE = true>
 __device__ __forceinline__ void continue_in_groups(cptr_t C, EnvWork<T>& w, PFState<T>& st, bool mine, double tol, int max_iter,
-                                   double* lds) {
+                                   double* lds, bool keep = false) {
   typedef Slot<T> S;
   constexpr int G = Shape<T>::G, NG = Shape<T>::NG, NB = T::NB;
   const int lane = threadIdx.x & 63;
@@ -852,9 +958,260 @@ __device__ __forceinline__ void continue_in_groups(cptr_t C, EnvWork<T>& w, PFSt
       });
       st.it = int(s[S::IT]);
       st.diff = s[S::FLAGS];
+      st.active = keep && s[S::FLAGS] == INFINITY;
+    }
+    ANM_WAVE_SYNC();
+  }
+}
+
+// ---------------------------------------------------------------------------------------------
+// One solve per 16-lane row (topologies with a codegen.row_plan): four solves per wavefront, one lane per bus, every
+// hand-over of the trip one row_newbcast instruction (row_mov / row_wsum / row_fold / row_fma above).  The per-lane algebra
+// is that of newton_groups<MERGED>: every floating-point operation of every bus is the same operation on the same
+// operands in the same order -- only where an operand comes from changes -- so a solve gives the same bits on rows as on
+// groups.  Nobody relies on neutral values in the unused lanes: every consumer names its source.
+// ---------------------------------------------------------------------------------------------
+template <class T>
+struct RowView {
+  int b;                   // bus played (0: unused lane)
+  bool lane_bus;
+  int height, depth;
+  double ybb_r, ybb_i, ybp_r, ybp_i, ypb_r, ypb_i;   // Y_bb, Y_b,parent, Y_parent,b (unused lanes: 0)
+  unsigned long long rmask; // lanes of my row
+
+  __device__ __forceinline__ void init(cptr_t C) {
+    typedef Layout<T> L;
+    const int lane = threadIdx.x & 63;
+    const unsigned w0 = T::T_ROW_LP[lane & 15];
+    b = int(w0 & 0x7Fu);
+    lane_bus = b > 0;
+    height = int((w0 >> 7) & 0x7Fu) - 1;
+    depth = int((w0 >> 14) & 0x7Fu) - 1;
+    rmask = 0xFFFFull << (lane & 48);
+    ybb_r = ybb_i = ybp_r = ybp_i = ypb_r = ypb_i = 0.0;
+    if (lane_bus) {
+      ybb_r = C[L::Y_RE + T::T_ZBB[b]]; ybb_i = C[L::Y_IM + T::T_ZBB[b]];
+      ybp_r = C[L::Y_RE + T::T_ZBP[b]]; ybp_i = C[L::Y_IM + T::T_ZBP[b]];
+      ypb_r = C[L::Y_RE + T::T_ZPB[b]]; ypb_i = C[L::Y_IM + T::T_ZPB[b]];
+    }
+  }
+};
+
+// newton_groups with rows for groups: same arguments, same results (rvalid: the row holds a solve, uniform per row).
+template <class T, class JT>
+__device__ __forceinline__ void newton_rows(const RowView<T>& V, bool rvalid, double& vm, double& cs, double& sn, double bus_p,
+                                            double bus_q, int& it, unsigned& tb, unsigned& tn, double tol, int max_iter) {
+  static_assert(T::T_ROW != 0, "codegen.row_plan: the topology has no row layout");
+  const int height = V.height, depth = V.depth;
+  const double ybb_r = V.ybb_r, ybb_i = V.ybb_i, ybp_r = V.ybp_r, ybp_i = V.ybp_i, ypb_r = V.ypb_r, ypb_i = V.ypb_i;
+  const bool isbus = V.lane_bus && rvalid;
+  const unsigned long long busm = __builtin_amdgcn_uicmp(isbus ? 1u : 0u, 0u, ICMP_NE);
+  unsigned long long runm = __builtin_amdgcn_uicmp(rvalid ? 1u : 0u, 0u, ICMP_NE);
+  const unsigned glo = unsigned(V.rmask & busm), ghi = unsigned((V.rmask & busm) >> 32);   // bus lanes of my row
+  tb = 0u; tn = 0u;
+  it -= rvalid ? 1 : 0;        // the first trip only evaluates: its `it += running` is undone here
+  Blk<JT> Sc = Blk<JT>{JT(0), JT(0), JT(0), JT(0)};
+  JT Lr0 = JT(0), Lr1 = JT(0), d0 = JT(0), d1 = JT(0);   // (an unused lane never writes its step: it stays zero)
+  // the voltage of the parent: a bus attached to the slack keeps 1 + 0j, every other bus receives its parent's every trip
+  double vpr = 1.0, vpi = 0.0;
+  // 1.0 in registers of its own for the fused folds (opaque to the compiler: not rematerialised in front of every use)
+  double one = 1.0;
+  asm volatile("" : "+v"(one));
+  const JT onej = JT(one);
+  for (;;) {
+    const double vr = vm * cs, vi = vm * sn;
+    row_points<T, ROW_PAR, 0, T::T_ROW_PAR_N>([&](auto N0, auto B0, auto N1, auto B1, auto N2, auto B2) {
+      row_mov<N0, B0, N1, B1, N2, B2>(vpr, vpi, vr, vi);
+    });
+    // W_bb = conj(Y_bb) vm^2;  P = V_b conj(V_p):  W_bp = conj(Y_bp) P,  W_pb = conj(Y_pb) conj(P)
+    const double m2 = vm * vm;
+    const double wbb_r = ybb_r * m2, wbb_i = -(ybb_i * m2);
+    const double pr = fma(vr, vpr, vi * vpi), pim = fma(vi, vpr, -(vr * vpi));
+    const double wbp_r = fma(ybp_r, pr, ybp_i * pim), wbp_i = fma(ybp_r, pim, -(ybp_i * pr));
+    const double wpb_r = fma(ypb_r, pr, -(ypb_i * pim)), nwpb_i = fma(ypb_r, pim, ypb_i * pr);   // (imaginary part: sign flipped)
+    // S_b = W_bb + W_bp + sum over the children c of W_pb(c)
+    double sr = wbb_r + wbp_r, si = wbb_i + wbp_i;
+    row_points<T, ROW_WS, 0, T::T_ROW_CH_N>([&](auto N0, auto B0, auto N1, auto B1, auto N2, auto B2) {
+      row_wsum<N0, B0, N1, B1, N2, B2>(sr, si, wpb_r, nwpb_i, one);
+    });
+    const double fr = sr - bus_p, fi = si - bus_q;
+    // row-wide stop test (see newton_groups)
+    const unsigned long long badm = __builtin_amdgcn_fcmp(fmax(fabs(fr), fabs(fi)), tol, FCMP_UGT);
+    const unsigned long long nanm = __builtin_amdgcn_fcmp(fr, fi, FCMP_UNO);
+    tb = (unsigned(badm) & glo) | (unsigned(badm >> 32) & ghi);
+    tn = (unsigned(nanm) & glo) | (unsigned(nanm >> 32) & ghi);
+    it += __builtin_amdgcn_inverse_ballot_w64(runm) ? 1 : 0;   // the update applied in the previous trip
+    runm &= __builtin_amdgcn_uicmp(tb, 0u, ICMP_NE) & ~__builtin_amdgcn_uicmp(tn, 0u, ICMP_NE) &
+            __builtin_amdgcn_sicmp(it, max_iter, ICMP_SLT);   // NaN > tol is false, like the reference
+    const bool all_done = runm == 0ull;   // (the loop is left at the END of the trip, see newton_groups)
+
+    // ---- Jacobian blocks: own diagonal and the two couplings with the parent
+    Blk<JT> Dg = Blk<JT>{JT(wbb_i - si), JT(sr + wbb_r), JT(sr - wbb_r), JT(si + wbb_i)};
+    const Blk<JT> Jbp = Blk<JT>{JT(wbp_i), JT(wbp_r), JT(-wbp_r), JT(wbp_i)};
+    const Blk<JT> Jpb = Blk<JT>{JT(-nwpb_i), JT(wpb_r), JT(-wpb_r), JT(-nwpb_i)};
+    JT r0 = JT(fr), r1 = JT(fi);
+    // ---- elimination by height: the folds of a level (every child of height h - 1 into its parent, whatever the parent's
+    // height) by all lanes, then one region for the pivots of the buses of this height
+    constexpr bool L0_FREE = roots_at_height<T>(0) == 0;
+    Blk<JT> Di = Dg;
+    static_for<0, T::T_MAXH + 1>([&](auto H) {
+      constexpr int h = H;
+      if constexpr (h > 0) {
+        row_points<T, ROW_CH, T::T_ROW_CH_OFF[h], T::T_ROW_CH_OFF[h + 1]>([&](auto N0, auto B0, auto N1, auto B1, auto N2, auto B2) {
+          row_fold<N0, B0, N1, B1, N2, B2>(Dg, r0, r1, Sc, Lr0, Lr1, onej);
+        });
+      }
+      const bool at_level = (h == 0 && L0_FREE) ? true : (height == h);
+      if (at_level) {
+        Di = blk_inv_fast(Dg);
+        if constexpr (roots_at_height<T>(h) == 2) {
+          d0 = fm(Di.a, r0, Di.b * r1);
+          d1 = fm(Di.c, r0, Di.d * r1);
+        } else if constexpr (roots_at_height<T>(h) == 1) {
+          if (depth == 0) {
+            d0 = fm(Di.a, r0, Di.b * r1);
+            d1 = fm(Di.c, r0, Di.d * r1);
+          }
+        }
+        if constexpr (h < T::T_MAXH) {
+          const Blk<JT> Lk = blk_mul(Jpb, Di);
+          Sc = blk_mul(Lk, Jbp);
+          Lr0 = fm(Lk.a, r0, Lk.b * r1);
+          Lr1 = fm(Lk.c, r0, Lk.d * r1);
+        }
+      }
+    });
+    // ---- back substitution by depth (Di holds the inverted pivots; the step of a bus attached to the slack was taken in
+    // the region of its pivot).  The parent's step goes straight into the right-hand side of its children: the banks of a
+    // hand-over hold buses of one depth, and r0 / r1 are rebuilt every trip.
+    static_for<1, T::T_MAXD + 1>([&](auto Dd) {
+      constexpr int dd = Dd;
+      row_points<T, ROW_PAR, T::T_ROW_PAR_OFF[dd], T::T_ROW_PAR_OFF[dd + 1]>([&](auto N0, auto B0, auto N1, auto B1, auto N2, auto B2) {
+        row_fma<N0, B0, N1, B1, N2, B2>(r0, r1, d0, d1, Jbp);
+      });
+      if (depth == dd) {
+        const JT a0 = r0, a1 = r1;
+        d0 = fm(Di.a, a0, Di.b * a1);
+        d1 = fm(Di.c, a0, Di.d * a1);
+      }
+    });
+    // ---- update of the running rows (see newton_groups, VPOLY)
+    const bool upd = __builtin_amdgcn_inverse_ballot_w64(runm);
+    const double dth = double(d0);
+    const unsigned long long bigm = __builtin_amdgcn_fcmp(fabs(dth), 0.78, FCMP_UGT) & runm;  // NaN counts
+    double sd_, cd_;
+    if (bigm == 0ull) {
+      sincos_kernel<true>(dth, 0, sd_, cd_);
+    } else {
+      sincos_medium<true>(dth, sd_, cd_);
+      const bool ish = !(fabs(dth) < SINCOS_MEDIUM_MAX);
+      if ((__builtin_amdgcn_uicmp(ish ? 1u : 0u, 0u, ICMP_NE) & runm) != 0ull) {
+        const SinCos r = sincos_huge(dth);
+        sd_ = ish ? r.s : sd_;
+        cd_ = ish ? r.c : cd_;
+      }
+    }
+    if (upd) {
+      vm = fma(-double(d1), fabs(vm), vm);
+      const double t1 = sn * sd_, t2 = cs * sd_;
+      cs = fma3<false>(cs, cd_, t1);
+      sn = fma3<true>(sn, cd_, t2);
+    }
+    if (all_done) break;
+  }
+}
+
+// continue_in_groups with four solves a pass, one per row: the same LDS slots, the same results in st.it / st.diff.
+template <class T, class JT>
+__device__ __forceinline__ void continue_in_rows(cptr_t C, EnvWork<T>& w, PFState<T>& st, bool mine, double tol, int max_iter,
+                                                 double* lds) {
+  typedef Slot<T> S;
+  constexpr int NR = 4, NB = T::NB;
+  static_assert(Shape<T>::NG >= NR, "the hand-over slots of the wavefront hold a solve per row");
+  const int lane = threadIdx.x & 63;
+  const int row = lane >> 4;
+  RowView<T> V;
+  V.init(C);
+  const int b = V.b;
+  const unsigned long long todo = __ballot(mine);
+  const int n_todo = __popcll(todo);
+  const int rank = __popcll(todo & ((1ull << lane) - 1ull));
+  for (int base = 0; base < n_todo; base += NR) {
+    const bool send = mine && rank >= base && rank < base + NR;
+    if (send) {
+      double* s = lds + (rank - base) * S::SIZE;
+      static_for<1, NB>([&](auto I) {
+        constexpr int i = I;
+        s[S::VM + i] = w.vm[i]; s[S::CS + i] = st.cs[i]; s[S::SN + i] = st.sn[i];
+        s[S::P + i] = w.bus_p[i]; s[S::Q + i] = w.bus_q[i];
+      });
+      s[S::IT] = double(st.it);
+    }
+    ANM_WAVE_SYNC();
+    const bool rvalid = base + row < n_todo;           // this row holds a solve
+    const bool isbus = V.lane_bus && rvalid;
+    double vm = 1.0, cs = 1.0, sn = 0.0, bus_p = 0.0, bus_q = 0.0;
+    int it = 0;
+    {
+      const double* s = lds + row * S::SIZE;
+      if (isbus) { vm = s[S::VM + b]; cs = s[S::CS + b]; sn = s[S::SN + b]; bus_p = s[S::P + b]; bus_q = s[S::Q + b]; }
+      if (rvalid) it = int(s[S::IT]);
+    }
+    ANM_WAVE_SYNC();
+    unsigned tb, tn;
+    newton_rows<T, JT>(V, rvalid, vm, cs, sn, bus_p, bus_q, it, tb, tn, tol, max_iter);
+
+    // ---- results back to the owner lanes
+    if (isbus) {
+      double* s = lds + row * S::SIZE;
+      s[S::VM + b] = vm; s[S::CS + b] = cs; s[S::SN + b] = sn;
+      if (b == 1) {
+        s[S::IT] = double(it);
+        s[S::FLAGS] = (tn != 0u) ? NAN : ((tb != 0u) ? INFINITY : 0.0);
+      }
+    }
+    ANM_WAVE_SYNC();
+    if (send) {
+      const double* s = lds + (rank - base) * S::SIZE;
+      static_for<1, NB>([&](auto I) {
+        constexpr int i = I;
+        w.vm[i] = s[S::VM + i]; st.cs[i] = s[S::CS + i]; st.sn[i] = s[S::SN + i];
+        w.vr[i] = w.vm[i] * st.cs[i];   // the iterate's V, as eval_mismatch leaves it (pf_end reads it)
+        w.vi[i] = w.vm[i] * st.sn[i];
+      });
+      st.it = int(s[S::IT]);
+      st.diff = s[S::FLAGS];
       st.active = false;
     }
     ANM_WAVE_SYNC();
+  }
+}
+
+// The collective continuation of a wavefront's handed-over solves, and the ONE place that chooses between rows and groups.
+// Every path gives the same bits, so the choice is what is fastest: a pass lasts as long as its longest solve, and a
+// diverging one runs to max_iter.  Rows take four solves a pass, groups 64 / GRP (eight for the 6-bus feeder) at a longer
+// trip; two passes that each hold a diverging solve double the chain.  rowc (anm_solver_opts.row_continuation):
+//    0  n <= 4 solves: rows.  More: groups up to iteration ANM_MID_CAP_DEFAULT (every converging solve seen needs <= 9),
+//       then the survivors on rows if at most 4 are left, else on groups to the cap;
+//    1  always rows;   -1  never.
+// A topology without a row plan (T_ROW = 0) keeps groups.
+template <class T, class JT, bool ROWS = true>
+__device__ __forceinline__ void continue_collective(cptr_t C, EnvWork<T>& w, PFState<T>& st, bool mine, double tol, int max_iter,
+                                                    int rowc, double* lds) {
+  if constexpr (T::T_ROW == 0 || !ROWS) {
+    continue_in_groups<T, JT>(C, w, st, mine, tol, max_iter, lds);
+  } else {
+    int n = __popcll(__ballot(mine));
+    bool groups = rowc < 0 || (rowc == 0 && n > 4);
+    int cap = (rowc == 0 && ANM_MID_CAP_DEFAULT < max_iter) ? ANM_MID_CAP_DEFAULT : max_iter;
+    while (groups) {
+      continue_in_groups<T, JT>(C, w, st, mine, tol, cap, lds, cap < max_iter);
+      mine = mine && st.active;   // (at the cap: nobody)
+      n = __popcll(__ballot(mine));
+      groups = n > 4;
+      cap = max_iter;
+    }
+    if (n > 0) continue_in_rows<T, JT>(C, w, st, mine, tol, max_iter, lds);
   }
 }
 

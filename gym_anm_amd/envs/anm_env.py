@@ -95,7 +95,7 @@ def check_env_args(K, delta_t, lamb, gamma, observation, aux_bounds, state_bound
 class BatchedANMEnv(GymEnv):
     def __init__(self, network, observation, K, delta_t, gamma, lamb, aux_bounds=None, costs_clipping=None, seed=None,
                  num_envs=1, device="cuda", tol=1e-5, max_iter=100, precision="f64", autoreset=False, series=None,
-                 env_offset=0, impl=None, straggler_after="auto", straggler_mid="auto", handoff_after="auto", track_full=False,
+                 env_offset=0, impl=None, straggler_after="auto", straggler_mid="auto", handoff_after="auto", row_continuation=0, track_full=False,
                  fuse_observation=True, variants=None, env_variant=None, exogenous=None, exo_low=None, exo_high=None, exo_noise=None,
                  exo_corr=None,
                  max_episode_steps=None, episode_stats=False, io_dtype=None, _backend=None):  # fmt: skip
@@ -120,8 +120,8 @@ class BatchedANMEnv(GymEnv):
 
         self.simulator = BatchedSimulator(network, delta_t, lamb, num_envs=num_envs, device=device, tol=tol,
                                           max_iter=max_iter, precision=precision, impl=impl,
-                                          handoff_after=handoff_after, variants=variants, env_variant=env_variant,
-                                          _backend=_backend)  # fmt: skip
+                                          handoff_after=handoff_after, row_continuation=row_continuation, variants=variants,
+                                          env_variant=env_variant, _backend=_backend)  # fmt: skip
         sim = self.simulator
         self.device = sim.device
         check_env_args(K, delta_t, lamb, gamma, observation, aux_bounds, sim.state_bounds)

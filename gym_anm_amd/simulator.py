@@ -145,7 +145,7 @@ def _component_views(sim):
 
 class BatchedSimulator:
     def __init__(self, network, delta_t, lamb, num_envs=1, device="cuda", tol=1e-5, max_iter=100,
-                 precision="f64", impl=None, handoff_after="auto", variants=None, env_variant=None,
+                 precision="f64", impl=None, handoff_after="auto", row_continuation=0, variants=None, env_variant=None,
                  _backend=None):  # fmt: skip
         self.model = NetworkModel(network, delta_t, lamb)
         m = self.model
@@ -176,10 +176,12 @@ class BatchedSimulator:
 
         # handoff_after: Newton iterations a solve spends in its own lane before a still-running (diverging)
         # one continues on a lane group, see anm_solver_opts in include/anm_mi355x.h; None = never
+        # row_continuation: where they continue, anm_solver_opts.row_continuation -- 0: the library's policy, 1: always one
+        # solve per 16-lane row, -1: always one per lane group (same bits either way)
         ho = _lib.HANDOFF_AUTO if handoff_after == "auto" else (_lib.HANDOFF_NEVER if handoff_after is None
                                                                 else int(handoff_after))  # fmt: skip
         self.opts = _lib.SolverOpts(float(tol), int(max_iter), _lib.SOLVE_F32 if precision == "f32" else _lib.SOLVE_F64,
-                                    ho)  # fmt: skip
+                                    ho, int(row_continuation))  # fmt: skip
         self._handle = C.c_void_p()
         desc, self._keep = _lib.network_desc(m)
         with self._device_ctx():

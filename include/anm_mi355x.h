@@ -328,6 +328,13 @@ typedef struct anm_solver_opts {
    * short.  >= 0: hand over after that many iterations; ANM_HANDOFF_NEVER: stay in the lane;
    * ANM_HANDOFF_AUTO: the library's default for the topology. */
   int32_t handoff_after;
+  /* Where the handed-over solves of a wavefront continue (topologies with a row layout, codegen.row_plan -- the 6-bus
+   * feeder has one; every other topology keeps lane groups whatever this says): one solve per 16-lane DPP row, four a
+   * pass, with every hand-over of the Newton trip a single 64-bit row_newbcast instruction, or one solve per lane group
+   * (eight a pass for ANM6) at a longer trip.  Both give the same bits.  0 (what a zero-initialised struct asks for): the
+   * library's policy -- rows when at most 4 solves hand over, else lane groups up to iteration 12 and then rows for
+   * the survivors if at most 4 are left; 1: always rows; -1: never. */
+  int32_t row_continuation;
 } anm_solver_opts;
 #define ANM_HANDOFF_NEVER (-1)
 #define ANM_HANDOFF_AUTO (-2)
@@ -450,6 +457,16 @@ int anm_step_f64(anm_model* m, int64_t num_envs, const double* action, const dou
 int anm_gather_obs_f64(int64_t num_envs, int32_t full_dim, const double* full, int32_t state_dim, int32_t K,
                        const double* state, const uint8_t* terminated, int32_t n_obs, const int32_t* index,
                        const double* scale, const double* low, const double* high, double* obs, void* stream);
+
+/* Test entry point: the 64-bit row_newbcast hand-over helpers of csrc/anm_group.hpp (v_fmac_f64_dpp / v_mov_b64_dpp with a
+ * bank mask) on ONE wavefront.  acc, x: dev [64]; out: dev [10, 64], lane l of row r (a 16-lane row: lanes 16 q .. 16 q + 15;
+ * x[q, N]: x of lane N of l's row; "banks B": on the lanes whose bank -- (l % 16) / 4 -- is set in B, acc[l] elsewhere):
+ *   0: acc + x[q, 5], banks 0x5             1: acc - x[q, 5], banks 0x5
+ *   2: acc - x[q, 0] on bank 0, - x[q, 7] on bank 1, - x[q, 15] on banks 2 and 3 (three pairs in one statement)
+ *   3, 4: x[q, 12], banks 0xA (the move)
+ *   5, 6, 7: acc - x[q, 3], bank 3 (the six-value fold: first, fourth and last value)
+ *   8: (acc - 2 x[q, 9]) - 4 x[q, 9]       9: (acc - 16 x[q, 9]) - 8 x[q, 9], banks 0x3 (the back substitution's two fused steps) */
+int anm_test_row_dpp(const double* acc, const double* x, double* out, void* stream);
 
 /* List-form observation produced INSIDE the step kernel (every kernel family; the list form of
  * anm_env.py:497-521, 562-592): after this call anm_step_f64 writes obs as [E, n_obs] with
