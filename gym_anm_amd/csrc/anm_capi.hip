@@ -165,8 +165,11 @@ __global__ __launch_bounds__(64) void k_test_row_dpp(const double* __restrict__ 
   Blk<double> D{a, a, a, a};
   double r0 = a, r1 = a;
   group::row_fold<3, 0x8>(D, r0, r1, Blk<double>{v, v, v, v}, v, v, one);
-  double b0 = a, b1 = a;
-  group::row_fma<9, 0x3>(b0, b1, v, v, Blk<double>{2.0, 4.0, 16.0, 8.0});
+  // (row_fma takes the two entries of a {ja, jb, -jb, ja} block: a0 = (a - ja v) - jb v of the first call, and of the
+  // second a1 = (a + jb v) - ja v with jb = -16, ja = 8 -- the chain whose first product carries no negation)
+  double b0 = a, b1 = a, u0 = a, u1 = a;
+  group::row_fma<9, 0x3>(b0, u0, v, v, 2.0, 4.0);
+  group::row_fma<9, 0x3>(u1, b1, v, v, 8.0, -16.0);
   out[l] = s0; out[64 + l] = s1; out[128 + l] = t1; out[192 + l] = m0; out[256 + l] = m1;
   out[320 + l] = D.a; out[384 + l] = D.d; out[448 + l] = r1; out[512 + l] = b0; out[576 + l] = b1;
 }

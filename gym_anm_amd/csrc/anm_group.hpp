@@ -242,26 +242,38 @@ constexpr bool child_moves_land_on_parents_or_zero() {
 // that folds the moved value in are one instruction: `D -= x_child` is fmac(D, -x, 1.0) -- the product by 1 is exact, one
 // rounding, the bits of the subtraction -- and `a = fma(-J, p_parent, a)` is fmac(a, -p, J), the same product.
 // Two rules these statements keep, because nothing else does:
-//   * the compiler inserts no wait states in front of inline-asm DPP (a VALU write of a register followed within two wait
-//     states by a DPP read of it is a hazard): every statement begins with its own `s_nop 1`, and no instruction of a
-//     statement reads through DPP what the statement itself wrote;
+//   * the compiler inserts no wait states in front of inline-asm DPP, and a DPP read of a register needs two of them behind
+//     the VALU write of it.  A statement therefore opens with a LEAD of at least two instructions that are no DPP reads, and
+//     no DPP read of a statement follows the write of its source, inside the statement, by fewer than two instructions:
+//     whatever the compiler wrote last in front of the statement is then two instructions away as well.  The lead is the
+//     trip's own arithmetic that stands in front of the hand-over anyway (row_*_lead: the same single v_mul / v_add /
+//     v_fmac the compiler makes of the source expression, the same operands in the same order), so the wait states cost no
+//     issue slot.  Where a hand-over point needs more than one statement, those behind the first (row_mov, row_wsum,
+//     row_fold, row_fma) have no arithmetic left to lead with and open with `s_nop 1`;
 //   * a source lane switched off by EXEC is not read: every lane of the wavefront executes them (asm volatile: not sunk
 //     into a divergent region).
-// One statement serves up to three (source lane, bank mask) pairs of one hand-over point -- they read the same registers --
-// so a point costs one `s_nop 1`, not one per pair.  (N1 / N2 < 0: no such pair.)
+// One statement serves up to four (source lane, bank mask) pairs of one hand-over point -- they read the same registers --
+// so a point has one lead, not one per pair.  (N1 / N2 / N3 < 0: no such pair.)
 // ---------------------------------------------------------------------------------------------
 #define ANM_ROW_CTL(n, b) " row_newbcast:%[" n "] row_mask:0xf bank_mask:%[" b "]\n"
-#define ANM_ROW_IMM [n0] "n"(N0), [b0] "n"(B0), [n1] "n"(N1 < 0 ? 0 : N1), [b1] "n"(B1), [n2] "n"(N2 < 0 ? 0 : N2), [b2] "n"(B2)
+#define ANM_ROW_TPL template <int N0, int B0, int N1 = -1, int B1 = 0, int N2 = -1, int B2 = 0, int N3 = -1, int B3 = 0>
+#define ANM_ROW_IMM                                                                                                    \
+  [n0] "n"(N0), [b0] "n"(B0), [n1] "n"(N1 < 0 ? 0 : N1), [b1] "n"(B1), [n2] "n"(N2 < 0 ? 0 : N2), [b2] "n"(B2),          \
+  [n3] "n"(N3 < 0 ? 0 : N3), [b3] "n"(B3)
 #define ANM_ROW_UNPAR(...) __VA_ARGS__
-#define ANM_ROW_ASM(BODY, OUTS, INS)                                                                                          \
+#define ANM_ROW_ASM_LEAD(LEAD, BODY, OUTS, INS)                                                                               \
   do {                                                                                                                        \
-    if constexpr (N1 < 0) asm volatile("s_nop 1\n" BODY("n0", "b0") : ANM_ROW_UNPAR OUTS : ANM_ROW_UNPAR INS, ANM_ROW_IMM);     \
+    if constexpr (N1 < 0) asm volatile(LEAD BODY("n0", "b0") : ANM_ROW_UNPAR OUTS : ANM_ROW_UNPAR INS, ANM_ROW_IMM);           \
     else if constexpr (N2 < 0)                                                                                                \
-      asm volatile("s_nop 1\n" BODY("n0", "b0") BODY("n1", "b1") : ANM_ROW_UNPAR OUTS : ANM_ROW_UNPAR INS, ANM_ROW_IMM);        \
-    else                                                                                                                      \
-      asm volatile("s_nop 1\n" BODY("n0", "b0") BODY("n1", "b1") BODY("n2", "b2") : ANM_ROW_UNPAR OUTS : ANM_ROW_UNPAR INS,     \
+      asm volatile(LEAD BODY("n0", "b0") BODY("n1", "b1") : ANM_ROW_UNPAR OUTS : ANM_ROW_UNPAR INS, ANM_ROW_IMM);              \
+    else if constexpr (N3 < 0)                                                                                                \
+      asm volatile(LEAD BODY("n0", "b0") BODY("n1", "b1") BODY("n2", "b2") : ANM_ROW_UNPAR OUTS : ANM_ROW_UNPAR INS,           \
                    ANM_ROW_IMM);                                                                                              \
+    else                                                                                                                      \
+      asm volatile(LEAD BODY("n0", "b0") BODY("n1", "b1") BODY("n2", "b2") BODY("n3", "b3") : ANM_ROW_UNPAR OUTS               \
+                   : ANM_ROW_UNPAR INS, ANM_ROW_IMM);                                                                         \
   } while (0)
+#define ANM_ROW_ASM(BODY, OUTS, INS) ANM_ROW_ASM_LEAD("s_nop 1\n", BODY, OUTS, INS)
 #define ANM_ROW_MOV2(n, b) "v_mov_b64_dpp %[d0], %[s0]" ANM_ROW_CTL(n, b) "v_mov_b64_dpp %[d1], %[s1]" ANM_ROW_CTL(n, b)
 #define ANM_ROW_WSUM(n, b) "v_fmac_f64_dpp %[d0], %[s0], %[one]" ANM_ROW_CTL(n, b) "v_fmac_f64_dpp %[d1], -%[s1], %[one]" ANM_ROW_CTL(n, b)
 #define ANM_ROW_FOLD6(F, n, b)                                                                                       \
@@ -271,45 +283,105 @@ constexpr bool child_moves_land_on_parents_or_zero() {
 #define ANM_ROW_FOLD6_F64(n, b) ANM_ROW_FOLD6("f64", n, b)
 #define ANM_ROW_FOLD6_F32(n, b) ANM_ROW_FOLD6("f32", n, b)
 #define ANM_ROW_FMA4(F, n, b)                                                                                        \
-  "v_fmac_" F "_dpp %[a0], -%[p0], %[ja]" ANM_ROW_CTL(n, b) "v_fmac_" F "_dpp %[a1], -%[p0], %[jc]" ANM_ROW_CTL(n, b)  \
-  "v_fmac_" F "_dpp %[a0], -%[p1], %[jb]" ANM_ROW_CTL(n, b) "v_fmac_" F "_dpp %[a1], -%[p1], %[jd]" ANM_ROW_CTL(n, b)
+  "v_fmac_" F "_dpp %[a0], -%[p0], %[ja]" ANM_ROW_CTL(n, b) "v_fmac_" F "_dpp %[a1], %[p0], %[jb]" ANM_ROW_CTL(n, b)   \
+  "v_fmac_" F "_dpp %[a0], -%[p1], %[jb]" ANM_ROW_CTL(n, b) "v_fmac_" F "_dpp %[a1], -%[p1], %[ja]" ANM_ROW_CTL(n, b)
 #define ANM_ROW_FMA4_F64(n, b) ANM_ROW_FMA4("f64", n, b)
 #define ANM_ROW_FMA4_F32(n, b) ANM_ROW_FMA4("f32", n, b)
 
 // (d0, d1) = (s0, s1) of lane N: the parent's voltage
-template <int N0, int B0, int N1 = -1, int B1 = 0, int N2 = -1, int B2 = 0>
-__device__ __forceinline__ void row_mov(double& d0, double& d1, double s0, double s1) {
+ANM_ROW_TPL __device__ __forceinline__ void row_mov(double& d0, double& d1, double s0, double s1) {
   ANM_ROW_ASM(ANM_ROW_MOV2, ([d0] "+v"(d0), [d1] "+v"(d1)), ([s0] "v"(s0), [s1] "v"(s1)));
 }
 // d0 += s0 of lane N, d1 -= s1 of lane N: a child's W product into its parent's sum (`one` holds 1.0)
-template <int N0, int B0, int N1 = -1, int B1 = 0, int N2 = -1, int B2 = 0>
-__device__ __forceinline__ void row_wsum(double& d0, double& d1, double s0, double s1, double one) {
+ANM_ROW_TPL __device__ __forceinline__ void row_wsum(double& d0, double& d1, double s0, double s1, double one) {
   ANM_ROW_ASM(ANM_ROW_WSUM, ([d0] "+v"(d0), [d1] "+v"(d1)), ([s0] "v"(s0), [s1] "v"(s1), [one] "v"(one)));
 }
 // D -= Sc of lane N, (r0, r1) -= (l0, l1) of lane N: a child's Schur complement and reduced right-hand side into its parent
-template <int N0, int B0, int N1 = -1, int B1 = 0, int N2 = -1, int B2 = 0>
-__device__ __forceinline__ void row_fold(Blk<double>& D, double& r0, double& r1, const Blk<double>& Sc, double l0, double l1, double one) {
+ANM_ROW_TPL __device__ __forceinline__ void row_fold(Blk<double>& D, double& r0, double& r1, const Blk<double>& Sc, double l0, double l1, double one) {
   ANM_ROW_ASM(ANM_ROW_FOLD6_F64, ([a] "+v"(D.a), [b] "+v"(D.b), [c] "+v"(D.c), [d] "+v"(D.d), [r0] "+v"(r0), [r1] "+v"(r1)),
               ([sa] "v"(Sc.a), [sb] "v"(Sc.b), [sc] "v"(Sc.c), [sd] "v"(Sc.d), [l0] "v"(l0), [l1] "v"(l1), [one] "v"(one)));
 }
-template <int N0, int B0, int N1 = -1, int B1 = 0, int N2 = -1, int B2 = 0>
-__device__ __forceinline__ void row_fold(Blk<float>& D, float& r0, float& r1, const Blk<float>& Sc, float l0, float l1, float one) {
+ANM_ROW_TPL __device__ __forceinline__ void row_fold(Blk<float>& D, float& r0, float& r1, const Blk<float>& Sc, float l0, float l1, float one) {
   ANM_ROW_ASM(ANM_ROW_FOLD6_F32, ([a] "+v"(D.a), [b] "+v"(D.b), [c] "+v"(D.c), [d] "+v"(D.d), [r0] "+v"(r0), [r1] "+v"(r1)),
               ([sa] "v"(Sc.a), [sb] "v"(Sc.b), [sc] "v"(Sc.c), [sd] "v"(Sc.d), [l0] "v"(l0), [l1] "v"(l1), [one] "v"(one)));
 }
 // a0 = fma(-J.b, p1 of lane N, fma(-J.a, p0 of lane N, a0)), a1 likewise with (J.c, J.d): the parent's Newton step into
-// the right-hand side of the back substitution
-template <int N0, int B0, int N1 = -1, int B1 = 0, int N2 = -1, int B2 = 0>
-__device__ __forceinline__ void row_fma(double& a0, double& a1, double p0, double p1, const Blk<double>& J) {
-  ANM_ROW_ASM(ANM_ROW_FMA4_F64, ([a0] "+v"(a0), [a1] "+v"(a1)),
-              ([p0] "v"(p0), [p1] "v"(p1), [ja] "v"(J.a), [jb] "v"(J.b), [jc] "v"(J.c), [jd] "v"(J.d)));
+// the right-hand side of the back substitution.  The block is a coupling block of the polar Jacobian, {ja, jb, -jb, ja}
+// (Jbp of newton_rows): the statement takes ja and jb alone and forms the product by J.c = -jb as +(p0 * jb) -- the sign
+// of a product is the exclusive or of its factors' signs, the magnitude is the same, so the bits are those of -p0 * -jb.
+ANM_ROW_TPL __device__ __forceinline__ void row_fma(double& a0, double& a1, double p0, double p1, double ja, double jb) {
+  ANM_ROW_ASM(ANM_ROW_FMA4_F64, ([a0] "+v"(a0), [a1] "+v"(a1)), ([p0] "v"(p0), [p1] "v"(p1), [ja] "v"(ja), [jb] "v"(jb)));
 }
-template <int N0, int B0, int N1 = -1, int B1 = 0, int N2 = -1, int B2 = 0>
-__device__ __forceinline__ void row_fma(float& a0, float& a1, float p0, float p1, const Blk<float>& J) {
-  ANM_ROW_ASM(ANM_ROW_FMA4_F32, ([a0] "+v"(a0), [a1] "+v"(a1)),
-              ([p0] "v"(p0), [p1] "v"(p1), [ja] "v"(J.a), [jb] "v"(J.b), [jc] "v"(J.c), [jd] "v"(J.d)));
+ANM_ROW_TPL __device__ __forceinline__ void row_fma(float& a0, float& a1, float p0, float p1, float ja, float jb) {
+  ANM_ROW_ASM(ANM_ROW_FMA4_F32, ([a0] "+v"(a0), [a1] "+v"(a1)), ([p0] "v"(p0), [p1] "v"(p1), [ja] "v"(ja), [jb] "v"(jb)));
 }
-// the pairs [lo, hi) of a hand-over table, three to a statement: f.template operator()<N0, B0, N1, B1, N2, B2>()
+// The first statement of each hand-over point, led by the arithmetic in front of it (the first rule above; the distances
+// are counted in instructions of the statement, lead included):
+//   row_mov_lead    vr = vm cs, vi = vm sn, m2 = vm^2, then the moves: vr is read at distance 2, vi at distance 2
+//   row_wsum_lead   the two additions that start the sums, then the children's products (no DPP read of a lead result)
+//   row_fold_lead   l0 += ka r0, l1 += kc r0 (the fmacs that finish Lr = Lk r), then the six folds: l0 / l1 at distance 5
+//   row_step_lead   p = Di r as mul, fmac (p0), mul, fmac (p1), then the four fused steps, which read p0, p0, p1, p1: each at
+//                   distance 2.  (r0 / r1 are read by the lead and accumulated into by the steps.)
+#define ANM_ROW_LEAD_MOV "v_mul_f64 %[s0], %[vm], %[cs]\nv_mul_f64 %[s1], %[vm], %[sn]\nv_mul_f64 %[m2], %[vm], %[vm]\n"
+#define ANM_ROW_LEAD_WSUM "v_add_f64 %[d0], %[x0], %[y0]\nv_add_f64 %[d1], %[x1], %[y1]\n"
+#define ANM_ROW_LEAD_FOLD(F) "v_fmac_" F " %[l0], %[ka], %[r0]\nv_fmac_" F " %[l1], %[kc], %[r0]\n"
+#define ANM_ROW_LEAD_STEP(F)                                                                                     \
+  "v_mul_" F " %[p0], %[a1], %[ib]\nv_fmac_" F " %[p0], %[ia], %[a0]\nv_mul_" F " %[p1], %[a1], %[id]\nv_fmac_" F  \
+  " %[p1], %[ic], %[a0]\n"
+ANM_ROW_TPL __device__ __forceinline__ void row_mov_lead(double& d0, double& d1, double& vr, double& vi, double& m2, double vm,
+                                                         double cs, double sn) {
+  ANM_ROW_ASM_LEAD(ANM_ROW_LEAD_MOV, ANM_ROW_MOV2, ([d0] "+v"(d0), [d1] "+v"(d1), [s0] "=&v"(vr), [s1] "=&v"(vi), [m2] "=&v"(m2)),
+                   ([vm] "v"(vm), [cs] "v"(cs), [sn] "v"(sn)));
+}
+// (d0, d1) = (x0 + y0, x1 + y1), then row_wsum
+ANM_ROW_TPL __device__ __forceinline__ void row_wsum_lead(double& d0, double& d1, double x0, double y0, double x1, double y1,
+                                                          double s0, double s1, double one) {
+  ANM_ROW_ASM_LEAD(ANM_ROW_LEAD_WSUM, ANM_ROW_WSUM, ([d0] "=&v"(d0), [d1] "=&v"(d1)),
+                   ([x0] "v"(x0), [y0] "v"(y0), [x1] "v"(x1), [y1] "v"(y1), [s0] "v"(s0), [s1] "v"(s1), [one] "v"(one)));
+}
+// (l0, l1) += (ka, kc) r0 -- they come in holding (kb, kd) r1 -- then row_fold
+ANM_ROW_TPL __device__ __forceinline__ void row_fold_lead(Blk<double>& D, double& r0, double& r1, const Blk<double>& Sc, double& l0,
+                                                          double& l1, double ka, double kc, double one) {
+  ANM_ROW_ASM_LEAD(ANM_ROW_LEAD_FOLD("f64"), ANM_ROW_FOLD6_F64,
+                   ([a] "+v"(D.a), [b] "+v"(D.b), [c] "+v"(D.c), [d] "+v"(D.d), [r0] "+v"(r0), [r1] "+v"(r1), [l0] "+v"(l0), [l1] "+v"(l1)),
+                   ([sa] "v"(Sc.a), [sb] "v"(Sc.b), [sc] "v"(Sc.c), [sd] "v"(Sc.d), [ka] "v"(ka), [kc] "v"(kc), [one] "v"(one)));
+}
+ANM_ROW_TPL __device__ __forceinline__ void row_fold_lead(Blk<float>& D, float& r0, float& r1, const Blk<float>& Sc, float& l0,
+                                                          float& l1, float ka, float kc, float one) {
+  ANM_ROW_ASM_LEAD(ANM_ROW_LEAD_FOLD("f32"), ANM_ROW_FOLD6_F32,
+                   ([a] "+v"(D.a), [b] "+v"(D.b), [c] "+v"(D.c), [d] "+v"(D.d), [r0] "+v"(r0), [r1] "+v"(r1), [l0] "+v"(l0), [l1] "+v"(l1)),
+                   ([sa] "v"(Sc.a), [sb] "v"(Sc.b), [sc] "v"(Sc.c), [sd] "v"(Sc.d), [ka] "v"(ka), [kc] "v"(kc), [one] "v"(one)));
+}
+// (p0, p1) = Di (r0, r1) -- a lane's own Newton step -- then row_fma with it: the step of a parent into its children
+ANM_ROW_TPL __device__ __forceinline__ void row_step_lead(double& r0, double& r1, double& p0, double& p1, const Blk<double>& Di,
+                                                          double ja, double jb) {
+  ANM_ROW_ASM_LEAD(ANM_ROW_LEAD_STEP("f64"), ANM_ROW_FMA4_F64, ([a0] "+v"(r0), [a1] "+v"(r1), [p0] "=&v"(p0), [p1] "=&v"(p1)),
+                   ([ia] "v"(Di.a), [ib] "v"(Di.b), [ic] "v"(Di.c), [id] "v"(Di.d), [ja] "v"(ja), [jb] "v"(jb)));
+}
+ANM_ROW_TPL __device__ __forceinline__ void row_step_lead(float& r0, float& r1, float& p0, float& p1, const Blk<float>& Di, float ja,
+                                                          float jb) {
+  ANM_ROW_ASM_LEAD(ANM_ROW_LEAD_STEP("f32"), ANM_ROW_FMA4_F32, ([a0] "+v"(r0), [a1] "+v"(r1), [p0] "=&v"(p0), [p1] "=&v"(p1)),
+                   ([ia] "v"(Di.a), [ib] "v"(Di.b), [ic] "v"(Di.c), [id] "v"(Di.d), [ja] "v"(ja), [jb] "v"(jb)));
+}
+// Two integer statements of the stop test that the compiler makes longer than the instruction set needs:
+//   row_count   it + 1 on the lanes of the wavefront mask m, it elsewhere: ONE add with carry-in (select and add: two)
+//   row_pick    (lo(m) & glo) | (hi(m) & ghi): v_and_b32 + v_and_or_b32 (and, and, or: three)
+// Both depend on wave64: m is a 64-bit lane mask in an SGPR pair (row_count's carry-in and carry-out are such pairs; each
+// VOP3 names one SGPR source, the limit of gfx9).  row_pick makes no assumption about where the lanes of glo / ghi lie; its
+// callers pass a row's bus lanes, which lie in one half of the wavefront, so one of the two terms is zero.
+__device__ __forceinline__ int row_count(int it, unsigned long long m) {
+  int d;
+  unsigned long long carry_out;
+  asm("v_addc_co_u32_e64 %[d], %[co], 0, %[a], %[m]" : [d] "=v"(d), [co] "=s"(carry_out) : [a] "v"(it), [m] "s"(m));
+  return d;
+}
+__device__ __forceinline__ unsigned row_pick(unsigned long long m, unsigned glo, unsigned ghi) {
+  unsigned t, d;
+  asm("v_and_b32 %[t], %[hi], %[ghi]\nv_and_or_b32 %[d], %[lo], %[glo], %[t]"
+      : [t] "=&v"(t), [d] "=v"(d)
+      : [lo] "s"(unsigned(m)), [hi] "s"(unsigned(m >> 32)), [glo] "v"(glo), [ghi] "v"(ghi));
+  return d;
+}
 // the tables of codegen.row_plan: PAR (parent -> children), CH (child -> parent, by level), WS (child -> parent, by parent)
 enum : int { ROW_PAR = 0, ROW_CH = 1, ROW_WS = 2 };
 template <class T, int W>
@@ -320,14 +392,19 @@ template <class T, int W>
 constexpr int row_bank(int i, int hi) {
   return i >= hi ? 0 : (W == ROW_PAR ? T::T_ROW_PAR_BANK[i] : (W == ROW_CH ? T::T_ROW_CH_BANK[i] : T::T_ROW_WS_BANK[i]));
 }
-// the pairs [LO, HI) of table W, three to a statement: f(N0, B0, N1, B1, N2, B2) with integral constants
+// the pairs [LO, HI) of table W, four to a statement: f(FIRST, N0, B0, ... N3, B3) with integral constants (FIRST: the
+// point's first statement, the one that takes the lead)
+#define ANM_ROW_PARAMS auto N0, auto B0, auto N1, auto B1, auto N2, auto B2, auto N3, auto B3
+#define ANM_ROW_ARGS N0, B0, N1, B1, N2, B2, N3, B3
 template <class T, int W, int LO, int HI, class F>
 __device__ __forceinline__ void row_points(F&& f) {
-  static_for<0, (HI - LO + 2) / 3>([&](auto Q) {
-    constexpr int i = LO + 3 * int(Q);
-    f(std::integral_constant<int, row_src<T, W>(i, HI)>{}, std::integral_constant<int, row_bank<T, W>(i, HI)>{},
+  static_for<0, (HI - LO + 3) / 4>([&](auto Q) {
+    constexpr int i = LO + 4 * int(Q);
+    f(std::bool_constant<int(Q) == 0>{},
+      std::integral_constant<int, row_src<T, W>(i, HI)>{}, std::integral_constant<int, row_bank<T, W>(i, HI)>{},
       std::integral_constant<int, row_src<T, W>(i + 1, HI)>{}, std::integral_constant<int, row_bank<T, W>(i + 1, HI)>{},
-      std::integral_constant<int, row_src<T, W>(i + 2, HI)>{}, std::integral_constant<int, row_bank<T, W>(i + 2, HI)>{});
+      std::integral_constant<int, row_src<T, W>(i + 2, HI)>{}, std::integral_constant<int, row_bank<T, W>(i + 2, HI)>{},
+      std::integral_constant<int, row_src<T, W>(i + 3, HI)>{}, std::integral_constant<int, row_bank<T, W>(i + 3, HI)>{});
   });
 }
 
@@ -1002,45 +1079,59 @@ template <class T, class JT>
 __device__ __forceinline__ void newton_rows(const RowView<T>& V, bool rvalid, double& vm, double& cs, double& sn, double bus_p,
                                             double bus_q, int& it, unsigned& tb, unsigned& tn, double tol, int max_iter) {
   static_assert(T::T_ROW != 0, "codegen.row_plan: the topology has no row layout");
-  const int height = V.height, depth = V.depth;
   const double ybb_r = V.ybb_r, ybb_i = V.ybb_i, ybp_r = V.ybp_r, ybp_i = V.ybp_i, ypb_r = V.ypb_r, ypb_i = V.ypb_i;
   const bool isbus = V.lane_bus && rvalid;
   const unsigned long long busm = __builtin_amdgcn_uicmp(isbus ? 1u : 0u, 0u, ICMP_NE);
-  unsigned long long runm = __builtin_amdgcn_uicmp(rvalid ? 1u : 0u, 0u, ICMP_NE);
+  // The running lanes are the BUS lanes of the running rows: every lane computes every level's pivot and every depth's step
+  // (below), so an unused lane carries Inf / NaN in its step (a zero pivot inverted).  Every ballot of the loop is taken
+  // under runm or glo / ghi, both subsets of busm, the update is applied under runm, and the caller reads bus lanes only:
+  // what an unused lane holds reaches no decision and no result.
+  unsigned long long runm = busm;
   const unsigned glo = unsigned(V.rmask & busm), ghi = unsigned((V.rmask & busm) >> 32);   // bus lanes of my row
   tb = 0u; tn = 0u;
   it -= rvalid ? 1 : 0;        // the first trip only evaluates: its `it += running` is undone here
-  Blk<JT> Sc = Blk<JT>{JT(0), JT(0), JT(0), JT(0)};
-  JT Lr0 = JT(0), Lr1 = JT(0), d0 = JT(0), d1 = JT(0);   // (an unused lane never writes its step: it stays zero)
   // the voltage of the parent: a bus attached to the slack keeps 1 + 0j, every other bus receives its parent's every trip
   double vpr = 1.0, vpi = 0.0;
   // 1.0 in registers of its own for the fused folds (opaque to the compiler: not rematerialised in front of every use)
   double one = 1.0;
   asm volatile("" : "+v"(one));
   const JT onej = JT(one);
+  // the loads issued before the loop (the caller's LDS reads, the admittances) are waited for HERE: left to the compiler,
+  // their counters are waited for inside the loop, on every trip
+  __builtin_amdgcn_s_waitcnt(0);
   for (;;) {
-    const double vr = vm * cs, vi = vm * sn;
-    row_points<T, ROW_PAR, 0, T::T_ROW_PAR_N>([&](auto N0, auto B0, auto N1, auto B1, auto N2, auto B2) {
-      row_mov<N0, B0, N1, B1, N2, B2>(vpr, vpi, vr, vi);
-    });
+    // V = vm (cs + j sn) and vm^2 lead the hand-over of the parent's voltage (a tree without one: plain)
+    double vr, vi, m2;
+    if constexpr (T::T_ROW_PAR_N == 0) {
+      vr = vm * cs; vi = vm * sn; m2 = vm * vm;
+    } else {
+      row_points<T, ROW_PAR, 0, T::T_ROW_PAR_N>([&](auto FIRST, ANM_ROW_PARAMS) {
+        if constexpr (FIRST) row_mov_lead<ANM_ROW_ARGS>(vpr, vpi, vr, vi, m2, vm, cs, sn);
+        else row_mov<ANM_ROW_ARGS>(vpr, vpi, vr, vi);
+      });
+    }
     // W_bb = conj(Y_bb) vm^2;  P = V_b conj(V_p):  W_bp = conj(Y_bp) P,  W_pb = conj(Y_pb) conj(P)
-    const double m2 = vm * vm;
     const double wbb_r = ybb_r * m2, wbb_i = -(ybb_i * m2);
     const double pr = fma(vr, vpr, vi * vpi), pim = fma(vi, vpr, -(vr * vpi));
     const double wbp_r = fma(ybp_r, pr, ybp_i * pim), wbp_i = fma(ybp_r, pim, -(ybp_i * pr));
     const double wpb_r = fma(ypb_r, pr, -(ypb_i * pim)), nwpb_i = fma(ypb_r, pim, ypb_i * pr);   // (imaginary part: sign flipped)
     // S_b = W_bb + W_bp + sum over the children c of W_pb(c)
-    double sr = wbb_r + wbp_r, si = wbb_i + wbp_i;
-    row_points<T, ROW_WS, 0, T::T_ROW_CH_N>([&](auto N0, auto B0, auto N1, auto B1, auto N2, auto B2) {
-      row_wsum<N0, B0, N1, B1, N2, B2>(sr, si, wpb_r, nwpb_i, one);
-    });
+    double sr, si;
+    if constexpr (T::T_ROW_CH_N == 0) {
+      sr = wbb_r + wbp_r; si = wbb_i + wbp_i;
+    } else {
+      row_points<T, ROW_WS, 0, T::T_ROW_CH_N>([&](auto FIRST, ANM_ROW_PARAMS) {
+        if constexpr (FIRST) row_wsum_lead<ANM_ROW_ARGS>(sr, si, wbb_r, wbp_r, wbb_i, wbp_i, wpb_r, nwpb_i, one);
+        else row_wsum<ANM_ROW_ARGS>(sr, si, wpb_r, nwpb_i, one);
+      });
+    }
     const double fr = sr - bus_p, fi = si - bus_q;
     // row-wide stop test (see newton_groups)
     const unsigned long long badm = __builtin_amdgcn_fcmp(fmax(fabs(fr), fabs(fi)), tol, FCMP_UGT);
     const unsigned long long nanm = __builtin_amdgcn_fcmp(fr, fi, FCMP_UNO);
-    tb = (unsigned(badm) & glo) | (unsigned(badm >> 32) & ghi);
-    tn = (unsigned(nanm) & glo) | (unsigned(nanm >> 32) & ghi);
-    it += __builtin_amdgcn_inverse_ballot_w64(runm) ? 1 : 0;   // the update applied in the previous trip
+    tb = row_pick(badm, glo, ghi);
+    tn = row_pick(nanm, glo, ghi);
+    it = row_count(it, runm);   // the update applied in the previous trip
     runm &= __builtin_amdgcn_uicmp(tb, 0u, ICMP_NE) & ~__builtin_amdgcn_uicmp(tn, 0u, ICMP_NE) &
             __builtin_amdgcn_sicmp(it, max_iter, ICMP_SLT);   // NaN > tol is false, like the reference
     const bool all_done = runm == 0ull;   // (the loop is left at the END of the trip, see newton_groups)
@@ -1050,51 +1141,50 @@ __device__ __forceinline__ void newton_rows(const RowView<T>& V, bool rvalid, do
     const Blk<JT> Jbp = Blk<JT>{JT(wbp_i), JT(wbp_r), JT(-wbp_r), JT(wbp_i)};
     const Blk<JT> Jpb = Blk<JT>{JT(-nwpb_i), JT(wpb_r), JT(-wpb_r), JT(-nwpb_i)};
     JT r0 = JT(fr), r1 = JT(fi);
+    // ---- The unconditional schedule.  EVERY lane runs every level's pivot code and every depth's step code; no level and
+    // no depth is a region.  A bus still ends with the bits of "pivot at my height, step at my depth":
+    //   * Dg, r0 and r1 of a bus are destinations of folds only at levels up to its own height, and r0 / r1 of a parent's
+    //     step only at its own depth (a bus attached to the slack: never) -- tests/test_row_plan.py, test_row_schedule.py;
+    //   * so what a lane computes BEFORE its level (depth) is overwritten before anybody reads it -- the hand-over of a bus
+    //     of height h is read at level h + 1, its step at depth + 1 -- and what it computes AFTER repeats the same
+    //     operations on unchanged operands.
+    // Hence also one place for the step of the buses attached to the slack: d = Di r at the head of the back substitution,
+    // after the last level, whatever their heights.
     // ---- elimination by height: the folds of a level (every child of height h - 1 into its parent, whatever the parent's
-    // height) by all lanes, then one region for the pivots of the buses of this height
-    constexpr bool L0_FREE = roots_at_height<T>(0) == 0;
-    Blk<JT> Di = Dg;
+    // height), then the pivot.  Lr = Lk r is finished by the lead of the next level's folds (Lr0 / Lr1 hold Lk.b r1, Lk.d r1).
+    Blk<JT> Di = Dg, Sc = Dg;
+    JT Lr0 = JT(0), Lr1 = JT(0), Lka = JT(0), Lkc = JT(0);
     static_for<0, T::T_MAXH + 1>([&](auto H) {
       constexpr int h = H;
       if constexpr (h > 0) {
-        row_points<T, ROW_CH, T::T_ROW_CH_OFF[h], T::T_ROW_CH_OFF[h + 1]>([&](auto N0, auto B0, auto N1, auto B1, auto N2, auto B2) {
-          row_fold<N0, B0, N1, B1, N2, B2>(Dg, r0, r1, Sc, Lr0, Lr1, onej);
+        static_assert(T::T_ROW_CH_OFF[h + 1] > T::T_ROW_CH_OFF[h], "a level above 0 folds the child that makes it one");
+        row_points<T, ROW_CH, T::T_ROW_CH_OFF[h], T::T_ROW_CH_OFF[h + 1]>([&](auto FIRST, ANM_ROW_PARAMS) {
+          if constexpr (FIRST) row_fold_lead<ANM_ROW_ARGS>(Dg, r0, r1, Sc, Lr0, Lr1, Lka, Lkc, onej);
+          else row_fold<ANM_ROW_ARGS>(Dg, r0, r1, Sc, Lr0, Lr1, onej);
         });
       }
-      const bool at_level = (h == 0 && L0_FREE) ? true : (height == h);
-      if (at_level) {
-        Di = blk_inv_fast(Dg);
-        if constexpr (roots_at_height<T>(h) == 2) {
-          d0 = fm(Di.a, r0, Di.b * r1);
-          d1 = fm(Di.c, r0, Di.d * r1);
-        } else if constexpr (roots_at_height<T>(h) == 1) {
-          if (depth == 0) {
-            d0 = fm(Di.a, r0, Di.b * r1);
-            d1 = fm(Di.c, r0, Di.d * r1);
-          }
-        }
-        if constexpr (h < T::T_MAXH) {
-          const Blk<JT> Lk = blk_mul(Jpb, Di);
-          Sc = blk_mul(Lk, Jbp);
-          Lr0 = fm(Lk.a, r0, Lk.b * r1);
-          Lr1 = fm(Lk.c, r0, Lk.d * r1);
-        }
+      Di = blk_inv_fast(Dg);
+      if constexpr (h < T::T_MAXH) {
+        const Blk<JT> Lk = blk_mul(Jpb, Di);
+        Sc = blk_mul(Lk, Jbp);
+        Lr0 = Lk.b * r1; Lka = Lk.a;
+        Lr1 = Lk.d * r1; Lkc = Lk.c;
       }
     });
-    // ---- back substitution by depth (Di holds the inverted pivots; the step of a bus attached to the slack was taken in
-    // the region of its pivot).  The parent's step goes straight into the right-hand side of its children: the banks of a
+    // ---- back substitution by depth (Di holds the inverted pivots).  The step d = Di r of every lane leads the hand-over of
+    // the next depth, where the parents' steps go straight into the right-hand sides of their children: the banks of a
     // hand-over hold buses of one depth, and r0 / r1 are rebuilt every trip.
+    JT d0, d1;
     static_for<1, T::T_MAXD + 1>([&](auto Dd) {
       constexpr int dd = Dd;
-      row_points<T, ROW_PAR, T::T_ROW_PAR_OFF[dd], T::T_ROW_PAR_OFF[dd + 1]>([&](auto N0, auto B0, auto N1, auto B1, auto N2, auto B2) {
-        row_fma<N0, B0, N1, B1, N2, B2>(r0, r1, d0, d1, Jbp);
+      static_assert(T::T_ROW_PAR_OFF[dd + 1] > T::T_ROW_PAR_OFF[dd], "a depth above 0 has a parent's step to receive");
+      row_points<T, ROW_PAR, T::T_ROW_PAR_OFF[dd], T::T_ROW_PAR_OFF[dd + 1]>([&](auto FIRST, ANM_ROW_PARAMS) {
+        if constexpr (FIRST) row_step_lead<ANM_ROW_ARGS>(r0, r1, d0, d1, Di, Jbp.a, Jbp.b);
+        else row_fma<ANM_ROW_ARGS>(r0, r1, d0, d1, Jbp.a, Jbp.b);
       });
-      if (depth == dd) {
-        const JT a0 = r0, a1 = r1;
-        d0 = fm(Di.a, a0, Di.b * a1);
-        d1 = fm(Di.c, a0, Di.d * a1);
-      }
     });
+    d0 = fm(Di.a, r0, Di.b * r1);
+    d1 = fm(Di.c, r0, Di.d * r1);
     // ---- update of the running rows (see newton_groups, VPOLY)
     const bool upd = __builtin_amdgcn_inverse_ballot_w64(runm);
     const double dth = double(d0);
