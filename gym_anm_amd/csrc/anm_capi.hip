@@ -16,9 +16,11 @@
 #include <cstring>
 #include <new>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include ANM_TOPO_HEADER
+#include "anm_devbuf.hpp"
 #include "anm_env_ops.hpp"
 #include "anm_pack.hpp"
 #include "anm_radial.hpp"
@@ -262,8 +264,8 @@ struct Tables {
   bool ok = false;              // the family can serve this model
   int off_obs_lo = 0, off_obs_hi = 0;   // where the observation bounds [SDIM + K] sit in a class's table
   std::vector<std::vector<double>> extra;
-  int* dev_int = nullptr;       // lane-group families: the int tables of the plan (the topology: one copy for all classes)
-  double* dev = nullptr;
+  DevBuf<int> dev_int;          // lane-group families: the int tables of the plan (the topology: one copy for all classes)
+  DevBuf<double> dev;
 };
 
 }  // namespace
@@ -287,7 +289,7 @@ struct anm_model {
   Tables t_thread{h_const, "hipMemcpy(constants)", "hipMalloc(class constants)"};
   Tables t_radial{plan.hd, "hipMemcpy(radial tables)", "hipMalloc(class tables)"};
   Tables t_mesh{mplan.hd, "hipMemcpy(mesh tables)", "hipMalloc(class tables)"};
-  double* d_series = nullptr;   // device exogenous series [NEXO][period]
+  DevBuf<double> d_series;      // device exogenous series [NEXO][period]
   int period = 0;
   int K = 0;
   bool env_set = false;
@@ -296,22 +298,22 @@ struct anm_model {
   unsigned obs_need = 0;
   int obs_row_stride = 0, obs_aux_off = 0;   // compact row layout (only the classes the list reads)
   short obs_cls_off[FC_COUNT] = {0};
-  int32_t* d_obs_index = nullptr;            // [2][n_obs]: compact-layout indices, identity-layout indices
-  double* d_obs_tab = nullptr;               // [3][n_obs]: scale, low, high
+  DevBuf<int32_t> d_obs_index;               // [2][n_obs]: compact-layout indices, identity-layout indices
+  DevBuf<double> d_obs_tab;                  // [3][n_obs]: scale, low, high
   const int32_t* d_env_class = nullptr;       // caller's device array [num_envs] (anm_model_bind_env_classes)
   bool class_per_env = false;                 // the classes do not come in aligned blocks of 64 environments
   uint8_t* d_state_same = nullptr;            // caller's device array [num_envs] (anm_model_bind_state_same)
   double* d_nr_diff = nullptr;                // caller's device array [num_envs] (anm_model_bind_nr_diff)
   const double* d_nr_start = nullptr;         // caller's device array [num_envs, 2 (n_bus - 1)] (anm_model_bind_nr_start)
-  int32_t* d_zero = nullptr;                  // one zero: the class of every environment when no classes are bound
-  double* d_samp = nullptr;                   // [n_dev][6] sampler table (anm_sample_init_state_f64)
+  DevBuf<int32_t> d_zero;                     // one zero: the class of every environment when no classes are bound
+  DevBuf<double> d_samp;                      // [n_dev][6] sampler table (anm_sample_init_state_f64)
   int s_nd = 0, s_nload = 0, s_ngen = 0, s_ndes = 0;
   // uniform exogenous mode and noisy time series (anm_env_config.exo_mode)
   int exo_mode = ANM_EXO_HOST;
   std::vector<double> exo_default;            // [2][n_load + n_gen] MW: loads [p_min, 0], generators [0, p_max]
-  double* d_exo = nullptr;                    // [2][n_load + n_gen] MW: low, high of every unit
-  double* d_noise = nullptr;                  // noisy time series: [n_load + n_gen][period] MW amplitudes
-  double* d_corr = nullptr;                   // ... correlated (anm_env_config_corr): [2][n_load + n_gen] rho, then sqrt(1 - rho^2)
+  DevBuf<double> d_exo;                       // [2][n_load + n_gen] MW: low, high of every unit
+  DevBuf<double> d_noise;                     // noisy time series: [n_load + n_gen][period] MW amplitudes
+  DevBuf<double> d_corr;                      // ... correlated (anm_env_config_corr): [2][n_load + n_gen] rho, then sqrt(1 - rho^2)
   double* exo_z = nullptr;                    // ... the caller's noise states [E][n_load + n_gen] (device; not owned)
   EpisodeIO ep{};                             // episode time limit and statistics (anm_env_config.max_episode_steps / .episode)
   int io_mode = ANM_IO_F64;                   // anm_model_set_io: float32 action / obs / reward arrays
@@ -336,16 +338,22 @@ void set_shape(anm_model* m, int NB, int ND, int NBR, int NLOAD, int NGEN, int N
 
 // device copies of a lane-group plan: its int tables and room for the doubles of class 0
 bool alloc_plan(Tables& t, const std::vector<int>& hi) {
-  return hipMalloc(&t.dev_int, hi.size() * sizeof(int)) == hipSuccess && hipMalloc(&t.dev, t.h0.size() * sizeof(double)) == hipSuccess &&
-         hipMemcpy(t.dev_int, hi.data(), hi.size() * sizeof(int), hipMemcpyHostToDevice) == hipSuccess;
+  return t.dev_int.assign(hi.data(), hi.size()) == hipSuccess && t.dev.alloc(t.h0.size()) == hipSuccess;
+}
+
+// an upload into a buffer of its own; the two error texts: of the allocation, of the copy
+template <class T>
+int stage(DevBuf<T>& b, const T* host, size_t count, size_t pad_bytes, const char* alloc_what, const char* copy_what) {
+  const hipError_t e = b.assign(host, count, pad_bytes);
+  return e == hipSuccess ? 0 : fail_hip(e, b.get() ? copy_what : alloc_what);
 }
 
 int upload(Tables& t) {
   if (!t.ok) return 0;
   const size_t n = t.h0.size();
-  hipError_t e = hipMemcpy(t.dev, t.h0.data(), n * sizeof(double), hipMemcpyHostToDevice);
+  hipError_t e = hipMemcpy(t.dev.get(), t.h0.data(), n * sizeof(double), hipMemcpyHostToDevice);
   for (size_t k = 0; k < t.extra.size() && e == hipSuccess; ++k)
-    e = hipMemcpy(t.dev + (k + 1) * n, t.extra[k].data(), n * sizeof(double), hipMemcpyHostToDevice);
+    e = hipMemcpy(t.dev.get() + (k + 1) * n, t.extra[k].data(), n * sizeof(double), hipMemcpyHostToDevice);
   return e == hipSuccess ? 0 : fail_hip(e, t.copy_what);
 }
 
@@ -358,11 +366,10 @@ int upload_const(anm_model* m) {
 // the device buffer for n_classes consecutive copies (the old one stays when there is no room for the new)
 int reallocate(Tables& t, int n_classes) {
   if (!t.ok) return 0;
-  double* p = nullptr;
-  hipError_t e = hipMalloc(&p, size_t(n_classes) * t.h0.size() * sizeof(double));
+  DevBuf<double> p;
+  hipError_t e = p.alloc(size_t(n_classes) * t.h0.size());
   if (e != hipSuccess) return fail_hip(e, t.alloc_what);
-  hipFree(t.dev);
-  t.dev = p;
+  t.dev = std::move(p);
   return 0;
 }
 
@@ -370,13 +377,6 @@ void set_obs_bounds(Tables& t, int cls, int n, const double* low, const double* 
   if (!t.ok) return;
   std::vector<double>& h = cls == 0 ? t.h0 : t.extra[cls - 1];
   for (int k = 0; k < n; ++k) { h[t.off_obs_lo + k] = low[k]; h[t.off_obs_hi + k] = high[k]; }
-}
-
-void release(Tables& t) {
-  if (t.dev_int) hipFree(t.dev_int);
-  if (t.dev) hipFree(t.dev);
-  t.dev_int = nullptr;
-  t.dev = nullptr;
 }
 
 // the task (anm_model_set_env) in the tables of a lane-group family: its scalars and the observation bounds are the
@@ -395,6 +395,121 @@ void set_lane_group_task(Tables& t, const anm_env_config& cfg, int state_dim) {
   };
   apply(t.h0);
   for (auto& x : t.extra) apply(x);
+}
+
+// The task of anm_model_set_env between its checks and its commit: what the checks resolve from cfg on the host, then
+// (stage_task) the device tables and the episode settings -- all of it apart from the model
+struct Task {
+  int period = 0;
+  const double* amp = nullptr;      // series-noise mode: the caller's amplitude table [nexo][period]
+  std::vector<double> ends;         // drawn modes: [2][nexo] low, high
+  std::vector<double> ar1;          // correlated noise: [2][nexo] rho, then sqrt(1 - rho^2)
+  double* exo_z = nullptr;          // ... the caller's noise states
+  DevBuf<double> series, exo, noise, corr;
+  EpisodeIO ep{};
+};
+
+// the ends of a drawn exogenous mode: the model's defaults overlaid by exo_low / exo_high.  finite: every end must be
+// finite (uniform mode); else merely not NaN (series-noise mode: an infinite end is no clip on that side)
+bool resolve_ends(const anm_model* m, const anm_env_config& cfg, bool finite, std::vector<double>& ends) {
+  const int nexo = m->dims.n_load + m->dims.n_gen;
+  ends = m->exo_default;
+  for (int k = 0; k < nexo; ++k) {
+    if (cfg.exo_low) ends[k] = cfg.exo_low[k];
+    if (cfg.exo_high) ends[nexo + k] = cfg.exo_high[k];
+    if (finite && !(std::isfinite(ends[k]) && std::isfinite(ends[nexo + k]))) return false;
+    if (!(ends[k] <= ends[nexo + k])) return false;   // (NaN fails the comparison)
+  }
+  return true;
+}
+
+int check_episode(const anm_model* m, const anm_env_config& cfg) {
+  if (cfg.tail < ANM_ENV_TAIL_EPISODE) return 0;   // (a struct that ends at exo_high: nothing behind it is read)
+  if (cfg.max_episode_steps < 0) return fail("anm_model_set_env: max_episode_steps must not be negative (0 = no limit)");
+  if (cfg.max_episode_steps == 0 && !cfg.episode) return 0;
+  if (m->has_view)
+    return fail("anm_model_set_env: an episode time limit or episode buffers do not go with a bound batch view (anm_model_bind_view)");
+  if (const anm_episode_buffers* b = cfg.episode) {
+    if ((b->ep_disc_return == nullptr) != (b->ep_discount == nullptr))
+      return fail("anm_model_set_env: ep_disc_return and ep_discount go together");
+    if ((b->last_return && !b->ep_return) || (b->last_disc_return && !b->ep_disc_return))
+      return fail("anm_model_set_env: last_return needs ep_return and last_disc_return needs ep_disc_return");
+  }
+  return 0;
+}
+
+// anm_model_set_env, part 1: every rule that can refuse the task.  Reads cfg and the model, writes t alone
+int check_task(const anm_model* m, const anm_env_config& cfg, Task& t) {
+  if (cfg.K < 0 || cfg.K > radial::KMAX) return fail("K (number of aux variables) must be in [0, 8]");
+  static_assert(int(Layout<Topo>::KMAX) == int(radial::KMAX));   // (the one bound pack_env checks itself)
+  const bool has_series = cfg.series && cfg.period > 0;
+  if (has_series && cfg.K != 1) return fail("series mode needs exactly K = 1 auxiliary variable (the time index)");
+  t.period = has_series ? cfg.period : 0;
+  if (cfg.tail < ANM_ENV_TAIL_NONE || cfg.tail > ANM_ENV_TAIL_CORR) return fail("anm_model_set_env: unknown value of tail");
+  if (cfg.tail == ANM_ENV_TAIL_CORR && cfg.exo_mode != ANM_EXO_SERIES_NOISE)
+    return fail("anm_model_set_env: correlated noise (tail = ANM_ENV_TAIL_CORR, an anm_env_config_corr) needs exo_mode = ANM_EXO_SERIES_NOISE");
+  const int nexo = m->dims.n_load + m->dims.n_gen;
+  const bool classes = m->n_classes() > 1 || m->d_env_class, no_defaults = int(m->exo_default.size()) != 2 * nexo;
+  if (cfg.exo_mode == ANM_EXO_SERIES_NOISE) {
+    // noisy time series: the series of series mode, an amplitude table beside it and clip ends (gym_anm_amd/rng.py)
+    if (cfg.K != 1) return fail("anm_model_set_env: the series-noise mode needs exactly K = 1 auxiliary variable (the time index)");
+    if (t.period <= 0) return fail("anm_model_set_env: the series-noise mode needs a series (series, period)");
+    t.amp = cfg.tail >= ANM_ENV_TAIL_NOISE ? reinterpret_cast<const anm_env_config_noise&>(cfg).exo_noise : nullptr;
+    if (!t.amp)
+      return fail("anm_model_set_env: the series-noise mode needs the amplitude table (an anm_env_config_noise: tail = ANM_ENV_TAIL_NOISE and exo_noise)");
+    if (classes) return fail("anm_model_set_env: the series-noise mode does not take parameter classes");
+    if (m->has_view) return fail("anm_model_set_env: the series-noise mode does not go with a bound batch view (anm_model_bind_view)");
+    if (no_defaults) return fail("anm_model_set_env: no default ends for the series-noise mode");
+    for (size_t k = 0, cells = size_t(nexo) * size_t(t.period); k < cells; ++k)
+      if (!std::isfinite(t.amp[k]) || t.amp[k] < 0.0)
+        return fail("anm_model_set_env: the amplitudes of the series-noise mode must be finite and >= 0");
+    if (!resolve_ends(m, cfg, false, t.ends))
+      return fail("anm_model_set_env: the clip ends of the series-noise mode must not be NaN, with exo_low <= exo_high");
+    if (cfg.tail == ANM_ENV_TAIL_CORR) {
+      // correlated noise: the AR(1) tables, both from the host (the kernels take no square root), and the caller's states
+      const anm_env_config_corr& cc = reinterpret_cast<const anm_env_config_corr&>(cfg);
+      if (!cc.exo_rho || !cc.exo_innov || !cc.exo_z)
+        return fail("anm_model_set_env: correlated noise needs exo_rho, exo_innov and exo_z (anm_env_config_corr): none may be NULL");
+      t.ar1.resize(size_t(2 * nexo));
+      for (int k = 0; k < nexo; ++k) {
+        const double r = cc.exo_rho[k], c = cc.exo_innov[k];
+        if (!std::isfinite(r) || !(r >= 0.0 && r < 1.0)) return fail("anm_model_set_env: exo_rho must be finite and in [0, 1)");
+        if (!std::isfinite(c) || !(c > 0.0 && c <= 1.0)) return fail("anm_model_set_env: exo_innov must be finite and in (0, 1]");
+        t.ar1[k] = r;
+        t.ar1[nexo + k] = c;
+      }
+      t.exo_z = cc.exo_z;
+    }
+  } else if (cfg.exo_mode != ANM_EXO_HOST) {
+    if (cfg.exo_mode != ANM_EXO_UNIFORM) return fail("anm_model_set_env: unknown exo_mode");
+    if (cfg.K != 1) return fail("anm_model_set_env: the uniform exogenous mode needs exactly K = 1 auxiliary variable (the step index)");
+    if (t.period > 0) return fail("anm_model_set_env: the uniform exogenous mode and a series do not go together");
+    if (classes) return fail("anm_model_set_env: the uniform exogenous mode does not take parameter classes");
+    if (no_defaults) return fail("anm_model_set_env: no default ends for the uniform exogenous mode");
+    if (!resolve_ends(m, cfg, true, t.ends))
+      return fail("anm_model_set_env: the ends of the uniform exogenous mode must be finite with exo_low <= exo_high");
+  }
+  return check_episode(m, cfg);
+}
+
+// anm_model_set_env, part 2: the device tables of a task that passed, and its episode settings, all into t
+int stage_task(const anm_model* m, const anm_env_config& cfg, Task& t) {
+  const size_t cells = size_t(m->dims.n_load + m->dims.n_gen) * size_t(t.period);
+  int rc = 0;
+  if (t.period > 0 && (rc = stage(t.series, cfg.series, cells, 0, "hipMalloc(series)", "hipMemcpy(series)"))) return rc;
+  if (!t.ends.empty() && (rc = stage(t.exo, t.ends.data(), t.ends.size(), 8, "hipMalloc(exo ends)", "hipMemcpy(exo ends)"))) return rc;
+  if (t.amp && (rc = stage(t.noise, t.amp, cells, 0, "hipMalloc(exo noise)", "hipMemcpy(exo noise)"))) return rc;
+  if (!t.ar1.empty() && (rc = stage(t.corr, t.ar1.data(), t.ar1.size(), 8, "hipMalloc(exo corr)", "hipMemcpy(exo corr)"))) return rc;
+  if (cfg.tail >= ANM_ENV_TAIL_EPISODE && (cfg.max_episode_steps > 0 || cfg.episode)) {
+    EpisodeIO& ep = t.ep;
+    if (const anm_episode_buffers* b = cfg.episode)
+      ep = EpisodeIO{0, 0, 0.0, b->truncated, b->ep_return, b->ep_disc_return, b->ep_discount, b->last_return, b->last_disc_return,
+                     b->last_length, b->episodes_done};
+    ep.max_steps = cfg.max_episode_steps;
+    ep.gamma = cfg.gamma;
+    ep.on = (ep.max_steps > 0 || ep.truncated || ep.ret || ep.disc_ret || ep.last_len || ep.n_done) ? 1 : 0;
+  }
+  return 0;
 }
 
 // the tables of parameter class k for a lane-group family: its plan is the model's own but for the numbers
@@ -425,7 +540,7 @@ int by_precision(int precision, F&& f) {
 }
 
 ClassSel class_sel(const anm_model* m, const Tables& t) {
-  if (!m->d_env_class) return ClassSel{m->d_zero, 0, 0, 0};
+  if (!m->d_env_class) return ClassSel{m->d_zero.get(), 0, 0, 0};
   return ClassSel{m->d_env_class, int(t.h0.size()), 1, m->class_per_env ? 1 : 0};
 }
 
@@ -457,7 +572,7 @@ int launch_mesh(anm_model* m, int precision, int64_t n, hipStream_t s, const rad
                 : !L.tables_in_lds    ? mesh_kernel<JT, false, 2, false>(pg)
                 : L.simd_waves == 3   ? mesh_kernel<JT, false, 3>(pg)
                                       : mesh_kernel<JT, false>(pg);
-    return launch("launch k_mesh", kern, grid, threads, L.lds, s, d, m->t_mesh.dev_int, m->t_mesh.dev, io, so, n, cs);
+    return launch("launch k_mesh", kern, grid, threads, L.lds, s, d, m->t_mesh.dev_int.get(), m->t_mesh.dev.get(), io, so, n, cs);
   });
 }
 
@@ -477,7 +592,7 @@ int launch_radial(anm_model* m, int precision, int64_t n, hipStream_t s, const r
   const ClassSel cs = class_sel(m, m->t_radial);
   const size_t obs_lds = (io.mode == 2 && io.e.n_obs > 0) ? radial_obs_lds_bytes(m) : 0;   // rows of a list-form observation
   auto go = [&](auto kern) {
-    return launch("launch k_radial", kern, grid, 64, obs_lds, s, m->plan.d, m->t_radial.dev_int, m->t_radial.dev, io, so, n, cs);
+    return launch("launch k_radial", kern, grid, 64, obs_lds, s, m->plan.d, m->t_radial.dev_int.get(), m->t_radial.dev.get(), io, so, n, cs);
   };
   return by_precision(precision, [&](auto jt) {
     using JT = decltype(jt);
@@ -516,6 +631,46 @@ SolverOpts solver(const anm_solver_opts* o, int& precision) {
   return s;
 }
 
+// the dense Y_bus of a generic model (the compiled topology has it from pack_constants)
+void dense_ybus(const anm_network_desc& desc, std::vector<cplx>& ybus) {
+  const int NB = desc.n_bus;
+  ybus.assign(size_t(NB) * NB, cplx(0, 0));
+  for (int b = 0; b < desc.n_branch; ++b) {
+    const int f = desc.br_from[b], t = desc.br_to[b];
+    const cplx ys(desc.br_series[2 * b], desc.br_series[2 * b + 1]), sh(desc.br_shunt[2 * b], desc.br_shunt[2 * b + 1]);
+    const cplx tap(desc.br_tap[2 * b], desc.br_tap[2 * b + 1]);
+    ybus[f * NB + t] = -ys / std::conj(tap);
+    ybus[t * NB + f] = -ys / tap;
+    ybus[f * NB + f] += (ys + sh) / (std::abs(tap) * std::abs(tap));
+    ybus[t * NB + t] += ys + sh;
+  }
+}
+
+// the table of the stand-alone sampler (class 0) and the default ends of the drawn exogenous modes
+int set_sampler_tables(anm_model* m, const anm_network_desc& desc) {
+  std::vector<double> tab(size_t(6) * desc.n_dev, 0.0);
+  m->s_nd = desc.n_dev;
+  for (int k = 0; k < desc.n_dev; ++k) {
+    const int t = desc.dev_type[k];
+    int slot = -1;
+    if (t == DEV_LOAD) slot = m->s_nload++;
+    else if (t == DEV_CLASSICAL || t == DEV_RENEWABLE) slot = m->s_ngen++;
+    else if (t == DEV_STORAGE) slot = m->s_ndes++;
+    double* o = &tab[6 * size_t(k)];
+    o[0] = t; o[1] = slot; o[2] = desc.dev_qmin[k]; o[3] = desc.dev_qmax[k];
+    o[4] = t == DEV_STORAGE ? desc.dev_soc_min[k] : 0.0; o[5] = t == DEV_STORAGE ? desc.dev_soc_max[k] : 0.0;
+  }
+  // default ends of the uniform exogenous mode, in MW, by unit (loads by device id, then non-slack generators)
+  const int nexo = m->s_nload + m->s_ngen;
+  m->exo_default.assign(2 * size_t(nexo), 0.0);
+  for (int k = 0; k < desc.n_dev; ++k) {
+    const int t = desc.dev_type[k], slot = int(tab[6 * size_t(k) + 1]);
+    if (t == DEV_LOAD) m->exo_default[slot] = desc.dev_pmin[k] * desc.base_mva;
+    else if (t == DEV_CLASSICAL || t == DEV_RENEWABLE) m->exo_default[nexo + m->s_nload + slot] = desc.dev_pmax[k] * desc.base_mva;
+  }
+  return m->d_samp.assign(tab.data(), tab.size(), 8) == hipSuccess ? 0 : fail("hipMalloc(sampler table)");
+}
+
 inline unsigned grid_for(int64_t n) { return unsigned((n + BLOCK - 1) / BLOCK); }
 
 }  // namespace
@@ -536,8 +691,8 @@ int anm_model_create(const anm_network_desc* desc, anm_model** out) {
   if (!desc || !out) return fail("anm_model_create: null argument");
   anm_model* m = new (std::nothrow) anm_model();
   if (!m) return fail("out of host memory");
-  auto give_up = [&](int rc) {   // (every way out but the last: what was allocated so far goes the way of a finished model)
-    anm_model_destroy(m);
+  auto give_up = [&](int rc) {   // (every way out but the last: what was allocated so far goes with the model)
+    delete m;
     return rc;
   };
   std::string err, err_topo;
@@ -556,7 +711,7 @@ int anm_model_create(const anm_network_desc* desc, anm_model** out) {
       hipError_t a2 = hipFuncSetAttribute((const void*)k_step_general<double>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
       if (a1 != hipSuccess || a2 != hipSuccess) return give_up(fail_hip(a1 != hipSuccess ? a1 : a2, "k_step_general: LDS size attribute"));
     }
-    hipError_t e = hipMalloc(&m->t_thread.dev, m->h_const.size() * sizeof(double));
+    hipError_t e = m->t_thread.dev.alloc(m->h_const.size());
     if (e != hipSuccess) return give_up(fail_hip(e, "hipMalloc(constants)"));
   }
   if (radial::is_radial(*desc) && radial::build_plan(*desc, m->plan, err) && alloc_plan(m->t_radial, m->plan.hi)) {
@@ -608,65 +763,17 @@ int anm_model_create(const anm_network_desc* desc, anm_model** out) {
     g_err = err_topo;
     return give_up(-3);
   }
-  if (!m->t_thread.ok) {  // generic model: dense Y_bus for diagnostics
-    const int NB = desc->n_bus;
-    m->ybus.assign(size_t(NB) * NB, cplx(0, 0));
-    for (int b = 0; b < desc->n_branch; ++b) {
-      const int f = desc->br_from[b], t = desc->br_to[b];
-      const cplx ys(desc->br_series[2 * b], desc->br_series[2 * b + 1]), sh(desc->br_shunt[2 * b], desc->br_shunt[2 * b + 1]);
-      const cplx tap(desc->br_tap[2 * b], desc->br_tap[2 * b + 1]);
-      m->ybus[f * NB + t] = -ys / std::conj(tap);
-      m->ybus[t * NB + f] = -ys / tap;
-      m->ybus[f * NB + f] += (ys + sh) / (std::abs(tap) * std::abs(tap));
-      m->ybus[t * NB + t] += ys + sh;
-    }
-  }
+  if (!m->t_thread.ok) dense_ybus(*desc, m->ybus);   // generic model: for diagnostics
   int rc = upload_const(m);
-  if (rc == 0 && (hipMalloc(&m->d_zero, sizeof(int32_t)) != hipSuccess || hipMemset(m->d_zero, 0, sizeof(int32_t)) != hipSuccess))
-    rc = fail("hipMalloc(class selector)");
-  if (rc == 0) {   // table of the stand-alone sampler (class 0)
-    std::vector<double> tab(size_t(6) * desc->n_dev, 0.0);
-    m->s_nd = desc->n_dev;
-    for (int k = 0; k < desc->n_dev; ++k) {
-      const int t = desc->dev_type[k];
-      int slot = -1;
-      if (t == DEV_LOAD) slot = m->s_nload++;
-      else if (t == DEV_CLASSICAL || t == DEV_RENEWABLE) slot = m->s_ngen++;
-      else if (t == DEV_STORAGE) slot = m->s_ndes++;
-      double* o = &tab[6 * size_t(k)];
-      o[0] = t; o[1] = slot; o[2] = desc->dev_qmin[k]; o[3] = desc->dev_qmax[k];
-      o[4] = t == DEV_STORAGE ? desc->dev_soc_min[k] : 0.0; o[5] = t == DEV_STORAGE ? desc->dev_soc_max[k] : 0.0;
-    }
-    // default ends of the uniform exogenous mode, in MW, by unit (loads by device id, then non-slack generators)
-    const int nexo = m->s_nload + m->s_ngen;
-    m->exo_default.assign(2 * size_t(nexo), 0.0);
-    for (int k = 0; k < desc->n_dev; ++k) {
-      const int t = desc->dev_type[k], slot = int(tab[6 * size_t(k) + 1]);
-      if (t == DEV_LOAD) m->exo_default[slot] = desc->dev_pmin[k] * desc->base_mva;
-      else if (t == DEV_CLASSICAL || t == DEV_RENEWABLE) m->exo_default[nexo + m->s_nload + slot] = desc->dev_pmax[k] * desc->base_mva;
-    }
-    if (hipMalloc(&m->d_samp, tab.size() * sizeof(double) + 8) != hipSuccess ||
-        hipMemcpy(m->d_samp, tab.data(), tab.size() * sizeof(double), hipMemcpyHostToDevice) != hipSuccess)
-      rc = fail("hipMalloc(sampler table)");
-  }
+  const int32_t zero = 0;
+  if (rc == 0 && m->d_zero.assign(&zero, 1) != hipSuccess) rc = fail("hipMalloc(class selector)");
+  if (rc == 0) rc = set_sampler_tables(m, *desc);
   if (rc) return give_up(rc);
   *out = m;
   return 0;
 }
 
-void anm_model_destroy(anm_model* m) {
-  if (!m) return;
-  for (Tables* t : m->tables()) release(*t);
-  if (m->d_series) hipFree(m->d_series);
-  if (m->d_zero) hipFree(m->d_zero);
-  if (m->d_samp) hipFree(m->d_samp);
-  if (m->d_exo) hipFree(m->d_exo);
-  if (m->d_noise) hipFree(m->d_noise);
-  if (m->d_corr) hipFree(m->d_corr);
-  if (m->d_obs_index) hipFree(m->d_obs_index);
-  if (m->d_obs_tab) hipFree(m->d_obs_tab);
-  delete m;
-}
+void anm_model_destroy(anm_model* m) { delete m; }
 
 int anm_model_dims(const anm_model* m, anm_dims* out) {
   if (!m || !out) return fail("anm_model_dims: null argument");
@@ -686,142 +793,29 @@ int anm_model_full_layout(const anm_model* m, anm_full_layout* o) {
 
 int anm_model_set_env(anm_model* m, const anm_env_config* cfg) {
   if (!m || !cfg) return fail("anm_model_set_env: null argument");
-  std::string err;
-  if (cfg->K < 0 || cfg->K > radial::KMAX) return fail("K (number of aux variables) must be in [0, 8]");
-  if (m->t_thread.ok && !pack_env<Topo>(*cfg, m->h_const, err)) {
-    g_err = err;
-    return -3;
-  }
-  if (m->t_thread.ok)
+  // 1. whatever can refuse the task, 2. its device tables, in buffers of their own: the model is untouched so far
+  Task t;
+  if (int rc = check_task(m, *cfg, t)) return rc;
+  if (int rc = stage_task(m, *cfg, t)) return rc;
+  // 3. commit
+  if (m->t_thread.ok) {
+    std::string err;   // (pack_env refuses nothing but the K that check_task has passed)
+    pack_env<Topo>(*cfg, m->h_const, err);
     for (auto& xc : m->t_thread.extra) pack_env<Topo>(*cfg, xc, err);
-  m->K = cfg->K;
+  }
+  // (a known difference: where obs_low / obs_high are NULL the lane-group tables keep their old observation bounds,
+  // the thread tables fall back to -inf / +inf)
   set_lane_group_task(m->t_radial, *cfg, m->dims.state_base_dim + cfg->K);
   set_lane_group_task(m->t_mesh, *cfg, m->dims.state_base_dim + cfg->K);
-  if (m->d_series) {
-    hipFree(m->d_series);
-    m->d_series = nullptr;
-  }
-  m->period = 0;
-  if (cfg->series && cfg->period > 0) {
-    if (cfg->K != 1) return fail("series mode needs exactly K = 1 auxiliary variable (the time index)");
-    const size_t bytes = sizeof(double) * size_t(m->dims.n_load + m->dims.n_gen) * size_t(cfg->period);
-    hipError_t e = hipMalloc(&m->d_series, bytes ? bytes : 8);
-    if (e != hipSuccess) return fail_hip(e, "hipMalloc(series)");
-    e = hipMemcpy(m->d_series, cfg->series, bytes, hipMemcpyHostToDevice);
-    if (e != hipSuccess) return fail_hip(e, "hipMemcpy(series)");
-    m->period = cfg->period;
-  }
-  m->exo_mode = ANM_EXO_HOST;
-  if (m->d_noise) {
-    hipFree(m->d_noise);
-    m->d_noise = nullptr;
-  }
-  if (m->d_corr) {
-    hipFree(m->d_corr);
-    m->d_corr = nullptr;
-  }
-  m->exo_z = nullptr;
-  if (cfg->tail != ANM_ENV_TAIL_NONE && cfg->tail != ANM_ENV_TAIL_EPISODE && cfg->tail != ANM_ENV_TAIL_NOISE &&
-      cfg->tail != ANM_ENV_TAIL_CORR)
-    return fail("anm_model_set_env: unknown value of tail");
-  if (cfg->tail == ANM_ENV_TAIL_CORR && cfg->exo_mode != ANM_EXO_SERIES_NOISE)
-    return fail("anm_model_set_env: correlated noise (tail = ANM_ENV_TAIL_CORR, an anm_env_config_corr) needs exo_mode = ANM_EXO_SERIES_NOISE");
-  if (cfg->exo_mode == ANM_EXO_SERIES_NOISE) {
-    // noisy time series: the series of series mode, an amplitude table beside it and clip ends (gym_anm_amd/rng.py)
-    if (cfg->K != 1) return fail("anm_model_set_env: the series-noise mode needs exactly K = 1 auxiliary variable (the time index)");
-    if (m->period <= 0) return fail("anm_model_set_env: the series-noise mode needs a series (series, period)");
-    const double* amp = cfg->tail >= ANM_ENV_TAIL_NOISE ? reinterpret_cast<const anm_env_config_noise*>(cfg)->exo_noise : nullptr;
-    if (!amp)
-      return fail("anm_model_set_env: the series-noise mode needs the amplitude table (an anm_env_config_noise: tail = ANM_ENV_TAIL_NOISE and exo_noise)");
-    if (m->n_classes() > 1 || m->d_env_class) return fail("anm_model_set_env: the series-noise mode does not take parameter classes");
-    if (m->has_view) return fail("anm_model_set_env: the series-noise mode does not go with a bound batch view (anm_model_bind_view)");
-    const int nexo = m->dims.n_load + m->dims.n_gen;
-    if (int(m->exo_default.size()) != 2 * nexo) return fail("anm_model_set_env: no default ends for the series-noise mode");
-    const size_t cells = size_t(nexo) * size_t(m->period);
-    for (size_t k = 0; k < cells; ++k)
-      if (!std::isfinite(amp[k]) || amp[k] < 0.0)
-        return fail("anm_model_set_env: the amplitudes of the series-noise mode must be finite and >= 0");
-    std::vector<double> ends(m->exo_default);
-    for (int k = 0; k < nexo; ++k) {
-      if (cfg->exo_low) ends[k] = cfg->exo_low[k];
-      if (cfg->exo_high) ends[nexo + k] = cfg->exo_high[k];
-      if (!(ends[k] <= ends[nexo + k]))   // (NaN fails the comparison; infinite ends are allowed: no clip on that side)
-        return fail("anm_model_set_env: the clip ends of the series-noise mode must not be NaN, with exo_low <= exo_high");
-    }
-    hipError_t e = m->d_exo ? hipSuccess : hipMalloc(&m->d_exo, sizeof(double) * size_t(2 * nexo) + 8);
-    if (e != hipSuccess) return fail_hip(e, "hipMalloc(exo ends)");
-    e = hipMemcpy(m->d_exo, ends.data(), sizeof(double) * ends.size(), hipMemcpyHostToDevice);
-    if (e != hipSuccess) return fail_hip(e, "hipMemcpy(exo ends)");
-    e = hipMalloc(&m->d_noise, cells ? sizeof(double) * cells : 8);
-    if (e != hipSuccess) return fail_hip(e, "hipMalloc(exo noise)");
-    e = hipMemcpy(m->d_noise, amp, sizeof(double) * cells, hipMemcpyHostToDevice);
-    if (e != hipSuccess) return fail_hip(e, "hipMemcpy(exo noise)");
-    if (cfg->tail == ANM_ENV_TAIL_CORR) {
-      // correlated noise: the AR(1) tables, both from the host (the kernels take no square root), and the caller's states
-      const anm_env_config_corr* cc = reinterpret_cast<const anm_env_config_corr*>(cfg);
-      if (!cc->exo_rho || !cc->exo_innov || !cc->exo_z)
-        return fail("anm_model_set_env: correlated noise needs exo_rho, exo_innov and exo_z (anm_env_config_corr): none may be NULL");
-      std::vector<double> tab(size_t(2 * nexo));
-      for (int k = 0; k < nexo; ++k) {
-        const double r = cc->exo_rho[k], c = cc->exo_innov[k];
-        if (!std::isfinite(r) || !(r >= 0.0 && r < 1.0)) return fail("anm_model_set_env: exo_rho must be finite and in [0, 1)");
-        if (!std::isfinite(c) || !(c > 0.0 && c <= 1.0)) return fail("anm_model_set_env: exo_innov must be finite and in (0, 1]");
-        tab[k] = r;
-        tab[nexo + k] = c;
-      }
-      e = hipMalloc(&m->d_corr, sizeof(double) * tab.size() + 8);
-      if (e != hipSuccess) return fail_hip(e, "hipMalloc(exo corr)");
-      e = hipMemcpy(m->d_corr, tab.data(), sizeof(double) * tab.size(), hipMemcpyHostToDevice);
-      if (e != hipSuccess) return fail_hip(e, "hipMemcpy(exo corr)");
-      m->exo_z = cc->exo_z;
-    }
-    m->exo_mode = ANM_EXO_SERIES_NOISE;
-  } else if (cfg->exo_mode != ANM_EXO_HOST) {
-    if (cfg->exo_mode != ANM_EXO_UNIFORM) return fail("anm_model_set_env: unknown exo_mode");
-    if (cfg->K != 1) return fail("anm_model_set_env: the uniform exogenous mode needs exactly K = 1 auxiliary variable (the step index)");
-    if (m->period > 0) return fail("anm_model_set_env: the uniform exogenous mode and a series do not go together");
-    if (m->n_classes() > 1 || m->d_env_class) return fail("anm_model_set_env: the uniform exogenous mode does not take parameter classes");
-    const int nexo = m->dims.n_load + m->dims.n_gen;
-    if (int(m->exo_default.size()) != 2 * nexo) return fail("anm_model_set_env: no default ends for the uniform exogenous mode");
-    std::vector<double> ends(m->exo_default);
-    for (int k = 0; k < nexo; ++k) {
-      if (cfg->exo_low) ends[k] = cfg->exo_low[k];
-      if (cfg->exo_high) ends[nexo + k] = cfg->exo_high[k];
-      if (!std::isfinite(ends[k]) || !std::isfinite(ends[nexo + k]) || !(ends[k] <= ends[nexo + k]))
-        return fail("anm_model_set_env: the ends of the uniform exogenous mode must be finite with exo_low <= exo_high");
-    }
-    hipError_t e = m->d_exo ? hipSuccess : hipMalloc(&m->d_exo, sizeof(double) * size_t(2 * nexo) + 8);
-    if (e != hipSuccess) return fail_hip(e, "hipMalloc(exo ends)");
-    e = hipMemcpy(m->d_exo, ends.data(), sizeof(double) * ends.size(), hipMemcpyHostToDevice);
-    if (e != hipSuccess) return fail_hip(e, "hipMemcpy(exo ends)");
-    m->exo_mode = ANM_EXO_UNIFORM;
-  }
-  m->ep = EpisodeIO{};
-  const bool has_ep = cfg->tail >= ANM_ENV_TAIL_EPISODE;   // (a struct that ends at exo_high: nothing behind it is read)
-  if (has_ep && cfg->max_episode_steps < 0) return fail("anm_model_set_env: max_episode_steps must not be negative (0 = no limit)");
-  if (has_ep && (cfg->max_episode_steps > 0 || cfg->episode)) {
-    if (m->has_view)
-      return fail("anm_model_set_env: an episode time limit or episode buffers do not go with a bound batch view (anm_model_bind_view)");
-    EpisodeIO ep{};
-    ep.max_steps = cfg->max_episode_steps;
-    ep.gamma = cfg->gamma;
-    if (const anm_episode_buffers* b = cfg->episode) {
-      if ((b->ep_disc_return == nullptr) != (b->ep_discount == nullptr))
-        return fail("anm_model_set_env: ep_disc_return and ep_discount go together");
-      if ((b->last_return && !b->ep_return) || (b->last_disc_return && !b->ep_disc_return))
-        return fail("anm_model_set_env: last_return needs ep_return and last_disc_return needs ep_disc_return");
-      ep.truncated = b->truncated;
-      ep.ret = b->ep_return;
-      ep.disc_ret = b->ep_disc_return;
-      ep.discount = b->ep_discount;
-      ep.last_ret = b->last_return;
-      ep.last_disc_ret = b->last_disc_return;
-      ep.last_len = b->last_length;
-      ep.n_done = b->episodes_done;
-    }
-    ep.on = (ep.max_steps > 0 || ep.truncated || ep.ret || ep.disc_ret || ep.last_len || ep.n_done) ? 1 : 0;
-    m->ep = ep;
-  }
+  m->d_series = std::move(t.series);
+  m->d_exo = std::move(t.exo);
+  m->d_noise = std::move(t.noise);
+  m->d_corr = std::move(t.corr);
+  m->K = cfg->K;
+  m->period = t.period;
+  m->exo_mode = cfg->exo_mode;
+  m->exo_z = t.exo_z;
+  m->ep = t.ep;
   m->env_set = true;
   return upload_const(m);
 }
@@ -1016,10 +1010,11 @@ int anm_model_obs_fusable(const anm_model* m) {
 int anm_model_set_obs(anm_model* m, int32_t n_obs, const int32_t* index, const double* scale, const double* low,
                       const double* high) {
   if (!m) return fail("anm_model_set_obs: null model");
-  if (m->d_obs_index) { hipFree(m->d_obs_index); m->d_obs_index = nullptr; }
-  if (m->d_obs_tab) { hipFree(m->d_obs_tab); m->d_obs_tab = nullptr; }
-  m->n_obs = 0;
-  if (n_obs <= 0) return 0;   // back to the "state" observation
+  if (n_obs <= 0) {   // back to the "state" observation
+    m->d_obs_index.reset(); m->d_obs_tab.reset(); m->n_obs = 0;
+    return 0;
+  }
+  // (a refused list leaves the one that is set as it was: checks and uploads first, the model last)
   if (!anm_model_obs_fusable(m))
     return fail("anm_model_set_obs: this model cannot gather inside the step kernel (use anm_gather_obs_f64)");
   if (!index || !scale || !low || !high) return fail("anm_model_set_obs: null argument");
@@ -1043,28 +1038,34 @@ int anm_model_set_obs(anm_model* m, int32_t n_obs, const int32_t* index, const d
     if (i < FS) need |= 1u << class_of(i);
     idx[k] = idx[n_obs + k] = i;   // (both halves: the identity layout -- `full` offsets, aux behind them)
   }
+  short cls_off[FC_COUNT] = {0};
+  int aux_off = 0;
   if (thread) {
     // thread family: rows of the compact layout (only the classes the list reads) unless the dump is asked for; the
     // first half of the indices points into those.  The lane-group families gather from the identity layout alone
-    int off = 0;
     for (unsigned c = 0; c < FC_COUNT; ++c) {
-      m->obs_cls_off[c] = short(off);
-      if ((need >> c) & 1u) off += base[c + 1] - base[c];
+      cls_off[c] = short(aux_off);
+      if ((need >> c) & 1u) aux_off += base[c + 1] - base[c];
     }
-    m->obs_aux_off = off;
-    m->obs_row_stride = (off + Layout<Topo>::KMAX) | 1;
     for (int k = 0; k < n_obs; ++k) {
       const int i = index[k];
-      idx[k] = i >= FS ? m->obs_aux_off + (i - FS) : m->obs_cls_off[class_of(i)] + (i - base[class_of(i)]);
+      idx[k] = i >= FS ? aux_off + (i - FS) : cls_off[class_of(i)] + (i - base[class_of(i)]);
     }
   }
   std::vector<double> tab(3 * size_t(n_obs));
   for (int k = 0; k < n_obs; ++k) { tab[k] = scale[k]; tab[n_obs + k] = low[k]; tab[2 * n_obs + k] = high[k]; }
-  hipError_t e = hipMalloc(&m->d_obs_index, idx.size() * sizeof(int32_t));
-  if (e == hipSuccess) e = hipMalloc(&m->d_obs_tab, tab.size() * sizeof(double));
-  if (e == hipSuccess) e = hipMemcpy(m->d_obs_index, idx.data(), idx.size() * sizeof(int32_t), hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipMemcpy(m->d_obs_tab, tab.data(), tab.size() * sizeof(double), hipMemcpyHostToDevice);
+  DevBuf<int32_t> d_index;
+  DevBuf<double> d_tab;
+  hipError_t e = d_index.assign(idx.data(), idx.size());
+  if (e == hipSuccess) e = d_tab.assign(tab.data(), tab.size());
   if (e != hipSuccess) return fail_hip(e, "anm_model_set_obs");
+  if (thread) {
+    std::copy(cls_off, cls_off + FC_COUNT, m->obs_cls_off);
+    m->obs_aux_off = aux_off;
+    m->obs_row_stride = (aux_off + Layout<Topo>::KMAX) | 1;
+  }
+  m->d_obs_index = std::move(d_index);
+  m->d_obs_tab = std::move(d_tab);
   m->obs_need = need;
   m->n_obs = n_obs;
   return 0;
@@ -1121,7 +1122,7 @@ int anm_transition_f64(anm_model* m, int64_t n, const double* p_load, const doub
   return by_precision(prec, [&](auto jt) {
     using JT = decltype(jt);
     auto kern = io.nr_start ? k_transition<JT, true, true> : m->has_view ? k_transition<JT, true> : k_transition<JT, false>;
-    return launch("launch k_transition", kern, grid_for(n), BLOCK, 0, s, (cptr_t)m->t_thread.dev, io, so, n, class_sel(m, m->t_thread), m->view);
+    return launch("launch k_transition", kern, grid_for(n), BLOCK, 0, s, (cptr_t)m->t_thread.dev.get(), io, so, n, class_sel(m, m->t_thread), m->view);
   });
 }
 
@@ -1131,15 +1132,15 @@ static int env_io_of_model(const anm_model* m, const char* who, EnvIO& io) {
   io = EnvIO{};
   io.K = m->K;
   io.exo_mode = m->exo_mode;
-  io.exo_lo = m->d_exo;
-  io.exo_hi = m->exo_mode != ANM_EXO_HOST ? m->d_exo + (m->dims.n_load + m->dims.n_gen) : nullptr;
-  io.exo_noise = m->exo_mode == ANM_EXO_SERIES_NOISE ? m->d_noise : nullptr;
-  if (m->exo_mode == ANM_EXO_SERIES_NOISE && m->d_corr) {
-    io.exo_rho = m->d_corr;
-    io.exo_innov = m->d_corr + (m->dims.n_load + m->dims.n_gen);
+  io.exo_lo = m->d_exo.get();
+  io.exo_hi = m->exo_mode != ANM_EXO_HOST ? m->d_exo.get() + (m->dims.n_load + m->dims.n_gen) : nullptr;
+  io.exo_noise = m->exo_mode == ANM_EXO_SERIES_NOISE ? m->d_noise.get() : nullptr;
+  if (m->exo_mode == ANM_EXO_SERIES_NOISE && m->d_corr.get()) {
+    io.exo_rho = m->d_corr.get();
+    io.exo_innov = m->d_corr.get() + (m->dims.n_load + m->dims.n_gen);
     io.exo_z = m->exo_z;
   }
-  io.series = m->d_series;
+  io.series = m->d_series.get();
   io.period = m->period;
   io.ep = m->ep;
   io.io32 = m->io_mode == ANM_IO_F32 ? 1 : 0;
@@ -1166,7 +1167,7 @@ int anm_reset_f64(anm_model* m, int64_t n, const double* init_state, const uint8
     return fail("anm_reset_f64: the uniform exogenous mode goes with neither a batch view nor parameter classes");
   if (m->exo_mode == ANM_EXO_SERIES_NOISE && (m->has_view || m->d_env_class))
     return fail("anm_reset_f64: the series-noise mode goes with neither a batch view nor parameter classes");
-  if (m->exo_mode == ANM_EXO_SERIES_NOISE && m->d_corr && !reset_count)
+  if (m->exo_mode == ANM_EXO_SERIES_NOISE && m->d_corr.get() && !reset_count)
     return fail("anm_reset_f64: correlated noise needs reset_count (the epoch keys the noise state every reset stores)");
   EnvIO io;
   if (int rc = env_io_of_model(m, "anm_reset_f64", io)) return rc;
@@ -1191,7 +1192,7 @@ int anm_reset_f64(anm_model* m, int64_t n, const double* init_state, const uint8
   if (on_lane_groups(m)) return launch_lane_groups(m, 1, nullptr, &io, prec, n, s, so);
   return by_precision(prec, [&](auto jt) {
     using JT = decltype(jt);
-    return launch("launch k_reset", m->has_view ? k_reset<JT, true> : k_reset<JT, false>, grid_for(n), BLOCK, 0, s, (cptr_t)m->t_thread.dev, io,
+    return launch("launch k_reset", m->has_view ? k_reset<JT, true> : k_reset<JT, false>, grid_for(n), BLOCK, 0, s, (cptr_t)m->t_thread.dev.get(), io,
                   so, n, class_sel(m, m->t_thread), m->view);
   });
 }
@@ -1200,16 +1201,16 @@ int anm_sample_init_state_f64(anm_model* m, int64_t n, uint64_t rng_seed, uint64
                               double* init_state, uint32_t* raw, void* stream) {
   if (!m || !init_state) return fail("anm_sample_init_state_f64: null argument");
   const bool uniform = m->env_set && m->exo_mode == ANM_EXO_UNIFORM;
-  if (!uniform && (!m->env_set || m->period <= 0 || m->K != 1 || !m->d_series))
+  if (!uniform && (!m->env_set || m->period <= 0 || m->K != 1 || !m->d_series.get()))
     return fail("anm_sample_init_state_f64: the model needs a series-mode or uniform-mode task (anm_model_set_env with series or exo_mode, K = 1)");
   if (m->d_env_class) return fail("anm_sample_init_state_f64: not while parameter classes are bound (the table is class 0's)");
   if (n <= 0) return 0;
   const int n_blocks = 1 + (m->s_ngen + m->s_ndes + 1) / 2;
   const bool noisy = m->exo_mode == ANM_EXO_SERIES_NOISE;
-  const double* exo_lo = (uniform || noisy) ? m->d_exo : nullptr;
+  const double* exo_lo = (uniform || noisy) ? m->d_exo.get() : nullptr;
   return launch("launch k_sample_init_state", k_sample_init_state, unsigned((n + 255) / 256), 256, 0, static_cast<hipStream_t>(stream), n,
-                m->s_nd, m->s_nload, m->s_ngen, m->s_ndes, m->d_samp, (const double*)m->d_series, m->period, rng_seed, env_offset,
-                (const int32_t*)reset_count, init_state, raw, n_blocks, exo_lo, (const double*)(noisy ? m->d_noise : nullptr));
+                m->s_nd, m->s_nload, m->s_ngen, m->s_ndes, m->d_samp.get(), (const double*)m->d_series.get(), m->period, rng_seed, env_offset,
+                (const int32_t*)reset_count, init_state, raw, n_blocks, exo_lo, (const double*)(noisy ? m->d_noise.get() : nullptr));
 }
 
 static int make_step_io(anm_model* m, const double* action, const double* exo, const double* aux_next, double* soc,
@@ -1279,19 +1280,19 @@ static int make_step_io(anm_model* m, const double* action, const double* exo, c
     for (unsigned cc = 0; cc < FC_COUNT; ++cc)
       io.cls_off[cc] = ident ? short(full_class_base<Topo>(cc)) : m->obs_cls_off[cc];
     if (m->n_obs > 0) {
-      io.obs_index = m->d_obs_index + (ident ? m->n_obs : 0);
-      io.obs_scale = m->d_obs_tab;
-      io.obs_lo = m->d_obs_tab + m->n_obs;
-      io.obs_hi = m->d_obs_tab + 2 * m->n_obs;
+      io.obs_index = m->d_obs_index.get() + (ident ? m->n_obs : 0);
+      io.obs_scale = m->d_obs_tab.get();
+      io.obs_lo = m->d_obs_tab.get() + m->n_obs;
+      io.obs_hi = m->d_obs_tab.get() + 2 * m->n_obs;
     }
   }
   if (m->impl != ANM_IMPL_THREAD && m->n_obs > 0) {   // lane-group families: identity layout (see anm_model_set_obs)
     io.n_obs = m->n_obs;
     io.obs_need = m->obs_need;
-    io.obs_index = m->d_obs_index;
-    io.obs_scale = m->d_obs_tab;
-    io.obs_lo = m->d_obs_tab + m->n_obs;
-    io.obs_hi = m->d_obs_tab + 2 * m->n_obs;
+    io.obs_index = m->d_obs_index.get();
+    io.obs_scale = m->d_obs_tab.get();
+    io.obs_lo = m->d_obs_tab.get() + m->n_obs;
+    io.obs_hi = m->d_obs_tab.get() + 2 * m->n_obs;
   }
   io.ws = nullptr;
   if (ws && ws->buf && m->t_thread.ok && !m->d_env_class) {  // (the straggler launch packs records of all blocks together)
@@ -1320,7 +1321,7 @@ static int launch_step(anm_model* m, const EnvIO& io_in, int64_t n, const anm_so
     if (int rc = clear_state_same()) return rc;
     return launch_lane_groups(m, 2, nullptr, &io, prec, n, s, so);
   }
-  const cptr_t C = (cptr_t)m->t_thread.dev;
+  const cptr_t C = (cptr_t)m->t_thread.dev.get();
   const unsigned grid = grid_for(n);
   if (m->has_view) {
     // a batch view: per-lane rows (the coalesced-row kernels need 64 consecutive environments)

@@ -36,6 +36,7 @@ from .. import _lib
 from .. import episode as _episode
 from .. import errors as E
 from .. import io_dtype as _io
+from .. import rng as _rng
 from ..model import STATE_VARIABLES
 from ..simulator import BatchedSimulator, StateView, _stream_ptr
 from ..spaces import Box, GymEnv
@@ -160,7 +161,23 @@ class BatchedANMEnv(GymEnv):
                 self.observation_space = Box(low=lo32, high=hi32, dtype=np.float32)
         self.single_observation_space = self.observation_space
 
-        # ---- device-resident per-environment state ------------------------------------------------
+        self._alloc_buffers()
+        # key of the device-side sampler (reset(options={"sampler": "device"}), autoreset).  Unseeded environments draw
+        # it from np_random (entropy-seeded in that case), so that two unseeded environments -- e.g. the ranks of a
+        # sharded batch -- are not correlated; explicit seeds stay deterministic.
+        self.rng_seed = int(self.np_random.integers(2**62)) if seed is None else int(seed)
+        self._act_low = torch.as_tensor(lo, dtype=self.io_dtype, device=self.device)
+        self._act_high = torch.as_tensor(hi, dtype=self.io_dtype, device=self.device)
+        self.check_actions = True
+        self._series = None if series is None else np.ascontiguousarray(series, dtype=np.float64)
+        self._check_exogenous(exogenous, exo_low, exo_high, exo_noise, exo_corr, variants is not None or env_variant is not None)
+        self._obs_is_state = self.obs_values is not None and self.obs_values == self.state_values
+        self._set_task()
+        self._set_observation_gather(fuse_observation)
+        self._plan_step_path(track_full, straggler_after, straggler_mid, max_iter)
+
+    def _alloc_buffers(self):
+        """Device-resident per-environment state, and the episode buffers the step kernels keep."""
         E_, S = self.num_envs, self.state_N
         f64 = dict(dtype=torch.float64, device=self.device)
         fio = dict(dtype=self.io_dtype, device=self.device)   # what the policy sees: obs and reward
@@ -200,24 +217,22 @@ class BatchedANMEnv(GymEnv):
                 b.last_disc_return = self.last_episode_discounted_return.data_ptr()
                 b.last_length, b.episodes_done = self.last_episode_length.data_ptr(), self.episodes_done.data_ptr()
             self._episode_bufs = b
-        # key of the device-side sampler (reset(options={"sampler": "device"}), autoreset).  Unseeded
-        # environments draw it from np_random (entropy-seeded in that case), so that two unseeded
-        # environments -- e.g. the ranks of a sharded batch -- are not correlated; explicit seeds stay
-        # deterministic.
-        self.rng_seed = int(self.np_random.integers(2**62)) if seed is None else int(seed)
-        self._act_low = torch.as_tensor(lo, **fio)
-        self._act_high = torch.as_tensor(hi, **fio)
-        self.check_actions = True
 
-        # ---- environment constants for the kernels ---------------------------------------------------
-        self._series = None if series is None else np.ascontiguousarray(series, dtype=np.float64)
-        # exogenous="uniform": the loads and generator potentials of every step are drawn INSIDE the step kernels,
-        # P_i ~ U(exo_low[i], exo_high[i]) MW (units: loads by device id, then non-slack generators; defaults: loads
-        # [p_min, 0], generators [0, p_max]) from the counter-based RNG -- the stream layout is rng.py's (exo_uniform).
-        # K = 1: the aux variable is the step index of the episode.  step() is one launch and never calls next_vars().
-        # exogenous="series_noise": series mode plus bounded noise drawn INSIDE the step kernels, clipped to
-        # [exo_low, exo_high] -- P_i = clip(series[i, aux'] + exo_noise[i, aux'] (2 u_i - 1)) MW, keyed by the step index of
-        # the episode (rng.py: exo_series_noise).  K = 1: the aux variable is the table index, as in series mode.
+    def _check_exogenous(self, exogenous, exo_low, exo_high, exo_noise, exo_corr, has_classes):
+        """The exogenous mode and its tables, checked and resolved; nothing is handed to the library here.
+
+        exogenous="uniform": the loads and generator potentials of every step are drawn INSIDE the step kernels,
+        P_i ~ U(exo_low[i], exo_high[i]) MW (units: loads by device id, then non-slack generators; defaults: loads
+        [p_min, 0], generators [0, p_max]) from the counter-based RNG -- the stream layout is rng.py's (exo_uniform).
+        K = 1: the aux variable is the step index of the episode.  step() is one launch and never calls next_vars().
+        exogenous="series_noise": series mode plus bounded noise drawn INSIDE the step kernels, clipped to
+        [exo_low, exo_high] -- P_i = clip(series[i, aux'] + exo_noise[i, aux'] (2 u_i - 1)) MW, keyed by the step index of
+        the episode (rng.py: exo_series_noise).  K = 1: the aux variable is the table index, as in series mode.
+        exo_corr=rho (series-noise mode; a scalar or [n_exo], every entry finite and in [0, 1)): the noise is an AR(1)
+        chain instead of white -- every unit keeps a noise state z in `exo_z` ([num_envs, n_exo], float64, read-only for
+        the caller), z' = fma(rho, z, sqrt(1 - rho^2) w), and z' takes the place of the factor w (rng.py:
+        exo_series_corr).  None: the mode as it was, no buffer; 0.0: the new path, which then equals it bit for bit."""
+        sim = self.simulator
         if exogenous not in (None, "host", "uniform", "series_noise"):
             raise E.ArgsError("The argument exogenous is %r but should be None, 'host', 'uniform' or 'series_noise'." % (exogenous,))
         self.exogenous = exogenous if exogenous in ("uniform", "series_noise") else "host"
@@ -225,18 +240,13 @@ class BatchedANMEnv(GymEnv):
         self._noisy = self.exogenous == "series_noise"
         self._drawn = self._uniform or self._noisy   # P_load / P_pot come from the kernels' RNG: next_vars() is never called
         sim.exogenous = self.exogenous   # (what an agent built from the simulator alone can know of the task: agents/mpc.py)
-        self.exo_low = self.exo_high = self.exo_noise = None
+        self.exo_low = self.exo_high = self.exo_noise = self.exo_corr = self.exo_z = self._exo_innov = None
+        n_exo = sim.N_load + sim.N_non_slack_gen
         if exo_noise is not None and not self._noisy:
             raise E.ArgsError("exo_noise needs exogenous='series_noise'")
-        # exo_corr=rho (series-noise mode; a scalar or [n_exo], every entry finite and in [0, 1)): the noise is an AR(1)
-        # chain instead of white -- every unit keeps a noise state z in `exo_z` ([num_envs, n_exo], float64, read-only for
-        # the caller), z' = fma(rho, z, sqrt(1 - rho^2) w), and z' takes the place of the factor w (rng.py:
-        # exo_series_corr).  None: the mode as it was, no buffer; 0.0: the new path, which then equals it bit for bit.
-        self.exo_corr = self.exo_z = self._exo_innov = None
         if exo_corr is not None:
             if not self._noisy:
                 raise E.ArgsError("exo_corr needs exogenous='series_noise'")
-            n_exo = sim.N_load + sim.N_non_slack_gen
             try:
                 rho = np.ascontiguousarray(np.broadcast_to(np.asarray(exo_corr, dtype=np.float64), (n_exo,)))
             except ValueError:
@@ -245,43 +255,25 @@ class BatchedANMEnv(GymEnv):
                 raise E.ArgsError("exo_corr must be finite and in [0, 1)")
             self.exo_corr = rho
             # (formed here, once, and handed to the library beside rho: the kernels take no square root)
-            from .. import rng as _rng
-
             self._exo_innov = np.ascontiguousarray(_rng.exo_innovation(rho))
         sim.exo_corr = self.exo_corr   # (tells the agents, like sim.exogenous above)
-        if self._uniform:
-            from .. import rng as _rng
-
-            if self._series is not None:
-                raise E.EnvInitializationError("exogenous='uniform' and series= do not go together")
-            if K != 1:
-                raise E.EnvInitializationError("exogenous='uniform' needs K = 1 (the aux variable is the step index)")
-            if variants is not None or env_variant is not None:
-                raise E.EnvInitializationError("exogenous='uniform' does not take parameter classes (variants=)")
-            if sim.backend.device_type != "cuda":
-                # (a backend that ignores the mode would run a different task without saying so)
-                raise E.EnvInitializationError("exogenous='uniform' needs the GPU library: this backend does not draw in its kernels")
-            n_exo = sim.N_load + sim.N_non_slack_gen
-            d_lo, d_hi = _rng.default_exo_bounds(sim.model)
-            self.exo_low = d_lo if exo_low is None else np.ascontiguousarray(exo_low, dtype=np.float64)
-            self.exo_high = d_hi if exo_high is None else np.ascontiguousarray(exo_high, dtype=np.float64)
-            if self.exo_low.shape != (n_exo,) or self.exo_high.shape != (n_exo,):
-                raise E.ArgsError("exo_low / exo_high must have %d entries (loads, then non-slack generators)" % n_exo)
-            if not (np.isfinite(self.exo_low).all() and np.isfinite(self.exo_high).all() and (self.exo_low <= self.exo_high).all()):
-                raise E.ArgsError("exo_low / exo_high must be finite with exo_low <= exo_high")
-        elif self._noisy:
-            from .. import rng as _rng
-
-            if self._series is None:
-                raise E.EnvInitializationError("exogenous='series_noise' needs series= (the table the noise is added to)")
-            if K != 1:
-                raise E.EnvInitializationError("exogenous='series_noise' needs K = 1 (the aux variable is the table index)")
-            if variants is not None or env_variant is not None:
-                raise E.EnvInitializationError("exogenous='series_noise' does not take parameter classes (variants=)")
-            if sim.backend.device_type != "cuda":
-                # (a backend that ignores the mode would run a different task without saying so)
-                raise E.EnvInitializationError("exogenous='series_noise' needs the GPU library: this backend does not draw in its kernels")
-            n_exo = sim.N_load + sim.N_non_slack_gen
+        if not self._drawn:
+            if exo_low is not None or exo_high is not None:
+                raise E.ArgsError("exo_low / exo_high need exogenous='uniform'")
+            return
+        mode = "exogenous='%s'" % self.exogenous
+        if self._uniform and self._series is not None:
+            raise E.EnvInitializationError("exogenous='uniform' and series= do not go together")
+        if self._noisy and self._series is None:
+            raise E.EnvInitializationError("exogenous='series_noise' needs series= (the table the noise is added to)")
+        if self.K != 1:
+            raise E.EnvInitializationError("%s needs K = 1 (the aux variable is the %s index)" % (mode, "step" if self._uniform else "table"))
+        if has_classes:
+            raise E.EnvInitializationError("%s does not take parameter classes (variants=)" % mode)
+        if sim.backend.device_type != "cuda":
+            # (a backend that ignores the mode would run a different task without saying so)
+            raise E.EnvInitializationError("%s needs the GPU library: this backend does not draw in its kernels" % mode)
+        if self._noisy:   # the amplitude table, broadcast to the shape of the series
             if self._series.ndim != 2 or self._series.shape[0] != n_exo:
                 raise E.ArgsError("series must have %d rows (loads, then non-slack generators)" % n_exo)
             if exo_noise is None:
@@ -296,39 +288,49 @@ class BatchedANMEnv(GymEnv):
             if not (np.isfinite(amp).all() and (amp >= 0).all()):
                 raise E.ArgsError("exo_noise must be finite and >= 0")
             self.exo_noise = amp
-            d_lo, d_hi = _rng.default_exo_bounds(sim.model)
-            self.exo_low = d_lo if exo_low is None else np.ascontiguousarray(exo_low, dtype=np.float64)
-            self.exo_high = d_hi if exo_high is None else np.ascontiguousarray(exo_high, dtype=np.float64)
-            if self.exo_low.shape != (n_exo,) or self.exo_high.shape != (n_exo,):
-                raise E.ArgsError("exo_low / exo_high must have %d entries (loads, then non-slack generators)" % n_exo)
-            if not (self.exo_low <= self.exo_high).all():   # (NaN fails the comparison; infinite ends mean "no clip")
-                raise E.ArgsError("exo_low / exo_high must not be NaN, with exo_low <= exo_high")
-        elif exo_low is not None or exo_high is not None:
-            raise E.ArgsError("exo_low / exo_high need exogenous='uniform'")
+        d_lo, d_hi = _rng.default_exo_bounds(sim.model)
+        self.exo_low = d_lo if exo_low is None else np.ascontiguousarray(exo_low, dtype=np.float64)
+        self.exo_high = d_hi if exo_high is None else np.ascontiguousarray(exo_high, dtype=np.float64)
+        if self.exo_low.shape != (n_exo,) or self.exo_high.shape != (n_exo,):
+            raise E.ArgsError("exo_low / exo_high must have %d entries (loads, then non-slack generators)" % n_exo)
+        ordered = (self.exo_low <= self.exo_high).all()   # (NaN fails the comparison; series-noise: infinite ends mean "no clip")
+        if self._uniform and not (ordered and np.isfinite(self.exo_low).all() and np.isfinite(self.exo_high).all()):
+            raise E.ArgsError("exo_low / exo_high must be finite with exo_low <= exo_high")
+        if not ordered:
+            raise E.ArgsError("exo_low / exo_high must not be NaN, with exo_low <= exo_high")
+
+    def _env_config(self):
+        """The anm_env_config of the task: the struct that ends with the last field the task uses.  The arrays behind its
+        pointers stay alive on self (`_cfg_keep`: the observation bounds; the exogenous tables; `exo_z`)."""
         slo, shi = self._state_bounds_vectors()
-        self._obs_is_state = self.obs_values is not None and self.obs_values == self.state_values
         if self._obs_is_state and self.observation_space is not None:
             slo, shi = np.asarray(self._obs_space64.low, float), np.asarray(self._obs_space64.high, float)
-        ep_kw = {}
-        if self._episode_bufs is not None:
-            ep_kw = dict(max_episode_steps=self.max_episode_steps or 0, episode=C.pointer(self._episode_bufs))
-        if self._noisy:
-            ep_kw["exo_noise"] = self.exo_noise.ctypes.data_as(_lib.c_double_p)
-        if self.exo_corr is not None:
-            self.exo_z = torch.zeros((E_, len(self.exo_corr)), dtype=torch.float64, device=self.device)
-            ep_kw.update(exo_rho=self.exo_corr.ctypes.data_as(_lib.c_double_p),
-                         exo_innov=self._exo_innov.ctypes.data_as(_lib.c_double_p), exo_z=self.exo_z.data_ptr())
-        cfg = (_lib.EnvConfigCorr if self.exo_corr is not None else _lib.EnvConfigNoise if self._noisy else _lib.EnvConfigEpisode if ep_kw else _lib.EnvConfig)(
-            K=K, gamma=float(gamma), clip_e_loss=float(c1), clip_penalty=float(c2),
-            obs_low=_lib.as_c(slo, np.float64)[1], obs_high=_lib.as_c(shi, np.float64)[1],
-            series=None if self._series is None else self._series.ctypes.data_as(_lib.c_double_p),
-            period=0 if self._series is None else int(self._series.shape[1]),
-            exo_mode=_lib.EXO_UNIFORM if self._uniform else _lib.EXO_SERIES_NOISE if self._noisy else _lib.EXO_HOST,
-            exo_low=self.exo_low.ctypes.data_as(_lib.c_double_p) if self._drawn else None,
-            exo_high=self.exo_high.ctypes.data_as(_lib.c_double_p) if self._drawn else None,
-            **ep_kw,
-        )  # fmt: skip
         self._cfg_keep = (slo, shi)
+        kw = dict(K=self.K, gamma=float(self.gamma), clip_e_loss=float(self.costs_clipping[0]), clip_penalty=float(self.costs_clipping[1]),
+                  obs_low=_lib.as_c(slo, np.float64)[1], obs_high=_lib.as_c(shi, np.float64)[1],
+                  exo_mode=_lib.EXO_UNIFORM if self._uniform else _lib.EXO_SERIES_NOISE if self._noisy else _lib.EXO_HOST)  # fmt: skip
+        if self._series is not None:
+            kw.update(series=self._series.ctypes.data_as(_lib.c_double_p), period=int(self._series.shape[1]))
+        if self._drawn:
+            kw.update(exo_low=self.exo_low.ctypes.data_as(_lib.c_double_p), exo_high=self.exo_high.ctypes.data_as(_lib.c_double_p))
+        struct = _lib.EnvConfig
+        if self._episode_bufs is not None:
+            struct = _lib.EnvConfigEpisode
+            kw.update(max_episode_steps=self.max_episode_steps or 0, episode=C.pointer(self._episode_bufs))
+        if self._noisy:
+            struct = _lib.EnvConfigNoise
+            kw.update(exo_noise=self.exo_noise.ctypes.data_as(_lib.c_double_p))
+        if self.exo_corr is not None:
+            struct = _lib.EnvConfigCorr
+            self.exo_z = torch.zeros((self.num_envs, len(self.exo_corr)), dtype=torch.float64, device=self.device)
+            kw.update(exo_rho=self.exo_corr.ctypes.data_as(_lib.c_double_p),
+                      exo_innov=self._exo_innov.ctypes.data_as(_lib.c_double_p), exo_z=self.exo_z.data_ptr())
+        return struct(**kw)
+
+    def _set_task(self):
+        """Hand the task to the library: anm_model_set_env, the I/O mode, the observation bounds of every class."""
+        sim = self.simulator
+        cfg = self._env_config()
         with sim._device_ctx():
             sim.backend.check(sim.backend.lib.anm_model_set_env(sim._handle, C.byref(cfg)), "anm_model_set_env")
             if self._io32:
@@ -340,39 +342,47 @@ class BatchedANMEnv(GymEnv):
         self.class_observation_bounds = None
         vms = getattr(sim, "variant_models", [sim.model])
         if len(vms) > 1 and self._obs_is_state and type(self).observation_bounds is BatchedANMEnv.observation_bounds:
-            los, his = [slo], [shi]
+            los, his = [self._cfg_keep[0]], [self._cfg_keep[1]]
             with sim._device_ctx():
                 for k, vm in enumerate(vms[1:], start=1):
                     lo_k, hi_k = self._state_bounds_vectors(vm.state_bounds())
-                    a_lo, p_lo = _lib.as_c(lo_k, np.float64)
-                    a_hi, p_hi = _lib.as_c(hi_k, np.float64)
+                    (a_lo, p_lo), (a_hi, p_hi) = (_lib.as_c(x, np.float64) for x in (lo_k, hi_k))
                     sim.backend.check(sim.backend.lib.anm_model_set_class_obs_bounds(sim._handle, k, p_lo, p_hi),
                                       "anm_model_set_class_obs_bounds")
                     los.append(lo_k)
                     his.append(hi_k)
             self.class_observation_bounds = (np.stack(los), np.stack(his))
-        # list-form observations (anm_env.py:497-521): gathered, scaled and clipped inside the step kernel when
-        # the library can (anm_model_set_obs), else by anm_gather_obs_f64 from the electrical-state dump
+
+    def _set_observation_gather(self, fuse_observation):
+        """List-form observations (anm_env.py:497-521): gathered, scaled and clipped inside the step kernel when
+        the library can (anm_model_set_obs), else by anm_gather_obs_f64 from the electrical-state dump."""
+        sim = self.simulator
         self._gather = None  # (index, scale, low, high) device tensors
         self._obs_fused = False
         self._obs_buf = None
         self._obs_gather64 = None   # float32 mode: where reset() gathers a list-form observation before the one cast
-        if self.obs_values is not None and not self._obs_is_state:
-            self._gather = self._build_gather(self.obs_values)
-            lib = sim.backend.lib
-            if fuse_observation and lib.anm_model_obs_fusable(sim._handle):
-                idx, sc, lo_, hi_ = (t.cpu().numpy() for t in self._gather)
-                a_i, p_i = _lib.as_c(idx, np.int32)
-                (a_s, p_s), (a_l, p_l), (a_h, p_h) = (_lib.as_c(x, np.float64) for x in (sc, lo_, hi_))
-                with sim._device_ctx():
-                    sim.backend.check(lib.anm_model_set_obs(sim._handle, len(a_i), p_i, p_s, p_l, p_h), "anm_model_set_obs")
-                self._obs_fused = True
-                self._obs_buf = torch.zeros((E_, len(a_i)), **fio)
-            if self._io32 and not self._obs_fused:
-                raise E.EnvInitializationError(
-                    "io_dtype=torch.float32 needs the list-form observation gathered inside the step kernel: "
-                    + ("fuse_observation=False" if not fuse_observation else "this model cannot gather in its kernel")
-                    + " leaves it to anm_gather_obs_f64, which writes float64 observations")
+        if self.obs_values is None or self._obs_is_state:
+            return
+        self._gather = self._build_gather(self.obs_values)
+        lib = sim.backend.lib
+        if fuse_observation and lib.anm_model_obs_fusable(sim._handle):
+            idx, sc, lo_, hi_ = (t.cpu().numpy() for t in self._gather)
+            a_i, p_i = _lib.as_c(idx, np.int32)
+            (a_s, p_s), (a_l, p_l), (a_h, p_h) = (_lib.as_c(x, np.float64) for x in (sc, lo_, hi_))
+            with sim._device_ctx():
+                sim.backend.check(lib.anm_model_set_obs(sim._handle, len(a_i), p_i, p_s, p_l, p_h), "anm_model_set_obs")
+            self._obs_fused = True
+            self._obs_buf = torch.zeros((self.num_envs, len(a_i)), dtype=self.io_dtype, device=self.device)
+        if self._io32 and not self._obs_fused:
+            raise E.EnvInitializationError(
+                "io_dtype=torch.float32 needs the list-form observation gathered inside the step kernel: "
+                + ("fuse_observation=False" if not fuse_observation else "this model cannot gather in its kernel")
+                + " leaves it to anm_gather_obs_f64, which writes float64 observations")
+
+    def _plan_step_path(self, track_full, straggler_after, straggler_mid, max_iter):
+        """What a step launches: the electrical-state dump, the compact time index of the fast path, the rows it
+        leaves unwritten (state_same) and the workspace of the two-launch step."""
+        sim = self.simulator
         # track_full: also dump the electrical state of every step, so that simulator.state /
         # simulator.pfe_converged follow the environment like the reference's (simulator.py:529-537)
         self.track_full = bool(track_full)
@@ -388,21 +398,20 @@ class BatchedANMEnv(GymEnv):
         # coalesced-row step kernel
         self._aux_index = None
         # (series-noise mode: the general step kernel serves it; no compact index, no state_same, no two-launch workspace)
-        if self._series is not None and K == 1 and sim.impl == "thread" and not self._noisy:
-            self._aux_index = torch.zeros(E_, dtype=torch.int32, device=self.device)
+        if self._series is not None and self.K == 1 and sim.impl == "thread" and not self._noisy:
+            self._aux_index = torch.zeros(self.num_envs, dtype=torch.int32, device=self.device)
         self._aux_index_ptr = None if self._aux_index is None else self._aux_index.data_ptr()
         # "state" observation on the fast path: obs = clip(state) is the state itself unless a bound bites, so
         # the kernel writes the state row only then and flags the rest (anm_model_bind_state_same)
         # (float32 mode: the state row has no float64 twin in obs and is always written)
         if self._aux_index is not None and self._obs_is_state and sim.backend.device_type == "cuda" and not self._io32:
-            self._state_same = torch.zeros(E_, dtype=torch.uint8, device=self.device)
+            self._state_same = torch.zeros(self.num_envs, dtype=torch.uint8, device=self.device)
             with sim._device_ctx():
                 sim.backend.check(sim.backend.lib.anm_model_bind_state_same(sim._handle, self._state_same.data_ptr()),
                                   "anm_model_bind_state_same")
         # two-phase step (see anm_step_ws in include/anm_mi355x.h): the first launch stops after
         # `straggler_after` Newton iterations, a second launch continues the solves still running
-        self._ws = None
-        self._ws_ref = None
+        self._ws = self._ws_ref = None
         if straggler_after == "auto":
             # measured on MI355X (scripts/handoff_sweep.py, profiles/r02_d_handoff_sweep.txt): at 65 536
             # environments the in-wave lane-group hand-over (anm_solver_opts.handoff_after) is the faster cure for
@@ -443,21 +452,8 @@ class BatchedANMEnv(GymEnv):
     def observation_bounds(self):  # anm_env.py:193-233
         if self.obs_values is None:
             return None
-        lower, upper = [], []
-        bounds = self.simulator.state_bounds
-        for key, nodes, unit in self.obs_values:
-            for n in nodes:
-                if key == "aux":
-                    if self.aux_bounds is not None:
-                        lower.append(self.aux_bounds[n][0])
-                        upper.append(self.aux_bounds[n][1])
-                    else:
-                        lower.append(-np.inf)
-                        upper.append(np.inf)
-                else:
-                    lower.append(bounds[key][n][unit][0])
-                    upper.append(bounds[key][n][unit][1])
-        return Box(low=np.array(lower), high=np.array(upper), dtype=np.float64)
+        lower, upper = self._bounds_vectors(self.obs_values, self.simulator.state_bounds)
+        return Box(low=lower, high=upper, dtype=np.float64)
 
     # ---- spaces helpers (anm_env.py:497-549) ------------------------------------------------------------
     def _build_observation_space(self, observation):
@@ -502,9 +498,12 @@ class BatchedANMEnv(GymEnv):
     def _state_bounds_vectors(self, bounds=None):
         """Box bounds of the *state* vector, used when the observation is the state (``bounds``: the state bounds of
         another network of the same topology: a parameter class)."""
+        return self._bounds_vectors(self.state_values, self.simulator.state_bounds if bounds is None else bounds)
+
+    def _bounds_vectors(self, values, bounds):
+        """(low, high) of the variables `values` names: `bounds` for the electrical ones, aux_bounds (else none) for aux."""
         lo, hi = [], []
-        bounds = self.simulator.state_bounds if bounds is None else bounds
-        for key, nodes, unit in self.state_values:
+        for key, nodes, unit in values:
             for n in nodes:
                 if key == "aux":
                     if self.aux_bounds is not None:
