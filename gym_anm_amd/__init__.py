@@ -12,6 +12,8 @@ _TOP_LEVEL = {  # the names gym_anm exports at top level (gym_anm/__init__.py:5-
     "MPCAgentConstant": ("gym_anm_amd.agents", "MPCAgentConstant"),
     # (this package's own: the perfect forecast of the tasks drawn inside the step kernels)
     "MPCAgentPerfectStream": ("gym_anm_amd.agents", "MPCAgentPerfectStream"),
+    # (... and of the series-noise task with correlated noise)
+    "MPCAgentPerfectChain": ("gym_anm_amd.agents", "MPCAgentPerfectChain"),
 }
 
 

@@ -111,6 +111,12 @@ class MpcStream(C.Structure):
                 ("reset_count", C.c_void_p), ("exo_low", C.c_void_p), ("exo_high", C.c_void_p), ("exo_noise", C.c_void_p)]
 
 
+class MpcChain(MpcStream):
+    """anm_mpc_chain: anm_mpc_stream grown at its tail by the AR(1) tables and the noise states of the correlated series-noise
+    task (anm_mpc_act_chain_f64; every pointer a device pointer)"""
+    _fields_ = [("exo_rho", C.c_void_p), ("exo_innov", C.c_void_p), ("exo_z", C.c_void_p)]
+
+
 class SolverOpts(C.Structure):
     _fields_ = [("tol", C.c_double), ("max_iter", C.c_int32), ("precision", C.c_int32), ("handoff_after", C.c_int32),
                 ("row_continuation", C.c_int32)]
@@ -173,6 +179,8 @@ ABI = {
                         + [C.POINTER(MpcOpts), _P]),
     "anm_mpc_act_stream_f64": (C.c_int, [C.c_void_p, C.c_int64, _P, _P, _P, C.c_int32, _P, _P, C.c_int32] + [_P] * 8
                                + [C.POINTER(MpcOpts), C.POINTER(MpcStream), _P]),
+    "anm_mpc_act_chain_f64": (C.c_int, [C.c_void_p, C.c_int64, _P, _P, _P, C.c_int32, _P, _P, C.c_int32] + [_P] * 8
+                              + [C.POINTER(MpcOpts), C.POINTER(MpcChain), _P]),
     "anm_gather_obs_f64": (C.c_int, [C.c_int64, C.c_int32, _P, C.c_int32, C.c_int32, _P, _P, C.c_int32, _P, _P, _P, _P, _P,
                                      _P]),
     "anm_test_row_dpp": (C.c_int, [_P, _P, _P, _P]),
@@ -185,7 +193,7 @@ ABI = {
 
 # entry points of modes that live in the GPU kernels alone: a backend that is not the GPU library (the host test double)
 # may lack them -- the host layer refuses those modes on such a backend before it would call them
-GPU_ONLY = ("anm_model_set_io", "anm_mpc_act_stream_f64", "anm_test_row_dpp")
+GPU_ONLY = ("anm_model_set_io", "anm_mpc_act_stream_f64", "anm_mpc_act_chain_f64", "anm_test_row_dpp")
 
 
 def bind(cdll, optional=()):
@@ -291,8 +299,8 @@ def load_for_topology(topo, impl=None) -> Backend:
 
 
 MPC_ABI = ("anm_last_error", "anm_topology_signature", "anm_mpc_create", "anm_mpc_destroy", "anm_mpc_dims_of", "anm_mpc_get_tables",
-           "anm_mpc_solve_f64", "anm_mpc_act_f64", "anm_mpc_act_stream_f64")
-MPC_FORECAST_CONSTANT, MPC_FORECAST_PERFECT, MPC_FORECAST_STREAM = 1, 2, 3
+           "anm_mpc_solve_f64", "anm_mpc_act_f64", "anm_mpc_act_stream_f64", "anm_mpc_act_chain_f64")
+MPC_FORECAST_CONSTANT, MPC_FORECAST_PERFECT, MPC_FORECAST_STREAM, MPC_FORECAST_CHAIN = 1, 2, 3, 4
 
 
 class MpcBackend:

@@ -13,7 +13,8 @@ of charge (``mpc.py:390-417``).  So here
   on a :class:`~gym_anm_amd.envs.anm_env.BatchedANMEnv`;
 * :class:`MPCAgentPerfectStream` is the perfect-forecast agent of the tasks whose exogenous variables are drawn inside
   the step kernels (``exogenous="uniform"`` / ``"series_noise"``): its forecast is the tasks' own random stream,
-  evaluated ahead;
+  evaluated ahead; :class:`MPCAgentPerfectChain` is the same for the series-noise task with correlated noise
+  (``exo_corr=``): the step's AR(1) recurrence rolled forward from the environment's noise states;
 * :class:`DCOPFProgram` spells the reference's program out row by row (``min q.x, l <= A x <= u``); nothing in
   the solve uses it -- it is what the tests check a solution's feasibility against.
 
@@ -235,7 +236,8 @@ class BatchedDCOPF:
     def act(self, forecast, env, act_low, act_high):
         """``MPCAgent.act`` as ONE launch (``anm_mpc_act_f64``): the forecasts are gathered inside the kernel -- ``forecast``
         1: constant, from the state rows of ``env``; 2: perfect, from its periodic tables; 3: the stream of a task drawn
-        inside the step kernels, evaluated ahead (``anm_mpc_act_stream_f64``) -- and the first stage's set-points come back
+        inside the step kernels, evaluated ahead (``anm_mpc_act_stream_f64``); 4: the same for the correlated series-noise
+        task, rolled forward from ``env.exo_z`` (``anm_mpc_act_chain_f64``) -- and the first stage's set-points come back
         as the clipped MW action rows ``[E, 2 n_gen + 2 n_des]`` (a persistent buffer)."""
         d = self.dims
         E = int(env.num_envs)
@@ -243,7 +245,7 @@ class BatchedDCOPF:
         if getattr(self, "_action", None) is None or self._action.shape[0] != E:
             self._action = torch.zeros((E, 2 * d.n_gen + 2 * d.n_des), dtype=torch.float64, device=self.device)
         series_ptr, period = None, 0
-        if forecast == 2 or (forecast == 3 and env._series is not None):
+        if forecast == 2 or (forecast in (3, 4) and getattr(env, "_series", None) is not None):
             if getattr(self, "_series_src", None) is not env._series:
                 self._series_src = env._series
                 self._series_dev = torch.as_tensor(env._series, dtype=torch.float64, device=self.device).contiguous()
@@ -253,6 +255,8 @@ class BatchedDCOPF:
         soc = env.simulator.soc
         if forecast == 3:
             return self._act_stream(env, E, same, aux, series_ptr, period, soc, act_low, act_high)
+        if forecast == 4:
+            return self._act_chain(env, E, same, aux, series_ptr, period, soc, act_low, act_high)
         with self._device_ctx():
             rc = self.backend.lib.anm_mpc_act_f64(
                 self._handle, E, int(forecast), env._state_buf.data_ptr(), None if same is None else env._state_obs.data_ptr(),
@@ -287,6 +291,32 @@ class BatchedDCOPF:
                 self.u0.data_ptr(), self.objective.data_ptr(), self.iters.data_ptr(), self.info.data_ptr(), C.byref(self.opts),
                 C.byref(st), self._stream_ptr())
         self.backend.check(rc, "anm_mpc_act_stream_f64")
+        return self._action
+
+    def _act_chain(self, env, E, same, aux, series_ptr, period, soc, act_low, act_high):
+        from .. import _lib
+
+        if not getattr(env, "_noisy", False) or getattr(env, "exo_corr", None) is None:
+            raise E_.ArgsError("the chain forecast needs an environment with exogenous='series_noise' and exo_corr=")
+        # device copies of the ends, the amplitude table and the AR(1) tables (host arrays of the environment), cached per
+        # environment; exo_z is the environment's own tensor, read in place
+        if getattr(self, "_chain_src", None) is not env:
+            dev = lambda a: torch.as_tensor(a, dtype=torch.float64, device=self.device).contiguous()  # noqa: E731
+            self._chain_src, self._chain_dev = env, tuple(dev(a) for a in (env.exo_low, env.exo_high, env.exo_noise, env.exo_corr,
+                                                                           env._exo_innov))
+        lo, hi, amp, rho, innov = self._chain_dev
+        st = _lib.MpcChain(exo_mode=_lib.EXO_SERIES_NOISE, rng_seed=int(env.rng_seed), env_offset=int(env.env_offset),
+                           timestep=env.timestep.data_ptr(), reset_count=env._reset_count.data_ptr(), exo_low=lo.data_ptr(),
+                           exo_high=hi.data_ptr(), exo_noise=amp.data_ptr(), exo_rho=rho.data_ptr(), exo_innov=innov.data_ptr(),
+                           exo_z=env.exo_z.data_ptr())
+        with self._device_ctx():
+            rc = self.backend.lib.anm_mpc_act_chain_f64(
+                self._handle, E, env._state_buf.data_ptr(), None if same is None else env._state_obs.data_ptr(),
+                None if same is None else same.data_ptr(), int(env._state_buf.shape[1]), None if aux is None else aux.data_ptr(),
+                series_ptr, period, soc.data_ptr(), act_low.data_ptr(), act_high.data_ptr(), self._action.data_ptr(),
+                self.u0.data_ptr(), self.objective.data_ptr(), self.iters.data_ptr(), self.info.data_ptr(), C.byref(self.opts),
+                C.byref(st), self._stream_ptr())
+        self.backend.check(rc, "anm_mpc_act_chain_f64")
         return self._action
 
     @property
@@ -357,11 +387,13 @@ class MPCAgent:
         state of charge, a batched environment of this package that has what the kernel reads."""
         cls = type(self)
         mode = self.FUSED_FORECAST
-        stock = {1: MPCAgentConstant, 2: MPCAgentPerfect, 3: MPCAgentPerfectStream}.get(mode)
-        symbol = "anm_mpc_act_stream_f64" if mode == 3 else "anm_mpc_act_f64"
-        # what the kernel reads: the tables (2), a drawn mode (3); the time index in the last column where a table is indexed
-        has = {1: True, 2: getattr(env, "_series", None) is not None, 3: bool(getattr(env, "_drawn", False))}.get(mode, False)
-        indexed = mode == 2 or (mode == 3 and getattr(env, "_noisy", False))
+        stock = {1: MPCAgentConstant, 2: MPCAgentPerfect, 3: MPCAgentPerfectStream, 4: MPCAgentPerfectChain}.get(mode)
+        symbol = {3: "anm_mpc_act_stream_f64", 4: "anm_mpc_act_chain_f64"}.get(mode, "anm_mpc_act_f64")
+        # what the kernel reads: the tables (2), a drawn mode (3), the noise states (4); the time index in the last column
+        # where a table is indexed
+        has = {1: True, 2: getattr(env, "_series", None) is not None, 3: bool(getattr(env, "_drawn", False)),
+               4: bool(getattr(env, "_noisy", False)) and getattr(env, "exo_z", None) is not None}.get(mode, False)
+        indexed = mode in (2, 4) or (mode == 3 and getattr(env, "_noisy", False))
         return (stock is not None and cls.forecast is stock.forecast and cls.solve is MPCAgent.solve and cls._soc is MPCAgent._soc
                 and hasattr(self.solver.backend.lib, symbol) and hasattr(env, "_state_buf") and has
                 and env._state_buf.shape[1] >= 2 * env.simulator.model.N_device + env.simulator.model.N_des
@@ -464,13 +496,14 @@ class MPCAgentPerfectStream(MPCAgent):
     agent looks past episode ends too.
 
     A task with correlated noise (``exo_corr=``) is refused, ``ArgsError``: its draws depend on the noise state of every
-    unit, not on the step index alone, and this agent's forecast is a pure function of the step index.  (Rolling the
-    chain forward from ``exo_z`` inside the solve is the follow-up; :class:`MPCAgentPerfect`, the profile forecast, and
-    :class:`MPCAgentConstant` read only state and tables and work on such a task.)"""
+    unit, not on the step index alone, and this agent's forecast is a pure function of the step index.
+    (:class:`MPCAgentPerfectChain` rolls the chain forward from ``exo_z`` inside the solve and is the perfect agent of such
+    a task; :class:`MPCAgentPerfect`, the profile forecast, and :class:`MPCAgentConstant` read only state and tables and
+    work on it too.)"""
 
     FUSED_FORECAST = 3
     _CORR_REFUSAL = ("MPCAgentPerfectStream has no forecast for a task with correlated noise (exo_corr=): the draws depend "
-                     "on the noise state exo_z, not on the step index alone")
+                     "on the noise state exo_z, not on the step index alone; use MPCAgentPerfectChain")
 
     def __init__(self, simulator, *args, **kw):
         if getattr(simulator, "exogenous", None) not in ("uniform", "series_noise"):
@@ -502,6 +535,56 @@ class MPCAgentPerfectStream(MPCAgent):
             env.rng_seed, env.env_offset, env._reset_count.cpu().numpy(), env.timestep.cpu().numpy(), self.planning_steps,
             env.exo_low, env.exo_high, series=env._series if noisy else None, noise=env.exo_noise if noisy else None,
             aux=env.state[:, -1].cpu().numpy().astype(np.int64) if noisy else None)
+        f = torch.as_tensor(f, dtype=torch.float64, device=self.device)   # [E, n_load + n_gen, N] MW
+        nl = env.simulator.N_load
+        return f[:, :nl] / self._base_t, f[:, nl:] / self._base_t
+
+
+class MPCAgentPerfectChain(MPCAgent):
+    """Perfect forecasts for the series-noise task with CORRELATED noise (``exogenous="series_noise", exo_corr=rho``): stage
+    ``i`` is the step kernels' own AR(1) recurrence applied ``i + 1`` times to the environment's noise states ``exo_z``, at
+    step index ``timestep + 1 + i`` and table index ``aux + 1 + i`` of the running episode -- what the environment then
+    draws, bit for bit (``rng.exo_forecast_corr`` is the specification).  The stages are the lanes of the solve: each draws
+    its own factor, the states travel up the group one stage per exchange (``anm_mpc_act_chain_f64``, still ONE launch per
+    ``act``; ``exo_z`` is only read).  This is the upper bound a learned policy is measured against on such a task.
+
+    As for :class:`MPCAgentPerfectStream`, the forecast of an environment that is terminated or past its episode limit is
+    the same pure function, and the horizon is not cut at ``max_episode_steps``.  An uncorrelated drawn task
+    (``exo_corr=None``) keeps no noise states: ``ArgsError``, use :class:`MPCAgentPerfectStream`."""
+
+    FUSED_FORECAST = 4
+
+    @staticmethod
+    def _check_task(exogenous, exo_corr, what):
+        if exogenous != "series_noise":
+            raise E_.ArgsError("MPCAgentPerfectChain needs %s with exogenous='series_noise' and exo_corr= (the task with "
+                               "correlated noise); this one is in mode %r" % (what, exogenous))
+        if exo_corr is None:
+            raise E_.ArgsError("MPCAgentPerfectChain rolls the noise states of an exogenous='series_noise' task with correlated noise forward "
+                               "and %s has none (exo_corr=None); for an uncorrelated task drawn inside the step kernels use "
+                               "MPCAgentPerfectStream" % what)
+
+    def __init__(self, simulator, *args, **kw):
+        self._check_task(getattr(simulator, "exogenous", None), getattr(simulator, "exo_corr", None), "the simulator of an environment")
+        super().__init__(simulator, *args, **kw)
+
+    def _chain_env(self, env):
+        self._check_task(getattr(env, "exogenous", None), getattr(env, "exo_corr", None), "an environment")
+
+    def act(self, env):
+        if not hasattr(env, "vec"):
+            self._chain_env(env)
+        return super().act(env)
+
+    def forecast(self, env):
+        """The unfused path: the specification itself (``rng.exo_forecast_corr_v``, exact) on the host, from ``env.exo_z``."""
+        from .. import rng
+
+        self._chain_env(env)
+        f = rng.exo_forecast_corr_v(
+            env.rng_seed, env.env_offset, env._reset_count.cpu().numpy(), env.timestep.cpu().numpy(), self.planning_steps,
+            env.state[:, -1].cpu().numpy().astype(np.int64), env.exo_z.cpu().numpy(), env._series, env.exo_noise, env.exo_corr,
+            env._exo_innov, env.exo_low, env.exo_high)
         f = torch.as_tensor(f, dtype=torch.float64, device=self.device)   # [E, n_load + n_gen, N] MW
         nl = env.simulator.N_load
         return f[:, :nl] / self._base_t, f[:, nl:] / self._base_t

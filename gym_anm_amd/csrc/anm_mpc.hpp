@@ -120,7 +120,7 @@ struct Opts {
 // from the state row, mpc_constant.py:24-35; perfect: from the task's periodic tables, mpc_perfect.py:24-40) and the
 // first stage's set-points leave as the clipped MW action row -- no forecast tensors, no permute / scale / cat / clip launches.
 struct Act {
-  int mode;                   // 0: off (forecast arrays given); 1: constant forecast; 2: perfect forecast; 3: the stream (below)
+  int mode;                   // 0: off (forecast arrays given); 1: constant forecast; 2: perfect forecast; 3: the stream, 4: the chain (below)
   const double* state;        // [E][state_dim] state rows, MW: dev_p of the loads, gen_p_max; the time index in the last column
   const double* state_alt;    // rows to read where state_same[e] != 0 (the observation rows: anm_model_bind_state_same), or null
   const uint8_t* state_same;  // [E] or null
@@ -146,6 +146,16 @@ struct Act {
   const double* exo_low;      // [NL + NG] MW: ends of the uniform draw / of the clip
   const double* exo_high;
   const double* exo_noise;    // [NL + NG][period] MW amplitudes (series-noise mode)
+  // mode 4 (ANM_MPC_FORECAST_CHAIN, anm_mpc_act_chain_f64): the series-noise task with correlated noise.  Stage i is the
+  // step kernels' AR(1) recurrence applied i + 1 times to the environment's row of exo_z (act_chain_value below;
+  // specification: rng.py, exo_forecast_corr).  The fields above as in mode 3, exo_mode = ANM_EXO_SERIES_NOISE.
+  const double* exo_rho;      // [NL + NG] dev
+  const double* exo_innov;    // [NL + NG] dev
+  const double* exo_z;        // [E][NL + NG] dev, read only
+  // (keeps the tail a multiple of 32 bytes: Act sits inside the kernel argument block, and what follows it there keeps its
+  // alignment -- the scalar loads of the arguments are merged by alignment, and with a tail of 24 bytes two of the existing
+  // stream instantiations came out 22 and 2 instructions longer; profiles/mpc_chain_kernels.txt)
+  const void* reserved;
 };
 
 // Stream forecast: what a stage's draws are keyed by.  The episode key and the step index are those of the step kernels
@@ -180,6 +190,40 @@ ANM_HD double act_stream_value(const Act& a, const StreamAt& s, int unit) {
     v = ExoUniform::draw(s.key, s.t, unit, lo, hi);
   }
   return v / a.base;
+}
+
+// Chain forecast (mode 4): the noise state of a unit at stage i is the step kernels' recurrence applied i + 1 times to the
+// environment's exo_z -- sequential across the stages, which are the LANES of a group.  Every lane holds the factor w of its
+// own stage (independent of the other stages); the states then travel up the group one stage per exchange, a systolic sweep
+// like the solver's: N - 1 exchanges (`x.up`: the previous stage's value), all of them executed by every lane, and after
+// exchange s the lane of stage s replaces its value by ExoNoise::advance of what stage s - 1 holds -- final since step
+// s - 1.  Stage 0 starts from z0 itself and never takes what `up` brings (0 there; the lane before it belongs to another
+// group).  What a later stage holds before its turn is a finite number nobody reads.  Each z_i is produced by the very
+// operations the step kernel will perform, in their order, so the forecast is exact; a log-depth scan would reassociate.
+// `x`: stage(), up(); no asm here -- tests/hostsim/mpc_chain_check.cpp instantiates it with one host thread per lane.
+template <class X>
+ANM_HD double chain_sweep(const X& x, int N, double rho, double c, double z0, double w) {
+  const int st = x.stage();
+  double z = ExoNoise::advance(rho, c, z0, w);
+  for (int s = 1; s < N; ++s) {   // (N: wave-uniform)
+    const double zn = ExoNoise::advance(rho, c, x.up(z), w);
+    z = st == s ? zn : z;
+  }
+  return z;
+}
+// unit `unit` (loads by slot, then the generators at nl + k; n_exo = nl + ng: the width of a row of exo_z) of the lane's stage,
+// p.u.  To be called by EVERY lane of the wavefront, outside divergent code (the exchanges); a lane that is not `on` (no
+// stage, or no environment) reads no row, draws nothing it uses and returns 0.
+template <class X>
+ANM_HD double act_chain_value(const Act& a, const StreamAt& s, bool on, int64_t env, int unit, int n_exo, int N, const X& x) {
+  uint32_t q[4];
+  ExoUniform::block(s.key, s.t, uint32_t(unit) >> 1, q);
+  const double w = on ? ExoNoise::factor(q, unit) : 0.0;
+  const double z0 = on ? a.exo_z[env * n_exo + unit] : 0.0;
+  const double z = chain_sweep(x, N, a.exo_rho[unit], a.exo_innov[unit], z0, w);
+  if (!on) return 0.0;
+  const int64_t at = int64_t(unit) * a.period + s.aux;
+  return ExoNoise::map_state(a.exo_noise[at], z, a.series[at], a.exo_low[unit], a.exo_high[unit]) / a.base;
 }
 
 // column of the k-th load's dev_p in a state row = its device index (anm_env.py:139-147: dev_p of every device first)
@@ -703,8 +747,9 @@ struct Step {
 };
 
 // One lane's run of the whole solve.  STREAM: the forecasts are the stream's (Act, mode 3), drawn by the lane in the
-// prologue -- the episode key once, then the units; nothing of the draws lives on into the iterations.
-template <class T, bool STREAM = false, class X>
+// prologue -- the episode key once, then the units; nothing of the draws lives on into the iterations.  STREAM == 2: the
+// chain (Act, mode 4): the same draws, rolled through the AR(1) recurrence from exo_z by a sweep over the group's lanes.
+template <class T, int STREAM = 0, class X>
 ANM_HD void solve(cptr_t C, const IO& io, const Opts& opt, int64_t env, bool valid, int N, X& x, double* lane_lds = nullptr) {
   typedef Sz<T> S;
   typedef Lane<T> L;
@@ -728,7 +773,16 @@ ANM_HD void solve(cptr_t C, const IO& io, const Opts& opt, int64_t env, bool val
     double pl[pos(NL)];
     constexpr bool PAD = is_padded<T>::value;
     const int nl = PAD ? io.nl : NL, ng = PAD ? io.ng : NG;   // (a topology's kernel: compile-time constants)
-    if constexpr (STREAM) {
+    if constexpr (STREAM == 2) {
+      StreamAt at{0, 0, 0};
+      if (on) at = act_stream_at(io.act, env, i);
+      // (l >= nl, g >= ng: wave-uniform -- the exchanges inside stay outside divergent code)
+      ANM_UFOR (int l = 0; l < NL; ++l) pl[l] = l >= nl ? 0.0 : act_chain_value(io.act, at, on, env, l, nl + ng, N, x);
+      ANM_UFOR (int g = 0; g < NG; ++g) {
+        const double fc = g >= ng ? 0.0 : act_chain_value(io.act, at, on, env, nl + g, nl + ng, N, x);
+        ln.wd[g] = fmax(fmin(C[S::T_GPMAX + g], fc) - C[S::T_GPMIN + g], 0.0);
+      }
+    } else if constexpr (STREAM == 1) {
       StreamAt at{0, 0, 0};
       if (on) at = act_stream_at(io.act, env, i);
       ANM_UFOR (int l = 0; l < NL; ++l) pl[l] = (!on || l >= nl) ? 0.0 : act_stream_value(io.act, at, l);
@@ -1125,8 +1179,9 @@ struct WaveGroup {
   __device__ bool all_done(bool d) const { return __all(d); }
 };
 
-// STREAM: the instantiations of anm_mpc_act_stream_f64 (solve: the lanes draw their forecasts from the tasks' stream)
-template <class T, int MODE, bool STREAM = false>
+// STREAM 1: the instantiations of anm_mpc_act_stream_f64 (solve: the lanes draw their forecasts from the tasks' stream);
+// 2: those of anm_mpc_act_chain_f64 (... and roll the noise states forward from exo_z)
+template <class T, int MODE, int STREAM = 0>
 __global__ __launch_bounds__(64) void k_mpc(cptr_t C, IO io, Opts opt, int64_t n_envs, int N, int G) {
   if constexpr (Sz<T>::FITS) {
     const int lane = threadIdx.x;

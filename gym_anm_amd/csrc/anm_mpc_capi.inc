@@ -10,14 +10,18 @@ bool mpc_lds_attribute() {   // above the default per-workgroup limit: ask for t
   return hipFuncSetAttribute((const void*)mpc::k_mpc<TT, 0>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) == hipSuccess &&
          hipFuncSetAttribute((const void*)mpc::k_mpc<TT, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) == hipSuccess &&
          hipFuncSetAttribute((const void*)mpc::k_mpc<TT, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) == hipSuccess &&
-         hipFuncSetAttribute((const void*)mpc::k_mpc<TT, 0, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) == hipSuccess &&
-         hipFuncSetAttribute((const void*)mpc::k_mpc<TT, 1, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) == hipSuccess &&
-         hipFuncSetAttribute((const void*)mpc::k_mpc<TT, 2, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) == hipSuccess;
+         hipFuncSetAttribute((const void*)mpc::k_mpc<TT, 0, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) == hipSuccess &&
+         hipFuncSetAttribute((const void*)mpc::k_mpc<TT, 1, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) == hipSuccess &&
+         hipFuncSetAttribute((const void*)mpc::k_mpc<TT, 2, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) == hipSuccess &&
+         hipFuncSetAttribute((const void*)mpc::k_mpc<TT, 0, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) == hipSuccess &&
+         hipFuncSetAttribute((const void*)mpc::k_mpc<TT, 1, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) == hipSuccess &&
+         hipFuncSetAttribute((const void*)mpc::k_mpc<TT, 2, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) == hipSuccess;
 }
 
 // one group of G lanes per environment: one thread (N = 1), a part of a DPP row (N <= 16), half or all of a wavefront
-// STREAM: the instantiations whose lanes draw the forecasts from the tasks' stream (anm_mpc_act_stream_f64)
-extern "C++" template <class TT, bool STREAM = false>
+// STREAM 1: the instantiations whose lanes draw the forecasts from the tasks' stream (anm_mpc_act_stream_f64); 2: ... and
+// roll the correlated task's noise states forward from exo_z (anm_mpc_act_chain_f64)
+extern "C++" template <class TT, int STREAM = 0>
 void launch_mpc(unsigned grid, hipStream_t s, anm_mpc* m, const mpc::IO& io, const mpc::Opts& o, int64_t num_envs, int G) {
   const size_t lds_bytes = mpc::Sz<TT>::LDS_BYTES;
   if (G == 1)
@@ -122,7 +126,7 @@ int anm_mpc_get_tables(const anm_mpc* m, double* out) {
 }
 
 static int mpc_launch(anm_mpc* m, int64_t num_envs, mpc::IO io, const anm_mpc_opts* opts, void* stream, const char* who) {
-  const bool drawn = io.act.mode == ANM_MPC_FORECAST_STREAM;
+  const bool drawn = io.act.mode == ANM_MPC_FORECAST_STREAM, chain = io.act.mode == ANM_MPC_FORECAST_CHAIN;
   typedef mpc::Sz<Topo> S;
   mpc::Opts o{1e-11, 40};
   if (opts) {
@@ -142,11 +146,14 @@ static int mpc_launch(anm_mpc* m, int64_t num_envs, mpc::IO io, const anm_mpc_op
   hipStream_t s = static_cast<hipStream_t>(stream);
   if (full) {
     if constexpr (S::FITS) {
-      if (drawn) launch_mpc<Topo, true>(grid, s, m, io, o, num_envs, G);
+      if (chain) launch_mpc<Topo, 2>(grid, s, m, io, o, num_envs, G);
+      else if (drawn) launch_mpc<Topo, 1>(grid, s, m, io, o, num_envs, G);
       else launch_mpc<Topo>(grid, s, m, io, o, num_envs, G);
     } else { g_err = std::string(who) + ": with its angle rows this network has too many rows per stage for the MPC kernel"; return -1; }
+  } else if (chain) {
+    launch_mpc<TopoNoTheta, 2>(grid, s, m, io, o, num_envs, G);
   } else if (drawn) {
-    launch_mpc<TopoNoTheta, true>(grid, s, m, io, o, num_envs, G);
+    launch_mpc<TopoNoTheta, 1>(grid, s, m, io, o, num_envs, G);
   } else {
     launch_mpc<TopoNoTheta>(grid, s, m, io, o, num_envs, G);
   }
@@ -167,12 +174,13 @@ int anm_mpc_solve_f64(anm_mpc* m, int64_t num_envs, const double* p_load_forecas
   return mpc_launch(m, num_envs, io, opts, stream, "anm_mpc_solve_f64");
 }
 
-// what anm_mpc_act_f64 and anm_mpc_act_stream_f64 share: the checks of the common arguments, the Act, the launch
+// what anm_mpc_act_f64, anm_mpc_act_stream_f64 and anm_mpc_act_chain_f64 share: the checks of the common arguments, the
+// Act, the launch.  `chain`: the three device arrays of the correlated task (with `exo` its stream part), or null
 static int mpc_act(anm_mpc* m, int64_t num_envs, int32_t forecast, const double* state, const double* state_alt,
                    const uint8_t* state_same, int32_t state_dim, const int32_t* aux_index, const double* series,
                    int32_t period, const double* soc, const double* act_low, const double* act_high, double* action,
                    double* u0, double* objective, int32_t* iters, double* info, const anm_mpc_opts* opts,
-                   const anm_mpc_stream* exo, void* stream, const char* who) {
+                   const anm_mpc_stream* exo, const anm_mpc_chain* chain, void* stream, const char* who) {
   typedef mpc::Sz<Topo> S;
   const std::string w(who);
   if (!m || !state || !action || !act_low || !act_high || (m->ng + m->ns > 0 && !u0) || !objective || !iters)
@@ -192,6 +200,8 @@ static int mpc_act(anm_mpc* m, int64_t num_envs, int32_t forecast, const double*
     if (table && (!series || period <= 0 || !exo->exo_noise))
       return fail((w + ": the series-noise mode needs the task's table (series, period) and its amplitudes (exo_noise)").c_str());
   }
+  if (chain && (!chain->exo_rho || !chain->exo_innov || !chain->exo_z))
+    return fail((w + ": the chain forecast needs exo_rho, exo_innov and exo_z (device arrays)").c_str());
   if (table && !aux_index && state_dim < sdim + 1)
     return fail((w + (exo ? ": the series-noise mode" : ": a perfect forecast") + " needs the time index (aux_index, or the last column of the state)").c_str());
   if (num_envs <= 0) return 0;
@@ -208,6 +218,11 @@ static int mpc_act(anm_mpc* m, int64_t num_envs, int32_t forecast, const double*
     a.exo_high = exo->exo_high;
     a.exo_noise = exo->exo_noise;
   }
+  if (chain) {
+    a.exo_rho = chain->exo_rho;
+    a.exo_innov = chain->exo_innov;
+    a.exo_z = chain->exo_z;
+  }
   mpc::IO io{nullptr, nullptr, soc, u0, objective, iters, info, nullptr, nullptr, a, 0, 0};
   return mpc_launch(m, num_envs, io, opts, stream, who);
 }
@@ -218,7 +233,7 @@ int anm_mpc_act_f64(anm_mpc* m, int64_t num_envs, int32_t forecast, const double
                     double* u0, double* objective, int32_t* iters, double* info, const anm_mpc_opts* opts, void* stream) {
   if (forecast != ANM_MPC_FORECAST_CONSTANT && forecast != ANM_MPC_FORECAST_PERFECT) return fail("anm_mpc_act_f64: unknown forecast");
   return mpc_act(m, num_envs, forecast, state, state_alt, state_same, state_dim, aux_index, series, period, soc, act_low, act_high,
-                 action, u0, objective, iters, info, opts, nullptr, stream, "anm_mpc_act_f64");
+                 action, u0, objective, iters, info, opts, nullptr, nullptr, stream, "anm_mpc_act_f64");
 }
 
 int anm_mpc_act_stream_f64(anm_mpc* m, int64_t num_envs, const double* state, const double* state_alt,
@@ -228,5 +243,17 @@ int anm_mpc_act_stream_f64(anm_mpc* m, int64_t num_envs, const double* state, co
                            const anm_mpc_stream* exo, void* stream) {
   if (!exo) return fail("anm_mpc_act_stream_f64: null argument (anm_mpc_stream)");
   return mpc_act(m, num_envs, ANM_MPC_FORECAST_STREAM, state, state_alt, state_same, state_dim, aux_index, series, period, soc,
-                 act_low, act_high, action, u0, objective, iters, info, opts, exo, stream, "anm_mpc_act_stream_f64");
+                 act_low, act_high, action, u0, objective, iters, info, opts, exo, nullptr, stream, "anm_mpc_act_stream_f64");
+}
+
+int anm_mpc_act_chain_f64(anm_mpc* m, int64_t num_envs, const double* state, const double* state_alt,
+                          const uint8_t* state_same, int32_t state_dim, const int32_t* aux_index, const double* series,
+                          int32_t period, const double* soc, const double* act_low, const double* act_high, double* action,
+                          double* u0, double* objective, int32_t* iters, double* info, const anm_mpc_opts* opts,
+                          const anm_mpc_chain* exo, void* stream) {
+  if (!exo) return fail("anm_mpc_act_chain_f64: null argument (anm_mpc_chain)");
+  if (exo->exo.exo_mode != ANM_EXO_SERIES_NOISE)
+    return fail("anm_mpc_act_chain_f64: exo_mode must be ANM_EXO_SERIES_NOISE (the mode that has correlated noise)");
+  return mpc_act(m, num_envs, ANM_MPC_FORECAST_CHAIN, state, state_alt, state_same, state_dim, aux_index, series, period, soc,
+                 act_low, act_high, action, u0, objective, iters, info, opts, &exo->exo, exo, stream, "anm_mpc_act_chain_f64");
 }

@@ -542,3 +542,56 @@ def exo_series_corr_v(seed, env, epoch, t, aux, z, series, noise, rho, innov, lo
         x = fma_v(noise[i][aux], z1[..., i], series[i][aux])
         P[..., i] = np.where(x < low[i], low[i], np.where(x > high[i], high[i], x))
     return P, z1
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# Perfect forecast of the correlated series-noise task (``MPCAgentPerfectChain``, anm_mpc_act_chain_f64; csrc/anm_mpc.hpp,
+# Act mode 4).
+#
+# With ``exo_corr`` the draws of a step depend on the noise state of every unit, so the future of a running episode is no
+# longer a function of the step index alone: it is the step's own recurrence, rolled forward from the environment's row
+# of ``exo_z``.  NORMATIVE, for an environment with global index env, epoch = uint32(reset_count - 1), current step index
+# t (``timestep``), current table index aux and noise states z (its row of ``exo_z`` at the time of ``act()``):
+#
+# * z_(-1) = z; for i = 0 .. N-1:
+#       (P_i, z_i) = exo_series_corr(seed, env, epoch, (t + 1 + i) & MASK, (aux + 1 + i) % period, z_(i-1), ...)
+#   and stage i of the forecast is P_i.  Nothing new is defined: the key, tag, block layout, table index, the rounded
+#   product c w, the one fma of the recurrence and the one fma plus compare-selects of the map are those of the mode
+#   (above: "Correlated noise for the noisy time series") -- every z_i is produced by the operations the step will
+#   perform, in their order, so the forecast is exact and not approximately right;
+# * units, MW and the division by baseMVA, "an environment that is terminated or past its limit gets the same function"
+#   and "the horizon is not cut at ``max_episode_steps``" as for the stream forecast above;
+# * a pure function of (seed, global index, epoch, t, aux, exo_z row).  The agent only reads ``exo_z``;
+# * Anchor: rho = 0 gives z_i = fma(0, z_(i-1), w_i) = w_i for any starting z: ``exo_forecast`` of the uncorrelated task,
+#   bit for bit.
+# ---------------------------------------------------------------------------------------------------------------------
+def exo_forecast_corr(seed, env, epoch, t, N, aux, z, series, noise, rho, innov, low, high):
+    """Loads / generator potentials (MW, ``[n_load + n_gen, N]``) of the N steps after step index ``t`` of the episode
+    (seed, env, epoch) of a correlated series-noise task, from the current table index ``aux`` and noise states ``z``."""
+    period = np.asarray(series).shape[1]
+    out = np.empty((len(low), int(N)))
+    z = np.asarray(z, dtype=np.float64)
+    for i in range(int(N)):
+        out[:, i], z = exo_series_corr(seed, env, epoch, (int(t) + 1 + i) & MASK, (int(aux) + 1 + i) % period, z, series, noise,
+                                       rho, innov, low, high)
+    return out
+
+
+def exo_forecast_corr_v(seed, env_offset, reset_count, timestep, N, aux, z, series, noise, rho, innov, low, high):
+    """``exo_forecast_corr`` for the environments of a batch: ``[E, n_load + n_gen, N]`` MW from the per-environment arrays
+    ``reset_count``, ``timestep``, ``aux`` and the noise states ``z`` ``[E, n_exo]``; environment e has global index
+    ``env_offset + e``.  EXACT (``exo_series_corr_v`` applied N times): it is what the unfused path of the agent feeds the
+    solver, which has to see the bits the fused kernel computes."""
+    N = int(N)
+    rc = np.asarray(reset_count).astype(np.int64).reshape(-1)
+    E, period = rc.shape[0], np.asarray(series).shape[1]
+    epoch = ((rc - 1) & MASK).astype(np.uint64)
+    env = np.uint64(int(env_offset) & 0xFFFFFFFFFFFFFFFF) + np.arange(E, dtype=np.uint64)
+    t = np.asarray(timestep).astype(np.int64).reshape(-1)
+    aux = np.asarray(aux).astype(np.int64).reshape(-1)
+    z = np.asarray(z, dtype=np.float64).reshape(E, -1)
+    out = np.empty((E, z.shape[1], N))
+    for i in range(N):
+        out[:, :, i], z = exo_series_corr_v(seed, env, epoch, ((t + 1 + i) & MASK).astype(np.uint64), (aux + 1 + i) % period, z,
+                                            series, noise, rho, innov, low, high)
+    return out

@@ -590,6 +590,34 @@ int anm_mpc_act_stream_f64(anm_mpc* m, int64_t num_envs, const double* state, co
                            double* u0, double* objective, int32_t* iters, double* info, const anm_mpc_opts* opts,
                            const anm_mpc_stream* exo, void* stream);
 
+/* The perfect forecast of the series-noise task with CORRELATED noise (an anm_env_config_corr): the draws of such a task
+ * depend on the noise state of every unit, so stage i of environment e is the step kernels' own recurrence applied i + 1
+ * times to the environment's row of exo_z,
+ *     z_(-1) = exo_z[e],   (P_i, z_i) = one real step at step index timestep[e] + 1 + i and table index (t + 1 + i) mod period
+ *     from z_(i-1)   (anm_env_config_corr: t = exo_innov w, z' = fma(exo_rho, z, t), the map, the clip)
+ * with the stream, key, epoch and table index of anm_mpc_stream.  The stages are the lanes of the solve: each draws its own
+ * factor w, the states travel up the group one stage per exchange (N - 1 exchanges per unit) -- every z_i by the very
+ * operations the step kernel will perform, so the forecast is exact.  Still ONE launch, and exo_z is only read.  The same
+ * pure function for an environment that is terminated or past its limit; the horizon is not cut at the limit; exo_rho = 0
+ * gives the stream forecast of the uncorrelated task bit for bit.  gym_anm_amd/rng.py (exo_forecast_corr) is the
+ * specification.  Every pointer is a DEVICE pointer (anm_env_config_corr takes exo_rho and exo_innov as host arrays: the
+ * caller keeps device copies; exo_z is the array the configuration names). */
+typedef struct anm_mpc_chain {
+  anm_mpc_stream exo;         /* exo_mode = ANM_EXO_SERIES_NOISE */
+  const double* exo_rho;      /* [n_load + n_gen] */
+  const double* exo_innov;    /* [n_load + n_gen] */
+  const double* exo_z;        /* [num_envs][n_load + n_gen]: the noise states as the last step (or reset) left them */
+} anm_mpc_chain;
+#define ANM_MPC_FORECAST_CHAIN 4
+/* anm_mpc_act_stream_f64 with that forecast (anm_mpc_act_f64 keeps refusing 3 and 4 as unknown).  Refused: a NULL struct; an
+ * exo_mode other than ANM_EXO_SERIES_NOISE; exo_rho, exo_innov or exo_z NULL; everything anm_mpc_act_stream_f64 refuses in
+ * series-noise mode.  num_envs <= 0 returns 0. */
+int anm_mpc_act_chain_f64(anm_mpc* m, int64_t num_envs, const double* state, const double* state_alt,
+                          const uint8_t* state_same, int32_t state_dim, const int32_t* aux_index, const double* series,
+                          int32_t period, const double* soc, const double* act_low, const double* act_high, double* action,
+                          double* u0, double* objective, int32_t* iters, double* info, const anm_mpc_opts* opts,
+                          const anm_mpc_chain* exo, void* stream);
+
 /* Offsets of each quantity inside one row of `full` (p.u. / rad), in the order of the reference's
  * STATE_VARIABLES (constants.py:31-48): bus_p, bus_q, bus_v_magn, bus_v_ang, bus_i_magn,
  * bus_i_ang [n_bus each], dev_p, dev_q [n_dev each], des_soc [n_des], gen_p_max [n_gen],

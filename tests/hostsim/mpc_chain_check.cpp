@@ -1,0 +1,129 @@
+// mpc_chain_check.cpp -- a stand-alone program (tests/test_mpc_chain_spec.py): the chain forecast of the MPC kernel,
+// mpc::act_chain_value / mpc::chain_sweep (gym_anm_amd/csrc/anm_mpc.hpp, Act mode ANM_MPC_FORECAST_CHAIN), compiled for the
+// host and run the way k_mpc runs it: a wavefront of 64 lanes, one host thread each, groups of G = 2^k >= N lanes, one
+// environment per group, lane = stage -- idle lanes (stage >= N, environment >= E) and neighbouring groups included.  The
+// bit patterns it prints are compared with gym_anm_amd/rng.py (exo_forecast_corr).  Built once per topology header
+// (-DANM_TOPO_HEADER=...): a generated topology, and an MPC size class (is_padded).
+//
+// stdin (whitespace separated; floating-point values as the decimal value of their 64 bit patterns):
+//   seed env_offset E N nl ng period base
+//   E x (timestep reset_count aux)
+//   low[n]  high[n]  rho[n]  innov[n]  z[E n]  series[n period]  noise[n period]        (n = nl + ng)
+// stdout: one line per (environment, stage, unit), the value's bit pattern in hex.
+#include <pthread.h>
+
+#include <cinttypes>
+#include <cstdio>
+#include <cstring>
+#include <thread>
+#include <vector>
+
+#include ANM_TOPO_HEADER
+#include "../../gym_anm_amd/csrc/anm_mpc.hpp"
+
+using namespace anm;
+
+// the part of mpc::WaveGroup the sweep uses: up() is the value of the lane before this one in the WAVEFRONT (row_shr:1 /
+// wave_shr:1), 0 at stage 0 -- every lane of the wavefront takes part in every exchange
+struct HostWave {
+  double slot[64];
+  pthread_barrier_t bar;
+  HostWave() { pthread_barrier_init(&bar, nullptr, 64); }
+  ~HostWave() { pthread_barrier_destroy(&bar); }
+};
+struct HostLane {
+  HostWave* w;
+  int lane, st;
+  int stage() const { return st; }
+  double up(double v) const {
+    w->slot[lane] = v;
+    pthread_barrier_wait(&w->bar);
+    const double r = (st == 0 || lane == 0) ? 0.0 : w->slot[lane - 1];
+    pthread_barrier_wait(&w->bar);
+    return r;
+  }
+};
+
+static bool read_u64(uint64_t& v) { return std::scanf("%" SCNu64, &v) == 1; }
+static bool read_f64(double& d) {
+  uint64_t v;
+  if (!read_u64(v)) return false;
+  std::memcpy(&d, &v, sizeof d);
+  return true;
+}
+static bool read_all(std::vector<double>& a) {
+  for (double& d : a)
+    if (!read_f64(d)) return false;
+  return true;
+}
+
+int main() {
+  uint64_t seed, env_offset, E, N, nl, ng, period;
+  double base;
+  if (!(read_u64(seed) && read_u64(env_offset) && read_u64(E) && read_u64(N) && read_u64(nl) && read_u64(ng) && read_u64(period) &&
+        read_f64(base)))
+    return 2;
+  constexpr bool PAD = mpc::is_padded<Topo>::value;
+  if (nl > uint64_t(Topo::NLOAD) || ng > uint64_t(Topo::NGEN) || (!PAD && (nl != uint64_t(Topo::NLOAD) || ng != uint64_t(Topo::NGEN)))) return 3;
+  if (E == 0 || E > 4096 || N == 0 || N > 64 || period == 0 || period > 4096) return 3;
+  const int n = int(nl + ng), state_dim = 2 * Topo::ND + Topo::NDES + Topo::NGEN + 1;
+  std::vector<int32_t> timestep(E), reset_count(E);
+  std::vector<double> state(E * state_dim, 0.0);
+  for (uint64_t e = 0; e < E; ++e) {
+    uint64_t t, r, a;
+    if (!(read_u64(t) && read_u64(r) && read_u64(a))) return 2;
+    timestep[e] = int32_t(t);
+    reset_count[e] = int32_t(r);
+    state[e * state_dim + state_dim - 1] = double(a);
+  }
+  std::vector<double> low(n), high(n), rho(n), innov(n), z(E * n), series(size_t(n) * period), noise(size_t(n) * period);
+  if (!(read_all(low) && read_all(high) && read_all(rho) && read_all(innov) && read_all(z) && read_all(series) && read_all(noise))) return 2;
+
+  mpc::Act a{};
+  a.mode = ANM_MPC_FORECAST_CHAIN;
+  a.state = state.data();
+  a.state_dim = state_dim;
+  a.series = series.data();
+  a.period = int(period);
+  a.base = base;
+  a.exo_mode = ANM_EXO_SERIES_NOISE;
+  a.seed = seed;
+  a.env_offset = env_offset;
+  a.timestep = timestep.data();
+  a.reset_count = reset_count.data();
+  a.exo_low = low.data();
+  a.exo_high = high.data();
+  a.exo_noise = noise.data();
+  a.exo_rho = rho.data();
+  a.exo_innov = innov.data();
+  a.exo_z = z.data();
+
+  int G = 1;
+  while (G < int(N)) G *= 2;
+  const int per_wave = 64 / G;
+  const int64_t waves = (int64_t(E) + per_wave - 1) / per_wave;
+  std::vector<double> out(E * N * n, 0.0);
+  HostWave wave;
+  std::vector<std::thread> th;
+  for (int lane = 0; lane < 64; ++lane)
+    th.emplace_back([&, lane]() {
+      const HostLane x{&wave, lane, lane % G};
+      for (int64_t b = 0; b < waves; ++b) {     // (k_mpc: env = block * (64 / G) + lane / G, on = env < n_envs && stage < N)
+        const int64_t env = b * per_wave + lane / G;
+        const bool on = env < int64_t(E) && x.st < int(N);
+        mpc::StreamAt at{0, 0, 0};
+        if (on) at = mpc::act_stream_at(a, env, x.st);
+        for (int u = 0; u < n; ++u) {
+          const double v = mpc::act_chain_value(a, at, on, env, u, n, int(N), x);
+          if (on) out[(env * N + x.st) * n + u] = v;
+        }
+      }
+    });
+  for (auto& t : th) t.join();
+  for (double v : out) {
+    uint64_t bits;
+    std::memcpy(&bits, &v, sizeof bits);
+    std::printf("%016" PRIx64 "\n", bits);
+  }
+  return 0;
+}
