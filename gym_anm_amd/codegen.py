@@ -545,6 +545,39 @@ def row_plan(n_bus, tt):
     )  # fmt: skip
 
 
+def row_pair_plan(n_bus, tt):
+    """The row plan with TWO lanes per bus (csrc/anm_group.hpp: newton_row_pairs).  Replica 0 of a bus keeps its lane of
+    row_plan; replica 1 takes an unused lane of the same bank: the next lane for a bus with children (rule (a) leaves its
+    bank-mates unused), the lane `number of leaves` further on for a leaf, so a leaf bank holds its leaves, then their
+    replicas.  Both replicas carry the same values of everything except the rows of Lk = Jpb Di, Sc = Lk Jbp and Lr = Lk r:
+    replica 0 forms row 0 (Sc.a, Sc.b, Lr0), replica 1 row 1 (Sc.c, Sc.d, Lr1).  The banks are those of row_plan, so every
+    destination bank of a hand-over holds its consumers, their replicas and unused lanes, nothing else.
+    A leaf bank with 3 or 4 leaves has no room for the replicas: None (the topology keeps one lane per bus).
+    Returns LANE / LANE1 (lane of replica 0 / 1 of each bus; bus 0: -1), LP (per lane: the word of row_plan | replica << 21;
+    0: unused lane) and the hand-overs of row_plan with the source lane PER VALUE: CH_SRC0 (Sc.a, Sc.b, Lr0: replica 0 of the
+    child) and CH_SRC1 (Sc.c, Sc.d, Lr1: replica 1); the parent's voltage and step (PAR) and the W products (WS) are equal
+    in both replicas and are taken from replica 0."""
+    rp = row_plan(n_bus, tt)
+    if rp is None:
+        return None
+    maxch = tt["MAXCH"]
+    has_ch = lambda b: any(c > 0 for c in tt["CH"][b * maxch:(b + 1) * maxch])  # noqa: E731
+    lane, lane1 = rp["LANE"], [-1] * n_bus
+    for bs in rp["BANKS"]:
+        if not has_ch(bs[0]) and len(bs) > 2:
+            return None
+        for b in bs:
+            lane1[b] = lane[b] + len(bs)
+    lp = list(rp["LP"])
+    for b in range(1, n_bus):
+        lp[lane1[b]] = lp[lane[b]] | (1 << 21)
+    rep1 = {lane[b]: lane1[b] for b in range(1, n_bus)}
+    out = {k: list(rp[k]) for k in ("LANE", "BANKS", "PAR_D", "PAR_SRC", "PAR_BANK", "PAR_OFF", "CH_H", "CH_BANK", "CH_OFF",
+                                    "WS_SRC", "WS_BANK")}  # fmt: skip
+    out.update(LANE1=lane1, LP=lp, CH_SRC0=list(rp["CH_SRC"]), CH_SRC1=[rep1[l] for l in rp["CH_SRC"]])
+    return out
+
+
 def _arr(name, values, typ="int"):
     vals = list(values)
     body = ", ".join(str(int(v)) for v in vals) if vals else "0"
@@ -704,6 +737,17 @@ def emit_header(topo, name=None) -> str:
               _arr("T_ROW_PAR_SRC", rp["PAR_SRC"]), _arr("T_ROW_PAR_BANK", rp["PAR_BANK"]), _arr("T_ROW_PAR_OFF", rp["PAR_OFF"]),
               _arr("T_ROW_CH_SRC", rp["CH_SRC"]), _arr("T_ROW_CH_BANK", rp["CH_BANK"]), _arr("T_ROW_CH_OFF", rp["CH_OFF"]),
               _arr("T_ROW_WS_SRC", rp["WS_SRC"]), _arr("T_ROW_WS_BANK", rp["WS_BANK"])]
+    pp = row_pair_plan(n_bus, tt) if tt is not None else None
+    if pp is None:
+        pp = {k: [0] for k in ("LANE1", "LP", "CH_SRC0", "CH_SRC1")}
+        lines += ["  static constexpr int T_ROW2 = 0;"]
+    else:
+        lines += ["  // the row layout with two lanes per bus (codegen.row_pair_plan): lane of each bus's replica 1, packed row of each lane",
+                  "  // (T_ROW_LP | replica << 21), source lane of every fold per value (rows 0 / 1 of Sc and Lr); the banks, the offsets and",
+                  "  // the sources of the parent's and the W hand-overs are those of T_ROW_*",
+                  "  static constexpr int T_ROW2 = 1;"]
+    lines += [_arr("T_ROW2_LANE1", pp["LANE1"]), _arr("T_ROW2_LP", pp["LP"], "unsigned"),
+              _arr("T_ROW2_CH_SRC0", pp["CH_SRC0"]), _arr("T_ROW2_CH_SRC1", pp["CH_SRC1"])]
     lines += [
         "};",
         "}  // namespace",

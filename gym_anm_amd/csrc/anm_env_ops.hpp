@@ -48,7 +48,7 @@ struct SolverOpts {
   double tol;
   int max_iter;
   int handoff;  // >= 0: Newton iterations in thread mode before a running solve moves to a lane group; < 0: never
-  int rowc = 0; // handed-over solves one per 16-lane row or one per lane group (group::continue_collective): 0 policy, 1 rows, -1 groups
+  int rowc = 0; // handed-over solves one per 16-lane row or one per lane group (group::continue_collective): 0 policy, 1 rows, -1 groups, 2 policy with one lane per bus
 };
 
 template <class T>

@@ -363,6 +363,60 @@ ANM_ROW_TPL __device__ __forceinline__ void row_step_lead(float& r0, float& r1, 
   ANM_ROW_ASM_LEAD(ANM_ROW_LEAD_STEP("f32"), ANM_ROW_FMA4_F32, ([a0] "+v"(r0), [a1] "+v"(r1), [p0] "=&v"(p0), [p1] "=&v"(p1)),
                    ([ia] "v"(Di.a), [ib] "v"(Di.b), [ic] "v"(Di.c), [id] "v"(Di.d), [ja] "v"(ja), [jb] "v"(jb)));
 }
+// The fold on TWO lanes per bus (codegen.row_pair_plan; newton_row_pairs below): lane N holds row 0 of the child's Schur
+// complement and reduced right-hand side -- (s0, s1, l) = (Sc.a, Sc.b, Lr0) -- and lane M row 1, (Sc.c, Sc.d, Lr1), in the
+// SAME three registers.  Six instructions per (N, M, bank mask) triple like row_fold, the same six subtractions; up to four
+// triples to a statement.
+//   row_fold2_lead  s1 += ka jb, l += ka r0 (the fmacs that finish my row of Sc = Lk Jbp and my entry of Lr = Lk r; s1 comes
+//                   in holding kb Jbp.d, l holding kb r1), then the folds, those of s0 first: s1 at distance 4, l at distance 5
+#define ANM_ROW2_TPL                                                                                                   \
+  template <int N0, int M0, int B0, int N1 = -1, int M1 = -1, int B1 = 0, int N2 = -1, int M2 = -1, int B2 = 0, int N3 = -1, \
+            int M3 = -1, int B3 = 0>
+#define ANM_ROW2_IMM                                                                                                   \
+  [n0] "n"(N0), [m0] "n"(M0), [b0] "n"(B0), [n1] "n"(N1 < 0 ? 0 : N1), [m1] "n"(M1 < 0 ? 0 : M1), [b1] "n"(B1),          \
+  [n2] "n"(N2 < 0 ? 0 : N2), [m2] "n"(M2 < 0 ? 0 : M2), [b2] "n"(B2), [n3] "n"(N3 < 0 ? 0 : N3), [m3] "n"(M3 < 0 ? 0 : M3), \
+  [b3] "n"(B3)
+#define ANM_ROW2_ASM_LEAD(LEAD, BODY, OUTS, INS)                                                                        \
+  do {                                                                                                                 \
+    if constexpr (N1 < 0) asm volatile(LEAD BODY("n0", "m0", "b0") : ANM_ROW_UNPAR OUTS : ANM_ROW_UNPAR INS, ANM_ROW2_IMM); \
+    else if constexpr (N2 < 0)                                                                                         \
+      asm volatile(LEAD BODY("n0", "m0", "b0") BODY("n1", "m1", "b1") : ANM_ROW_UNPAR OUTS : ANM_ROW_UNPAR INS, ANM_ROW2_IMM); \
+    else if constexpr (N3 < 0)                                                                                         \
+      asm volatile(LEAD BODY("n0", "m0", "b0") BODY("n1", "m1", "b1") BODY("n2", "m2", "b2") : ANM_ROW_UNPAR OUTS       \
+                   : ANM_ROW_UNPAR INS, ANM_ROW2_IMM);                                                                 \
+    else                                                                                                               \
+      asm volatile(LEAD BODY("n0", "m0", "b0") BODY("n1", "m1", "b1") BODY("n2", "m2", "b2") BODY("n3", "m3", "b3")     \
+                   : ANM_ROW_UNPAR OUTS : ANM_ROW_UNPAR INS, ANM_ROW2_IMM);                                            \
+  } while (0)
+#define ANM_ROW2_FOLD6(F, n, m, b)                                                                                   \
+  "v_fmac_" F "_dpp %[a], -%[s0], %[one]" ANM_ROW_CTL(n, b) "v_fmac_" F "_dpp %[c], -%[s0], %[one]" ANM_ROW_CTL(m, b)  \
+  "v_fmac_" F "_dpp %[b], -%[s1], %[one]" ANM_ROW_CTL(n, b) "v_fmac_" F "_dpp %[d], -%[s1], %[one]" ANM_ROW_CTL(m, b)  \
+  "v_fmac_" F "_dpp %[r0], -%[l], %[one]" ANM_ROW_CTL(n, b) "v_fmac_" F "_dpp %[r1], -%[l], %[one]" ANM_ROW_CTL(m, b)
+#define ANM_ROW2_FOLD6_F64(n, m, b) ANM_ROW2_FOLD6("f64", n, m, b)
+#define ANM_ROW2_FOLD6_F32(n, m, b) ANM_ROW2_FOLD6("f32", n, m, b)
+#define ANM_ROW2_LEAD_FOLD(F) "v_fmac_" F " %[s1], %[ka], %[jb]\nv_fmac_" F " %[l], %[ka], %[r0]\n"
+ANM_ROW2_TPL __device__ __forceinline__ void row_fold2(Blk<double>& D, double& r0, double& r1, double s0, double s1, double l, double one) {
+  ANM_ROW2_ASM_LEAD("s_nop 1\n", ANM_ROW2_FOLD6_F64,
+                    ([a] "+v"(D.a), [b] "+v"(D.b), [c] "+v"(D.c), [d] "+v"(D.d), [r0] "+v"(r0), [r1] "+v"(r1)),
+                    ([s0] "v"(s0), [s1] "v"(s1), [l] "v"(l), [one] "v"(one)));
+}
+ANM_ROW2_TPL __device__ __forceinline__ void row_fold2(Blk<float>& D, float& r0, float& r1, float s0, float s1, float l, float one) {
+  ANM_ROW2_ASM_LEAD("s_nop 1\n", ANM_ROW2_FOLD6_F32,
+                    ([a] "+v"(D.a), [b] "+v"(D.b), [c] "+v"(D.c), [d] "+v"(D.d), [r0] "+v"(r0), [r1] "+v"(r1)),
+                    ([s0] "v"(s0), [s1] "v"(s1), [l] "v"(l), [one] "v"(one)));
+}
+ANM_ROW2_TPL __device__ __forceinline__ void row_fold2_lead(Blk<double>& D, double& r0, double& r1, double s0, double& s1, double& l,
+                                                            double ka, double jb, double one) {
+  ANM_ROW2_ASM_LEAD(ANM_ROW2_LEAD_FOLD("f64"), ANM_ROW2_FOLD6_F64,
+                    ([a] "+v"(D.a), [b] "+v"(D.b), [c] "+v"(D.c), [d] "+v"(D.d), [r0] "+v"(r0), [r1] "+v"(r1), [s1] "+v"(s1), [l] "+v"(l)),
+                    ([s0] "v"(s0), [ka] "v"(ka), [jb] "v"(jb), [one] "v"(one)));
+}
+ANM_ROW2_TPL __device__ __forceinline__ void row_fold2_lead(Blk<float>& D, float& r0, float& r1, float s0, float& s1, float& l, float ka,
+                                                            float jb, float one) {
+  ANM_ROW2_ASM_LEAD(ANM_ROW2_LEAD_FOLD("f32"), ANM_ROW2_FOLD6_F32,
+                    ([a] "+v"(D.a), [b] "+v"(D.b), [c] "+v"(D.c), [d] "+v"(D.d), [r0] "+v"(r0), [r1] "+v"(r1), [s1] "+v"(s1), [l] "+v"(l)),
+                    ([s0] "v"(s0), [ka] "v"(ka), [jb] "v"(jb), [one] "v"(one)));
+}
 // Two integer statements of the stop test that the compiler makes longer than the instruction set needs:
 //   row_count   it + 1 on the lanes of the wavefront mask m, it elsewhere: ONE add with carry-in (select and add: two)
 //   row_pick    (lo(m) & glo) | (hi(m) & ghi): v_and_b32 + v_and_or_b32 (and, and, or: three)
@@ -405,6 +459,21 @@ __device__ __forceinline__ void row_points(F&& f) {
       std::integral_constant<int, row_src<T, W>(i + 1, HI)>{}, std::integral_constant<int, row_bank<T, W>(i + 1, HI)>{},
       std::integral_constant<int, row_src<T, W>(i + 2, HI)>{}, std::integral_constant<int, row_bank<T, W>(i + 2, HI)>{},
       std::integral_constant<int, row_src<T, W>(i + 3, HI)>{}, std::integral_constant<int, row_bank<T, W>(i + 3, HI)>{});
+  });
+}
+// the folds [LO, HI) of table CH on two lanes per bus (codegen.row_pair_plan): (source of row 0, source of row 1, bank mask)
+#define ANM_ROW2_PARAMS auto N0, auto M0, auto B0, auto N1, auto M1, auto B1, auto N2, auto M2, auto B2, auto N3, auto M3, auto B3
+#define ANM_ROW2_ARGS N0, M0, B0, N1, M1, B1, N2, M2, B2, N3, M3, B3
+template <class T, int LO, int HI, class F>
+__device__ __forceinline__ void row_points2(F&& f) {
+  static_for<0, (HI - LO + 3) / 4>([&](auto Q) {
+    constexpr int i = LO + 4 * int(Q);
+#define ANM_ROW2_TRIPLE(k)                                                                                     \
+  std::integral_constant<int, (k) >= HI ? -1 : T::T_ROW2_CH_SRC0[(k) >= HI ? 0 : (k)]>{},                           \
+  std::integral_constant<int, (k) >= HI ? -1 : T::T_ROW2_CH_SRC1[(k) >= HI ? 0 : (k)]>{},                           \
+  std::integral_constant<int, row_bank<T, ROW_CH>((k), HI)>{}
+    f(std::bool_constant<int(Q) == 0>{}, ANM_ROW2_TRIPLE(i), ANM_ROW2_TRIPLE(i + 1), ANM_ROW2_TRIPLE(i + 2), ANM_ROW2_TRIPLE(i + 3));
+#undef ANM_ROW2_TRIPLE
   });
 }
 
@@ -1052,16 +1121,18 @@ template <class T>
 struct RowView {
   int b;                   // bus played (0: unused lane)
   bool lane_bus;
+  bool rep;                // two lanes per bus (codegen.row_pair_plan): this lane is replica 1 of its bus
   int height, depth;
   double ybb_r, ybb_i, ybp_r, ybp_i, ypb_r, ypb_i;   // Y_bb, Y_b,parent, Y_parent,b (unused lanes: 0)
   unsigned long long rmask; // lanes of my row
 
-  __device__ __forceinline__ void init(cptr_t C) {
+  __device__ __forceinline__ void init(cptr_t C, bool pairs = false) {
     typedef Layout<T> L;
     const int lane = threadIdx.x & 63;
-    const unsigned w0 = T::T_ROW_LP[lane & 15];
+    const unsigned w0 = pairs ? T::T_ROW2_LP[lane & 15] : T::T_ROW_LP[lane & 15];
     b = int(w0 & 0x7Fu);
     lane_bus = b > 0;
+    rep = ((w0 >> 21) & 1u) != 0u;
     height = int((w0 >> 7) & 0x7Fu) - 1;
     depth = int((w0 >> 14) & 0x7Fu) - 1;
     rmask = 0xFFFFull << (lane & 48);
@@ -1211,17 +1282,152 @@ __device__ __forceinline__ void newton_rows(const RowView<T>& V, bool rvalid, do
   }
 }
 
-// continue_in_groups with four solves a pass, one per row: the same LDS slots, the same results in st.it / st.diff.
+// The sign of x flipped on the lanes whose `flip` holds the sign bit (0 elsewhere): one v_xor_b32 on the high word.
+__device__ __forceinline__ double row_flip(double x, unsigned flip) {
+  return __hiloint2double(__double2hiint(x) ^ int(flip), __double2loint(x));
+}
+__device__ __forceinline__ float row_flip(float x, unsigned flip) { return __uint_as_float(__float_as_uint(x) ^ flip); }
+
+// newton_rows on TWO lanes per bus (codegen.row_pair_plan): same arguments, same results.  Both lanes of a bus are full
+// replicas -- the same loads, W products, Dg, Di, step and update, so nothing ever moves between them -- except that each
+// forms ONE row of Lk = Jpb Di, Sc = Lk Jbp and Lr = Lk r: replica 0 row 0, replica 1 row 1, by the source expressions of
+// blk_mul and of newton_rows' Lr0 / Lr1 restricted to that row.  A fold names replica 0 of the child for Sc.a, Sc.b and Lr0
+// and replica 1 for Sc.c, Sc.d and Lr1 (row_fold2); every other hand-over names replica 0.  Every floating-point operation
+// that reaches a result is that of newton_rows on the same operands in the same order: the same bits.
 template <class T, class JT>
+__device__ __forceinline__ void newton_row_pairs(const RowView<T>& V, bool rvalid, double& vm, double& cs, double& sn, double bus_p,
+                                                 double bus_q, int& it, unsigned& tb, unsigned& tn, double tol, int max_iter) {
+  static_assert(T::T_ROW != 0 && T::T_ROW2 != 0, "codegen.row_pair_plan: the topology has no row layout with two lanes per bus");
+  const double ybb_r = V.ybb_r, ybb_i = V.ybb_i, ybp_r = V.ybp_r, ybp_i = V.ybp_i, ypb_r = V.ypb_r, ypb_i = V.ypb_i;
+  const bool isbus = V.lane_bus && rvalid;
+  // both replicas are bus lanes: they hold identical F, so every ballot says what it says with one lane per bus
+  const unsigned long long busm = __builtin_amdgcn_uicmp(isbus ? 1u : 0u, 0u, ICMP_NE);
+  unsigned long long runm = busm;   // (see newton_rows: what an unused lane holds reaches no decision and no result)
+  const unsigned glo = unsigned(V.rmask & busm), ghi = unsigned((V.rmask & busm) >> 32);   // bus lanes of my row
+  const bool rep = V.rep;
+  const unsigned flip = rep ? 0x80000000u : 0u;
+  tb = 0u; tn = 0u;
+  it -= rvalid ? 1 : 0;        // the first trip only evaluates: its `it += running` is undone here
+  double vpr = 1.0, vpi = 0.0;
+  double one = 1.0;
+  asm volatile("" : "+v"(one));
+  const JT onej = JT(one);
+  __builtin_amdgcn_s_waitcnt(0);
+  for (;;) {
+    double vr, vi, m2;
+    if constexpr (T::T_ROW_PAR_N == 0) {
+      vr = vm * cs; vi = vm * sn; m2 = vm * vm;
+    } else {
+      row_points<T, ROW_PAR, 0, T::T_ROW_PAR_N>([&](auto FIRST, ANM_ROW_PARAMS) {
+        if constexpr (FIRST) row_mov_lead<ANM_ROW_ARGS>(vpr, vpi, vr, vi, m2, vm, cs, sn);
+        else row_mov<ANM_ROW_ARGS>(vpr, vpi, vr, vi);
+      });
+    }
+    const double wbb_r = ybb_r * m2, wbb_i = -(ybb_i * m2);
+    const double pr = fma(vr, vpr, vi * vpi), pim = fma(vi, vpr, -(vr * vpi));
+    const double wbp_r = fma(ybp_r, pr, ybp_i * pim), wbp_i = fma(ybp_r, pim, -(ybp_i * pr));
+    const double wpb_r = fma(ypb_r, pr, -(ypb_i * pim)), nwpb_i = fma(ypb_r, pim, ypb_i * pr);   // (imaginary part: sign flipped)
+    double sr, si;
+    if constexpr (T::T_ROW_CH_N == 0) {
+      sr = wbb_r + wbp_r; si = wbb_i + wbp_i;
+    } else {
+      row_points<T, ROW_WS, 0, T::T_ROW_CH_N>([&](auto FIRST, ANM_ROW_PARAMS) {
+        if constexpr (FIRST) row_wsum_lead<ANM_ROW_ARGS>(sr, si, wbb_r, wbp_r, wbb_i, wbp_i, wpb_r, nwpb_i, one);
+        else row_wsum<ANM_ROW_ARGS>(sr, si, wpb_r, nwpb_i, one);
+      });
+    }
+    const double fr = sr - bus_p, fi = si - bus_q;
+    const unsigned long long badm = __builtin_amdgcn_fcmp(fmax(fabs(fr), fabs(fi)), tol, FCMP_UGT);
+    const unsigned long long nanm = __builtin_amdgcn_fcmp(fr, fi, FCMP_UNO);
+    tb = row_pick(badm, glo, ghi);
+    tn = row_pick(nanm, glo, ghi);
+    it = row_count(it, runm);   // the update applied in the previous trip
+    runm &= __builtin_amdgcn_uicmp(tb, 0u, ICMP_NE) & ~__builtin_amdgcn_uicmp(tn, 0u, ICMP_NE) &
+            __builtin_amdgcn_sicmp(it, max_iter, ICMP_SLT);   // NaN > tol is false, like the reference
+    const bool all_done = runm == 0ull;
+
+    // ---- Jacobian blocks: own diagonal, the coupling Jbp, and MY ROW of Jpb = {-nwpb_i, wpb_r, -wpb_r, -nwpb_i}, selected
+    // once per trip: row 0 is (-nwpb_i, wpb_r), row 1 (-wpb_r, -nwpb_i)
+    Blk<JT> Dg = Blk<JT>{JT(wbb_i - si), JT(sr + wbb_r), JT(sr - wbb_r), JT(si + wbb_i)};
+    const Blk<JT> Jbp = Blk<JT>{JT(wbp_i), JT(wbp_r), JT(-wbp_r), JT(wbp_i)};
+    const JT jpr = JT(wpb_r), jpi = JT(nwpb_i);
+    const JT ja = -(rep ? jpr : jpi), jb = row_flip(rep ? jpi : jpr, flip);
+    JT r0 = JT(fr), r1 = JT(fi);
+    // ---- the unconditional schedule of newton_rows: every lane runs every level's pivot and every depth's step.
+    // S0 / S1: my row of Sc (S1 is finished by the lead of the next level's folds: it holds Lk.b Jbp.d, resp. Lk.d Jbp.d);
+    // Lr: my entry of Lr = Lk r (finished there as well: it holds Lk.b r1, resp. Lk.d r1); Lka: Lk.a, resp. Lk.c.
+    Blk<JT> Di = Dg;
+    JT S0 = JT(0), S1 = JT(0), Lr = JT(0), Lka = JT(0);
+    static_for<0, T::T_MAXH + 1>([&](auto H) {
+      constexpr int h = H;
+      if constexpr (h > 0) {
+        static_assert(T::T_ROW_CH_OFF[h + 1] > T::T_ROW_CH_OFF[h], "a level above 0 folds the child that makes it one");
+        row_points2<T, T::T_ROW_CH_OFF[h], T::T_ROW_CH_OFF[h + 1]>([&](auto FIRST, ANM_ROW2_PARAMS) {
+          if constexpr (FIRST) row_fold2_lead<ANM_ROW2_ARGS>(Dg, r0, r1, S0, S1, Lr, Lka, Jbp.b, onej);
+          else row_fold2<ANM_ROW2_ARGS>(Dg, r0, r1, S0, S1, Lr, onej);
+        });
+      }
+      Di = blk_inv_fast(Dg);
+      if constexpr (h < T::T_MAXH) {
+        Lka = fm(ja, Di.a, jb * Di.c);                 // blk_mul(Jpb, Di), my row
+        const JT Lkb = fm(ja, Di.b, jb * Di.d);
+        S0 = fm(Lka, Jbp.a, Lkb * Jbp.c);              // blk_mul(Lk, Jbp), my row
+        S1 = Lkb * Jbp.d;
+        Lr = Lkb * r1;
+      }
+    });
+    JT d0, d1;
+    static_for<1, T::T_MAXD + 1>([&](auto Dd) {
+      constexpr int dd = Dd;
+      static_assert(T::T_ROW_PAR_OFF[dd + 1] > T::T_ROW_PAR_OFF[dd], "a depth above 0 has a parent's step to receive");
+      row_points<T, ROW_PAR, T::T_ROW_PAR_OFF[dd], T::T_ROW_PAR_OFF[dd + 1]>([&](auto FIRST, ANM_ROW_PARAMS) {
+        if constexpr (FIRST) row_step_lead<ANM_ROW_ARGS>(r0, r1, d0, d1, Di, Jbp.a, Jbp.b);
+        else row_fma<ANM_ROW_ARGS>(r0, r1, d0, d1, Jbp.a, Jbp.b);
+      });
+    });
+    d0 = fm(Di.a, r0, Di.b * r1);
+    d1 = fm(Di.c, r0, Di.d * r1);
+    // ---- update of the running rows (see newton_groups, VPOLY)
+    const bool upd = __builtin_amdgcn_inverse_ballot_w64(runm);
+    const double dth = double(d0);
+    const unsigned long long bigm = __builtin_amdgcn_fcmp(fabs(dth), 0.78, FCMP_UGT) & runm;  // NaN counts
+    double sd_, cd_;
+    if (bigm == 0ull) {
+      sincos_kernel<true>(dth, 0, sd_, cd_);
+    } else {
+      sincos_medium<true>(dth, sd_, cd_);
+      const bool ish = !(fabs(dth) < SINCOS_MEDIUM_MAX);
+      if ((__builtin_amdgcn_uicmp(ish ? 1u : 0u, 0u, ICMP_NE) & runm) != 0ull) {
+        const SinCos r = sincos_huge(dth);
+        sd_ = ish ? r.s : sd_;
+        cd_ = ish ? r.c : cd_;
+      }
+    }
+    if (upd) {
+      vm = fma(-double(d1), fabs(vm), vm);
+      const double t1 = sn * sd_, t2 = cs * sd_;
+      cs = fma3<false>(cs, cd_, t1);
+      sn = fma3<true>(sn, cd_, t2);
+    }
+    if (all_done) break;
+  }
+}
+
+// continue_in_groups with four solves a pass, one per row: the same LDS slots, the same results in st.it / st.diff.
+// PAIRS: the topology has a pair plan, and the pass runs on two lanes per bus (newton_row_pairs; only replica 0 of a bus
+// writes its results back) unless one_lane (uniform) asks for newton_rows.  The hand-over around the loop is ONE copy for
+// both: a second copy of it costs the kernels that hold an environment per lane 20 and more registers.
+template <class T, class JT, bool PAIRS = false>
 __device__ __forceinline__ void continue_in_rows(cptr_t C, EnvWork<T>& w, PFState<T>& st, bool mine, double tol, int max_iter,
-                                                 double* lds) {
+                                                 double* lds, bool one_lane = true) {
   typedef Slot<T> S;
   constexpr int NR = 4, NB = T::NB;
   static_assert(Shape<T>::NG >= NR, "the hand-over slots of the wavefront hold a solve per row");
   const int lane = threadIdx.x & 63;
   const int row = lane >> 4;
+  const bool pairs = PAIRS && !one_lane;
   RowView<T> V;
-  V.init(C);
+  V.init(C, pairs);
   const int b = V.b;
   const unsigned long long todo = __ballot(mine);
   const int n_todo = __popcll(todo);
@@ -1249,10 +1455,15 @@ __device__ __forceinline__ void continue_in_rows(cptr_t C, EnvWork<T>& w, PFStat
     }
     ANM_WAVE_SYNC();
     unsigned tb, tn;
-    newton_rows<T, JT>(V, rvalid, vm, cs, sn, bus_p, bus_q, it, tb, tn, tol, max_iter);
+    if constexpr (PAIRS) {
+      if (pairs) newton_row_pairs<T, JT>(V, rvalid, vm, cs, sn, bus_p, bus_q, it, tb, tn, tol, max_iter);
+      else newton_rows<T, JT>(V, rvalid, vm, cs, sn, bus_p, bus_q, it, tb, tn, tol, max_iter);
+    } else {
+      newton_rows<T, JT>(V, rvalid, vm, cs, sn, bus_p, bus_q, it, tb, tn, tol, max_iter);
+    }
 
-    // ---- results back to the owner lanes
-    if (isbus) {
+    // ---- results back to the owner lanes (V.rep: never set on one lane per bus)
+    if (isbus && !V.rep) {
       double* s = lds + row * S::SIZE;
       s[S::VM + b] = vm; s[S::CS + b] = cs; s[S::SN + b] = sn;
       if (b == 1) {
@@ -1283,17 +1494,20 @@ __device__ __forceinline__ void continue_in_rows(cptr_t C, EnvWork<T>& w, PFStat
 // trip; two passes that each hold a diverging solve double the chain.  rowc (anm_solver_opts.row_continuation):
 //    0  n <= 4 solves: rows.  More: groups up to iteration ANM_MID_CAP_DEFAULT (every converging solve seen needs <= 9),
 //       then the survivors on rows if at most 4 are left, else on groups to the cap;
-//    1  always rows;   -1  never.
-// A topology without a row plan (T_ROW = 0) keeps groups.
+//    1  always rows;   -1  never;
+//    2  the policy of 0 with the rows on ONE lane per bus (newton_rows) even where the topology has a pair plan.
+// A row pass runs on two lanes per bus (newton_row_pairs: a shorter trip) where the topology has a pair plan (T_ROW2), else
+// on one.  A topology without a row plan (T_ROW = 0) keeps groups.
 template <class T, class JT, bool ROWS = true>
 __device__ __forceinline__ void continue_collective(cptr_t C, EnvWork<T>& w, PFState<T>& st, bool mine, double tol, int max_iter,
                                                     int rowc, double* lds) {
   if constexpr (T::T_ROW == 0 || !ROWS) {
     continue_in_groups<T, JT>(C, w, st, mine, tol, max_iter, lds);
   } else {
+    const bool policy = rowc == 0 || rowc == 2;
     int n = __popcll(__ballot(mine));
-    bool groups = rowc < 0 || (rowc == 0 && n > 4);
-    int cap = (rowc == 0 && ANM_MID_CAP_DEFAULT < max_iter) ? ANM_MID_CAP_DEFAULT : max_iter;
+    bool groups = rowc < 0 || (policy && n > 4);
+    int cap = (policy && ANM_MID_CAP_DEFAULT < max_iter) ? ANM_MID_CAP_DEFAULT : max_iter;
     while (groups) {
       continue_in_groups<T, JT>(C, w, st, mine, tol, cap, lds, cap < max_iter);
       mine = mine && st.active;   // (at the cap: nobody)
@@ -1301,7 +1515,7 @@ __device__ __forceinline__ void continue_collective(cptr_t C, EnvWork<T>& w, PFS
       groups = n > 4;
       cap = max_iter;
     }
-    if (n > 0) continue_in_rows<T, JT>(C, w, st, mine, tol, max_iter, lds);
+    if (n > 0) continue_in_rows<T, JT, T::T_ROW2 != 0>(C, w, st, mine, tol, max_iter, lds, rowc == 2);
   }
 }
 

@@ -177,7 +177,8 @@ class BatchedSimulator:
         # handoff_after: Newton iterations a solve spends in its own lane before a still-running (diverging)
         # one continues on a lane group, see anm_solver_opts in include/anm_mi355x.h; None = never
         # row_continuation: where they continue, anm_solver_opts.row_continuation -- 0: the library's policy, 1: always one
-        # solve per 16-lane row, -1: always one per lane group (same bits either way)
+        # solve per 16-lane row, -1: always one per lane group, 2: the policy with the rows on one lane per bus even where the
+        # topology has a pair layout (same bits every way)
         ho = _lib.HANDOFF_AUTO if handoff_after == "auto" else (_lib.HANDOFF_NEVER if handoff_after is None
                                                                 else int(handoff_after))  # fmt: skip
         self.opts = _lib.SolverOpts(float(tol), int(max_iter), _lib.SOLVE_F32 if precision == "f32" else _lib.SOLVE_F64,

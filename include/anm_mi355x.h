@@ -333,7 +333,9 @@ typedef struct anm_solver_opts {
    * pass, with every hand-over of the Newton trip a single 64-bit row_newbcast instruction, or one solve per lane group
    * (eight a pass for ANM6) at a longer trip.  Both give the same bits.  0 (what a zero-initialised struct asks for): the
    * library's policy -- rows when at most 4 solves hand over, else lane groups up to iteration 12 and then rows for
-   * the survivors if at most 4 are left; 1: always rows; -1: never. */
+   * the survivors if at most 4 are left; 1: always rows; -1: never.  A row pass runs on two lanes per bus, each forming
+   * one row of the child blocks, where the topology has a pair layout (codegen.row_pair_plan; the 6-bus feeder has one);
+   * 2: the policy of 0 with the row passes on one lane per bus even there (the same bits again; for comparisons). */
   int32_t row_continuation;
 } anm_solver_opts;
 #define ANM_HANDOFF_NEVER (-1)
