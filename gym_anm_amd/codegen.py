@@ -546,7 +546,7 @@ def row_plan(n_bus, tt):
 
 
 def row_pair_plan(n_bus, tt):
-    """The row plan with TWO lanes per bus (csrc/anm_group.hpp: newton_row_pairs).  Replica 0 of a bus keeps its lane of
+    """The row plan with TWO lanes per bus (csrc/anm_group.hpp: newton_rows<.., PAIRS = true>).  Replica 0 of a bus keeps its lane of
     row_plan; replica 1 takes an unused lane of the same bank: the next lane for a bus with children (rule (a) leaves its
     bank-mates unused), the lane `number of leaves` further on for a leaf, so a leaf bank holds its leaves, then their
     replicas.  Both replicas carry the same values of everything except the rows of Lk = Jpb Di, Sc = Lk Jbp and Lr = Lk r:

@@ -252,170 +252,136 @@ constexpr bool child_moves_land_on_parents_or_zero() {
 //     row_fold, row_fma) have no arithmetic left to lead with and open with `s_nop 1`;
 //   * a source lane switched off by EXEC is not read: every lane of the wavefront executes them (asm volatile: not sunk
 //     into a divergent region).
-// One statement serves up to four (source lane, bank mask) pairs of one hand-over point -- they read the same registers --
-// so a point has one lead, not one per pair.  (N1 / N2 / N3 < 0: no such pair.)
+// One statement serves up to four hand-overs of one point -- they read the same registers -- so a point has one lead, not
+// one per hand-over.  A hand-over is a (source lane N, second source lane M, bank mask B) triple: M is named by the fold
+// on two lanes per bus alone (ANM_ROW2_FOLD6), every other body reads lane N only, so a statement's template arguments are
+// the (N, B) pairs followed by the M's, which default to none.  (N1 / N2 / N3 < 0: no such hand-over.)
+// A statement is LEAD(F) followed by BODY(F, n, m, b) per hand-over, F the "f64" / "f32" of the element type (ANM_ROW_ASM_T
+// chooses it; the voltage and W statements are f64 only).
 // ---------------------------------------------------------------------------------------------
 #define ANM_ROW_CTL(n, b) " row_newbcast:%[" n "] row_mask:0xf bank_mask:%[" b "]\n"
-#define ANM_ROW_TPL template <int N0, int B0, int N1 = -1, int B1 = 0, int N2 = -1, int B2 = 0, int N3 = -1, int B3 = 0>
+#define ANM_ROW_INTS                                                                                                   \
+  int N0, int B0, int N1 = -1, int B1 = 0, int N2 = -1, int B2 = 0, int N3 = -1, int B3 = 0, int M0 = -1, int M1 = -1,   \
+      int M2 = -1, int M3 = -1
 #define ANM_ROW_IMM                                                                                                    \
-  [n0] "n"(N0), [b0] "n"(B0), [n1] "n"(N1 < 0 ? 0 : N1), [b1] "n"(B1), [n2] "n"(N2 < 0 ? 0 : N2), [b2] "n"(B2),          \
-  [n3] "n"(N3 < 0 ? 0 : N3), [b3] "n"(B3)
+  [n0] "n"(N0), [k0] "n"(M0 < 0 ? 0 : M0), [b0] "n"(B0), [n1] "n"(N1 < 0 ? 0 : N1), [k1] "n"(M1 < 0 ? 0 : M1),            \
+  [b1] "n"(B1), [n2] "n"(N2 < 0 ? 0 : N2), [k2] "n"(M2 < 0 ? 0 : M2), [b2] "n"(B2), [n3] "n"(N3 < 0 ? 0 : N3),           \
+  [k3] "n"(M3 < 0 ? 0 : M3), [b3] "n"(B3)
 #define ANM_ROW_UNPAR(...) __VA_ARGS__
-#define ANM_ROW_ASM_LEAD(LEAD, BODY, OUTS, INS)                                                                               \
-  do {                                                                                                                        \
-    if constexpr (N1 < 0) asm volatile(LEAD BODY("n0", "b0") : ANM_ROW_UNPAR OUTS : ANM_ROW_UNPAR INS, ANM_ROW_IMM);           \
-    else if constexpr (N2 < 0)                                                                                                \
-      asm volatile(LEAD BODY("n0", "b0") BODY("n1", "b1") : ANM_ROW_UNPAR OUTS : ANM_ROW_UNPAR INS, ANM_ROW_IMM);              \
-    else if constexpr (N3 < 0)                                                                                                \
-      asm volatile(LEAD BODY("n0", "b0") BODY("n1", "b1") BODY("n2", "b2") : ANM_ROW_UNPAR OUTS : ANM_ROW_UNPAR INS,           \
-                   ANM_ROW_IMM);                                                                                              \
-    else                                                                                                                      \
-      asm volatile(LEAD BODY("n0", "b0") BODY("n1", "b1") BODY("n2", "b2") BODY("n3", "b3") : ANM_ROW_UNPAR OUTS               \
-                   : ANM_ROW_UNPAR INS, ANM_ROW_IMM);                                                                         \
+#define ANM_ROW_ASM(F, LEAD, BODY, OUTS, INS)                                                                           \
+  do {                                                                                                                 \
+    if constexpr (N1 < 0) asm volatile(LEAD(F) BODY(F, "n0", "k0", "b0") : ANM_ROW_UNPAR OUTS : ANM_ROW_UNPAR INS, ANM_ROW_IMM); \
+    else if constexpr (N2 < 0)                                                                                         \
+      asm volatile(LEAD(F) BODY(F, "n0", "k0", "b0") BODY(F, "n1", "k1", "b1") : ANM_ROW_UNPAR OUTS                      \
+                   : ANM_ROW_UNPAR INS, ANM_ROW_IMM);                                                                  \
+    else if constexpr (N3 < 0)                                                                                         \
+      asm volatile(LEAD(F) BODY(F, "n0", "k0", "b0") BODY(F, "n1", "k1", "b1") BODY(F, "n2", "k2", "b2")                 \
+                   : ANM_ROW_UNPAR OUTS : ANM_ROW_UNPAR INS, ANM_ROW_IMM);                                             \
+    else                                                                                                               \
+      asm volatile(LEAD(F) BODY(F, "n0", "k0", "b0") BODY(F, "n1", "k1", "b1") BODY(F, "n2", "k2", "b2")                 \
+                   BODY(F, "n3", "k3", "b3") : ANM_ROW_UNPAR OUTS : ANM_ROW_UNPAR INS, ANM_ROW_IMM);                    \
   } while (0)
-#define ANM_ROW_ASM(BODY, OUTS, INS) ANM_ROW_ASM_LEAD("s_nop 1\n", BODY, OUTS, INS)
-#define ANM_ROW_MOV2(n, b) "v_mov_b64_dpp %[d0], %[s0]" ANM_ROW_CTL(n, b) "v_mov_b64_dpp %[d1], %[s1]" ANM_ROW_CTL(n, b)
-#define ANM_ROW_WSUM(n, b) "v_fmac_f64_dpp %[d0], %[s0], %[one]" ANM_ROW_CTL(n, b) "v_fmac_f64_dpp %[d1], -%[s1], %[one]" ANM_ROW_CTL(n, b)
-#define ANM_ROW_FOLD6(F, n, b)                                                                                       \
+#define ANM_ROW_ASM_T(R, LEAD, BODY, OUTS, INS)                                                                         \
+  do {                                                                                                                 \
+    if constexpr (std::is_same_v<R, double>) ANM_ROW_ASM("f64", LEAD, BODY, OUTS, INS);                                 \
+    else ANM_ROW_ASM("f32", LEAD, BODY, OUTS, INS);                                                                     \
+  } while (0)
+#define ANM_ROW_MOV2(F, n, m, b) "v_mov_b64_dpp %[d0], %[s0]" ANM_ROW_CTL(n, b) "v_mov_b64_dpp %[d1], %[s1]" ANM_ROW_CTL(n, b)
+#define ANM_ROW_WSUM(F, n, m, b) "v_fmac_f64_dpp %[d0], %[s0], %[one]" ANM_ROW_CTL(n, b) "v_fmac_f64_dpp %[d1], -%[s1], %[one]" ANM_ROW_CTL(n, b)
+#define ANM_ROW_FOLD6(F, n, m, b)                                                                                    \
   "v_fmac_" F "_dpp %[a], -%[sa], %[one]" ANM_ROW_CTL(n, b) "v_fmac_" F "_dpp %[b], -%[sb], %[one]" ANM_ROW_CTL(n, b)  \
   "v_fmac_" F "_dpp %[c], -%[sc], %[one]" ANM_ROW_CTL(n, b) "v_fmac_" F "_dpp %[d], -%[sd], %[one]" ANM_ROW_CTL(n, b)  \
   "v_fmac_" F "_dpp %[r0], -%[l0], %[one]" ANM_ROW_CTL(n, b) "v_fmac_" F "_dpp %[r1], -%[l1], %[one]" ANM_ROW_CTL(n, b)
-#define ANM_ROW_FOLD6_F64(n, b) ANM_ROW_FOLD6("f64", n, b)
-#define ANM_ROW_FOLD6_F32(n, b) ANM_ROW_FOLD6("f32", n, b)
-#define ANM_ROW_FMA4(F, n, b)                                                                                        \
+#define ANM_ROW_FMA4(F, n, m, b)                                                                                     \
   "v_fmac_" F "_dpp %[a0], -%[p0], %[ja]" ANM_ROW_CTL(n, b) "v_fmac_" F "_dpp %[a1], %[p0], %[jb]" ANM_ROW_CTL(n, b)   \
   "v_fmac_" F "_dpp %[a0], -%[p1], %[jb]" ANM_ROW_CTL(n, b) "v_fmac_" F "_dpp %[a1], -%[p1], %[ja]" ANM_ROW_CTL(n, b)
-#define ANM_ROW_FMA4_F64(n, b) ANM_ROW_FMA4("f64", n, b)
-#define ANM_ROW_FMA4_F32(n, b) ANM_ROW_FMA4("f32", n, b)
+// The fold on TWO lanes per bus (codegen.row_pair_plan; newton_rows<.., PAIRS>): lane N holds row 0 of the child's Schur
+// complement and reduced right-hand side -- (s0, s1, l) = (Sc.a, Sc.b, Lr0) -- and lane M row 1, (Sc.c, Sc.d, Lr1), in the
+// SAME three registers.  Six instructions per hand-over like ANM_ROW_FOLD6, the same six subtractions.
+#define ANM_ROW2_FOLD6(F, n, m, b)                                                                                   \
+  "v_fmac_" F "_dpp %[a], -%[s0], %[one]" ANM_ROW_CTL(n, b) "v_fmac_" F "_dpp %[c], -%[s0], %[one]" ANM_ROW_CTL(m, b)  \
+  "v_fmac_" F "_dpp %[b], -%[s1], %[one]" ANM_ROW_CTL(n, b) "v_fmac_" F "_dpp %[d], -%[s1], %[one]" ANM_ROW_CTL(m, b)  \
+  "v_fmac_" F "_dpp %[r0], -%[l], %[one]" ANM_ROW_CTL(n, b) "v_fmac_" F "_dpp %[r1], -%[l], %[one]" ANM_ROW_CTL(m, b)
+// The leads (the first rule above; the distances are counted in instructions of the statement, lead included):
+//   ANM_ROW_LEAD_NOP   a statement behind the first of its point
+//   ANM_ROW_LEAD_MOV   vr = vm cs, vi = vm sn, m2 = vm^2, then the moves: vr is read at distance 2, vi at distance 2
+//   ANM_ROW_LEAD_WSUM  the two additions that start the sums, then the children's products (no DPP read of a lead result)
+//   ANM_ROW_LEAD_FOLD  l0 += ka r0, l1 += kc r0 (the fmacs that finish Lr = Lk r), then the six folds: l0 / l1 at distance 5
+//   ANM_ROW2_LEAD_FOLD s1 += ka jb, l += ka r0 (the fmacs that finish my row of Sc = Lk Jbp and my entry of Lr = Lk r; s1 comes
+//                      in holding kb Jbp.d, l holding kb r1), then the folds, those of s0 first: s1 at distance 4, l at distance 5
+//   ANM_ROW_LEAD_STEP  p = Di r as mul, fmac (p0), mul, fmac (p1), then the four fused steps, which read p0, p0, p1, p1: each at
+//                      distance 2.  (r0 / r1 are read by the lead and accumulated into by the steps.)
+#define ANM_ROW_LEAD_NOP(F) "s_nop 1\n"
+#define ANM_ROW_LEAD_MOV(F) "v_mul_f64 %[s0], %[vm], %[cs]\nv_mul_f64 %[s1], %[vm], %[sn]\nv_mul_f64 %[m2], %[vm], %[vm]\n"
+#define ANM_ROW_LEAD_WSUM(F) "v_add_f64 %[d0], %[x0], %[y0]\nv_add_f64 %[d1], %[x1], %[y1]\n"
+#define ANM_ROW_LEAD_FOLD(F) "v_fmac_" F " %[l0], %[ka], %[r0]\nv_fmac_" F " %[l1], %[kc], %[r0]\n"
+#define ANM_ROW2_LEAD_FOLD(F) "v_fmac_" F " %[s1], %[ka], %[jb]\nv_fmac_" F " %[l], %[ka], %[r0]\n"
+#define ANM_ROW_LEAD_STEP(F)                                                                                     \
+  "v_mul_" F " %[p0], %[a1], %[ib]\nv_fmac_" F " %[p0], %[ia], %[a0]\nv_mul_" F " %[p1], %[a1], %[id]\nv_fmac_" F  \
+  " %[p1], %[ic], %[a0]\n"
 
 // (d0, d1) = (s0, s1) of lane N: the parent's voltage
-ANM_ROW_TPL __device__ __forceinline__ void row_mov(double& d0, double& d1, double s0, double s1) {
-  ANM_ROW_ASM(ANM_ROW_MOV2, ([d0] "+v"(d0), [d1] "+v"(d1)), ([s0] "v"(s0), [s1] "v"(s1)));
+template <ANM_ROW_INTS>
+__device__ __forceinline__ void row_mov(double& d0, double& d1, double s0, double s1) {
+  ANM_ROW_ASM("f64", ANM_ROW_LEAD_NOP, ANM_ROW_MOV2, ([d0] "+v"(d0), [d1] "+v"(d1)), ([s0] "v"(s0), [s1] "v"(s1)));
+}
+// (vr, vi, m2) = (vm cs, vm sn, vm^2), then row_mov of (vr, vi)
+template <ANM_ROW_INTS>
+__device__ __forceinline__ void row_mov_lead(double& d0, double& d1, double& vr, double& vi, double& m2, double vm, double cs, double sn) {
+  ANM_ROW_ASM("f64", ANM_ROW_LEAD_MOV, ANM_ROW_MOV2, ([d0] "+v"(d0), [d1] "+v"(d1), [s0] "=&v"(vr), [s1] "=&v"(vi), [m2] "=&v"(m2)),
+              ([vm] "v"(vm), [cs] "v"(cs), [sn] "v"(sn)));
 }
 // d0 += s0 of lane N, d1 -= s1 of lane N: a child's W product into its parent's sum (`one` holds 1.0)
-ANM_ROW_TPL __device__ __forceinline__ void row_wsum(double& d0, double& d1, double s0, double s1, double one) {
-  ANM_ROW_ASM(ANM_ROW_WSUM, ([d0] "+v"(d0), [d1] "+v"(d1)), ([s0] "v"(s0), [s1] "v"(s1), [one] "v"(one)));
+template <ANM_ROW_INTS>
+__device__ __forceinline__ void row_wsum(double& d0, double& d1, double s0, double s1, double one) {
+  ANM_ROW_ASM("f64", ANM_ROW_LEAD_NOP, ANM_ROW_WSUM, ([d0] "+v"(d0), [d1] "+v"(d1)), ([s0] "v"(s0), [s1] "v"(s1), [one] "v"(one)));
+}
+// (d0, d1) = (x0 + y0, x1 + y1), then row_wsum
+template <ANM_ROW_INTS>
+__device__ __forceinline__ void row_wsum_lead(double& d0, double& d1, double x0, double y0, double x1, double y1, double s0, double s1,
+                                              double one) {
+  ANM_ROW_ASM("f64", ANM_ROW_LEAD_WSUM, ANM_ROW_WSUM, ([d0] "=&v"(d0), [d1] "=&v"(d1)),
+              ([x0] "v"(x0), [y0] "v"(y0), [x1] "v"(x1), [y1] "v"(y1), [s0] "v"(s0), [s1] "v"(s1), [one] "v"(one)));
 }
 // D -= Sc of lane N, (r0, r1) -= (l0, l1) of lane N: a child's Schur complement and reduced right-hand side into its parent
-ANM_ROW_TPL __device__ __forceinline__ void row_fold(Blk<double>& D, double& r0, double& r1, const Blk<double>& Sc, double l0, double l1, double one) {
-  ANM_ROW_ASM(ANM_ROW_FOLD6_F64, ([a] "+v"(D.a), [b] "+v"(D.b), [c] "+v"(D.c), [d] "+v"(D.d), [r0] "+v"(r0), [r1] "+v"(r1)),
-              ([sa] "v"(Sc.a), [sb] "v"(Sc.b), [sc] "v"(Sc.c), [sd] "v"(Sc.d), [l0] "v"(l0), [l1] "v"(l1), [one] "v"(one)));
+template <ANM_ROW_INTS, class R>
+__device__ __forceinline__ void row_fold(Blk<R>& D, R& r0, R& r1, const Blk<R>& Sc, R l0, R l1, R one) {
+  ANM_ROW_ASM_T(R, ANM_ROW_LEAD_NOP, ANM_ROW_FOLD6, ([a] "+v"(D.a), [b] "+v"(D.b), [c] "+v"(D.c), [d] "+v"(D.d), [r0] "+v"(r0), [r1] "+v"(r1)),
+                ([sa] "v"(Sc.a), [sb] "v"(Sc.b), [sc] "v"(Sc.c), [sd] "v"(Sc.d), [l0] "v"(l0), [l1] "v"(l1), [one] "v"(one)));
 }
-ANM_ROW_TPL __device__ __forceinline__ void row_fold(Blk<float>& D, float& r0, float& r1, const Blk<float>& Sc, float l0, float l1, float one) {
-  ANM_ROW_ASM(ANM_ROW_FOLD6_F32, ([a] "+v"(D.a), [b] "+v"(D.b), [c] "+v"(D.c), [d] "+v"(D.d), [r0] "+v"(r0), [r1] "+v"(r1)),
-              ([sa] "v"(Sc.a), [sb] "v"(Sc.b), [sc] "v"(Sc.c), [sd] "v"(Sc.d), [l0] "v"(l0), [l1] "v"(l1), [one] "v"(one)));
+// (l0, l1) += (ka, kc) r0 -- they come in holding (kb, kd) r1 -- then row_fold
+template <ANM_ROW_INTS, class R>
+__device__ __forceinline__ void row_fold_lead(Blk<R>& D, R& r0, R& r1, const Blk<R>& Sc, R& l0, R& l1, R ka, R kc, R one) {
+  ANM_ROW_ASM_T(R, ANM_ROW_LEAD_FOLD, ANM_ROW_FOLD6,
+                ([a] "+v"(D.a), [b] "+v"(D.b), [c] "+v"(D.c), [d] "+v"(D.d), [r0] "+v"(r0), [r1] "+v"(r1), [l0] "+v"(l0), [l1] "+v"(l1)),
+                ([sa] "v"(Sc.a), [sb] "v"(Sc.b), [sc] "v"(Sc.c), [sd] "v"(Sc.d), [ka] "v"(ka), [kc] "v"(kc), [one] "v"(one)));
+}
+// row_fold on two lanes per bus: D's row 0 and r0 -= (s0, s1, l) of lane N, row 1 and r1 -= those of lane M
+template <ANM_ROW_INTS, class R>
+__device__ __forceinline__ void row_pair_fold(Blk<R>& D, R& r0, R& r1, R s0, R s1, R l, R one) {
+  ANM_ROW_ASM_T(R, ANM_ROW_LEAD_NOP, ANM_ROW2_FOLD6, ([a] "+v"(D.a), [b] "+v"(D.b), [c] "+v"(D.c), [d] "+v"(D.d), [r0] "+v"(r0), [r1] "+v"(r1)),
+                ([s0] "v"(s0), [s1] "v"(s1), [l] "v"(l), [one] "v"(one)));
+}
+// s1 += ka jb, l += ka r0, then row_pair_fold
+template <ANM_ROW_INTS, class R>
+__device__ __forceinline__ void row_pair_fold_lead(Blk<R>& D, R& r0, R& r1, R s0, R& s1, R& l, R ka, R jb, R one) {
+  ANM_ROW_ASM_T(R, ANM_ROW2_LEAD_FOLD, ANM_ROW2_FOLD6,
+                ([a] "+v"(D.a), [b] "+v"(D.b), [c] "+v"(D.c), [d] "+v"(D.d), [r0] "+v"(r0), [r1] "+v"(r1), [s1] "+v"(s1), [l] "+v"(l)),
+                ([s0] "v"(s0), [ka] "v"(ka), [jb] "v"(jb), [one] "v"(one)));
 }
 // a0 = fma(-J.b, p1 of lane N, fma(-J.a, p0 of lane N, a0)), a1 likewise with (J.c, J.d): the parent's Newton step into
 // the right-hand side of the back substitution.  The block is a coupling block of the polar Jacobian, {ja, jb, -jb, ja}
 // (Jbp of newton_rows): the statement takes ja and jb alone and forms the product by J.c = -jb as +(p0 * jb) -- the sign
 // of a product is the exclusive or of its factors' signs, the magnitude is the same, so the bits are those of -p0 * -jb.
-ANM_ROW_TPL __device__ __forceinline__ void row_fma(double& a0, double& a1, double p0, double p1, double ja, double jb) {
-  ANM_ROW_ASM(ANM_ROW_FMA4_F64, ([a0] "+v"(a0), [a1] "+v"(a1)), ([p0] "v"(p0), [p1] "v"(p1), [ja] "v"(ja), [jb] "v"(jb)));
-}
-ANM_ROW_TPL __device__ __forceinline__ void row_fma(float& a0, float& a1, float p0, float p1, float ja, float jb) {
-  ANM_ROW_ASM(ANM_ROW_FMA4_F32, ([a0] "+v"(a0), [a1] "+v"(a1)), ([p0] "v"(p0), [p1] "v"(p1), [ja] "v"(ja), [jb] "v"(jb)));
-}
-// The first statement of each hand-over point, led by the arithmetic in front of it (the first rule above; the distances
-// are counted in instructions of the statement, lead included):
-//   row_mov_lead    vr = vm cs, vi = vm sn, m2 = vm^2, then the moves: vr is read at distance 2, vi at distance 2
-//   row_wsum_lead   the two additions that start the sums, then the children's products (no DPP read of a lead result)
-//   row_fold_lead   l0 += ka r0, l1 += kc r0 (the fmacs that finish Lr = Lk r), then the six folds: l0 / l1 at distance 5
-//   row_step_lead   p = Di r as mul, fmac (p0), mul, fmac (p1), then the four fused steps, which read p0, p0, p1, p1: each at
-//                   distance 2.  (r0 / r1 are read by the lead and accumulated into by the steps.)
-#define ANM_ROW_LEAD_MOV "v_mul_f64 %[s0], %[vm], %[cs]\nv_mul_f64 %[s1], %[vm], %[sn]\nv_mul_f64 %[m2], %[vm], %[vm]\n"
-#define ANM_ROW_LEAD_WSUM "v_add_f64 %[d0], %[x0], %[y0]\nv_add_f64 %[d1], %[x1], %[y1]\n"
-#define ANM_ROW_LEAD_FOLD(F) "v_fmac_" F " %[l0], %[ka], %[r0]\nv_fmac_" F " %[l1], %[kc], %[r0]\n"
-#define ANM_ROW_LEAD_STEP(F)                                                                                     \
-  "v_mul_" F " %[p0], %[a1], %[ib]\nv_fmac_" F " %[p0], %[ia], %[a0]\nv_mul_" F " %[p1], %[a1], %[id]\nv_fmac_" F  \
-  " %[p1], %[ic], %[a0]\n"
-ANM_ROW_TPL __device__ __forceinline__ void row_mov_lead(double& d0, double& d1, double& vr, double& vi, double& m2, double vm,
-                                                         double cs, double sn) {
-  ANM_ROW_ASM_LEAD(ANM_ROW_LEAD_MOV, ANM_ROW_MOV2, ([d0] "+v"(d0), [d1] "+v"(d1), [s0] "=&v"(vr), [s1] "=&v"(vi), [m2] "=&v"(m2)),
-                   ([vm] "v"(vm), [cs] "v"(cs), [sn] "v"(sn)));
-}
-// (d0, d1) = (x0 + y0, x1 + y1), then row_wsum
-ANM_ROW_TPL __device__ __forceinline__ void row_wsum_lead(double& d0, double& d1, double x0, double y0, double x1, double y1,
-                                                          double s0, double s1, double one) {
-  ANM_ROW_ASM_LEAD(ANM_ROW_LEAD_WSUM, ANM_ROW_WSUM, ([d0] "=&v"(d0), [d1] "=&v"(d1)),
-                   ([x0] "v"(x0), [y0] "v"(y0), [x1] "v"(x1), [y1] "v"(y1), [s0] "v"(s0), [s1] "v"(s1), [one] "v"(one)));
-}
-// (l0, l1) += (ka, kc) r0 -- they come in holding (kb, kd) r1 -- then row_fold
-ANM_ROW_TPL __device__ __forceinline__ void row_fold_lead(Blk<double>& D, double& r0, double& r1, const Blk<double>& Sc, double& l0,
-                                                          double& l1, double ka, double kc, double one) {
-  ANM_ROW_ASM_LEAD(ANM_ROW_LEAD_FOLD("f64"), ANM_ROW_FOLD6_F64,
-                   ([a] "+v"(D.a), [b] "+v"(D.b), [c] "+v"(D.c), [d] "+v"(D.d), [r0] "+v"(r0), [r1] "+v"(r1), [l0] "+v"(l0), [l1] "+v"(l1)),
-                   ([sa] "v"(Sc.a), [sb] "v"(Sc.b), [sc] "v"(Sc.c), [sd] "v"(Sc.d), [ka] "v"(ka), [kc] "v"(kc), [one] "v"(one)));
-}
-ANM_ROW_TPL __device__ __forceinline__ void row_fold_lead(Blk<float>& D, float& r0, float& r1, const Blk<float>& Sc, float& l0,
-                                                          float& l1, float ka, float kc, float one) {
-  ANM_ROW_ASM_LEAD(ANM_ROW_LEAD_FOLD("f32"), ANM_ROW_FOLD6_F32,
-                   ([a] "+v"(D.a), [b] "+v"(D.b), [c] "+v"(D.c), [d] "+v"(D.d), [r0] "+v"(r0), [r1] "+v"(r1), [l0] "+v"(l0), [l1] "+v"(l1)),
-                   ([sa] "v"(Sc.a), [sb] "v"(Sc.b), [sc] "v"(Sc.c), [sd] "v"(Sc.d), [ka] "v"(ka), [kc] "v"(kc), [one] "v"(one)));
+template <ANM_ROW_INTS, class R>
+__device__ __forceinline__ void row_fma(R& a0, R& a1, R p0, R p1, R ja, R jb) {
+  ANM_ROW_ASM_T(R, ANM_ROW_LEAD_NOP, ANM_ROW_FMA4, ([a0] "+v"(a0), [a1] "+v"(a1)), ([p0] "v"(p0), [p1] "v"(p1), [ja] "v"(ja), [jb] "v"(jb)));
 }
 // (p0, p1) = Di (r0, r1) -- a lane's own Newton step -- then row_fma with it: the step of a parent into its children
-ANM_ROW_TPL __device__ __forceinline__ void row_step_lead(double& r0, double& r1, double& p0, double& p1, const Blk<double>& Di,
-                                                          double ja, double jb) {
-  ANM_ROW_ASM_LEAD(ANM_ROW_LEAD_STEP("f64"), ANM_ROW_FMA4_F64, ([a0] "+v"(r0), [a1] "+v"(r1), [p0] "=&v"(p0), [p1] "=&v"(p1)),
-                   ([ia] "v"(Di.a), [ib] "v"(Di.b), [ic] "v"(Di.c), [id] "v"(Di.d), [ja] "v"(ja), [jb] "v"(jb)));
-}
-ANM_ROW_TPL __device__ __forceinline__ void row_step_lead(float& r0, float& r1, float& p0, float& p1, const Blk<float>& Di, float ja,
-                                                          float jb) {
-  ANM_ROW_ASM_LEAD(ANM_ROW_LEAD_STEP("f32"), ANM_ROW_FMA4_F32, ([a0] "+v"(r0), [a1] "+v"(r1), [p0] "=&v"(p0), [p1] "=&v"(p1)),
-                   ([ia] "v"(Di.a), [ib] "v"(Di.b), [ic] "v"(Di.c), [id] "v"(Di.d), [ja] "v"(ja), [jb] "v"(jb)));
-}
-// The fold on TWO lanes per bus (codegen.row_pair_plan; newton_row_pairs below): lane N holds row 0 of the child's Schur
-// complement and reduced right-hand side -- (s0, s1, l) = (Sc.a, Sc.b, Lr0) -- and lane M row 1, (Sc.c, Sc.d, Lr1), in the
-// SAME three registers.  Six instructions per (N, M, bank mask) triple like row_fold, the same six subtractions; up to four
-// triples to a statement.
-//   row_fold2_lead  s1 += ka jb, l += ka r0 (the fmacs that finish my row of Sc = Lk Jbp and my entry of Lr = Lk r; s1 comes
-//                   in holding kb Jbp.d, l holding kb r1), then the folds, those of s0 first: s1 at distance 4, l at distance 5
-#define ANM_ROW2_TPL                                                                                                   \
-  template <int N0, int M0, int B0, int N1 = -1, int M1 = -1, int B1 = 0, int N2 = -1, int M2 = -1, int B2 = 0, int N3 = -1, \
-            int M3 = -1, int B3 = 0>
-#define ANM_ROW2_IMM                                                                                                   \
-  [n0] "n"(N0), [m0] "n"(M0), [b0] "n"(B0), [n1] "n"(N1 < 0 ? 0 : N1), [m1] "n"(M1 < 0 ? 0 : M1), [b1] "n"(B1),          \
-  [n2] "n"(N2 < 0 ? 0 : N2), [m2] "n"(M2 < 0 ? 0 : M2), [b2] "n"(B2), [n3] "n"(N3 < 0 ? 0 : N3), [m3] "n"(M3 < 0 ? 0 : M3), \
-  [b3] "n"(B3)
-#define ANM_ROW2_ASM_LEAD(LEAD, BODY, OUTS, INS)                                                                        \
-  do {                                                                                                                 \
-    if constexpr (N1 < 0) asm volatile(LEAD BODY("n0", "m0", "b0") : ANM_ROW_UNPAR OUTS : ANM_ROW_UNPAR INS, ANM_ROW2_IMM); \
-    else if constexpr (N2 < 0)                                                                                         \
-      asm volatile(LEAD BODY("n0", "m0", "b0") BODY("n1", "m1", "b1") : ANM_ROW_UNPAR OUTS : ANM_ROW_UNPAR INS, ANM_ROW2_IMM); \
-    else if constexpr (N3 < 0)                                                                                         \
-      asm volatile(LEAD BODY("n0", "m0", "b0") BODY("n1", "m1", "b1") BODY("n2", "m2", "b2") : ANM_ROW_UNPAR OUTS       \
-                   : ANM_ROW_UNPAR INS, ANM_ROW2_IMM);                                                                 \
-    else                                                                                                               \
-      asm volatile(LEAD BODY("n0", "m0", "b0") BODY("n1", "m1", "b1") BODY("n2", "m2", "b2") BODY("n3", "m3", "b3")     \
-                   : ANM_ROW_UNPAR OUTS : ANM_ROW_UNPAR INS, ANM_ROW2_IMM);                                            \
-  } while (0)
-#define ANM_ROW2_FOLD6(F, n, m, b)                                                                                   \
-  "v_fmac_" F "_dpp %[a], -%[s0], %[one]" ANM_ROW_CTL(n, b) "v_fmac_" F "_dpp %[c], -%[s0], %[one]" ANM_ROW_CTL(m, b)  \
-  "v_fmac_" F "_dpp %[b], -%[s1], %[one]" ANM_ROW_CTL(n, b) "v_fmac_" F "_dpp %[d], -%[s1], %[one]" ANM_ROW_CTL(m, b)  \
-  "v_fmac_" F "_dpp %[r0], -%[l], %[one]" ANM_ROW_CTL(n, b) "v_fmac_" F "_dpp %[r1], -%[l], %[one]" ANM_ROW_CTL(m, b)
-#define ANM_ROW2_FOLD6_F64(n, m, b) ANM_ROW2_FOLD6("f64", n, m, b)
-#define ANM_ROW2_FOLD6_F32(n, m, b) ANM_ROW2_FOLD6("f32", n, m, b)
-#define ANM_ROW2_LEAD_FOLD(F) "v_fmac_" F " %[s1], %[ka], %[jb]\nv_fmac_" F " %[l], %[ka], %[r0]\n"
-ANM_ROW2_TPL __device__ __forceinline__ void row_fold2(Blk<double>& D, double& r0, double& r1, double s0, double s1, double l, double one) {
-  ANM_ROW2_ASM_LEAD("s_nop 1\n", ANM_ROW2_FOLD6_F64,
-                    ([a] "+v"(D.a), [b] "+v"(D.b), [c] "+v"(D.c), [d] "+v"(D.d), [r0] "+v"(r0), [r1] "+v"(r1)),
-                    ([s0] "v"(s0), [s1] "v"(s1), [l] "v"(l), [one] "v"(one)));
-}
-ANM_ROW2_TPL __device__ __forceinline__ void row_fold2(Blk<float>& D, float& r0, float& r1, float s0, float s1, float l, float one) {
-  ANM_ROW2_ASM_LEAD("s_nop 1\n", ANM_ROW2_FOLD6_F32,
-                    ([a] "+v"(D.a), [b] "+v"(D.b), [c] "+v"(D.c), [d] "+v"(D.d), [r0] "+v"(r0), [r1] "+v"(r1)),
-                    ([s0] "v"(s0), [s1] "v"(s1), [l] "v"(l), [one] "v"(one)));
-}
-ANM_ROW2_TPL __device__ __forceinline__ void row_fold2_lead(Blk<double>& D, double& r0, double& r1, double s0, double& s1, double& l,
-                                                            double ka, double jb, double one) {
-  ANM_ROW2_ASM_LEAD(ANM_ROW2_LEAD_FOLD("f64"), ANM_ROW2_FOLD6_F64,
-                    ([a] "+v"(D.a), [b] "+v"(D.b), [c] "+v"(D.c), [d] "+v"(D.d), [r0] "+v"(r0), [r1] "+v"(r1), [s1] "+v"(s1), [l] "+v"(l)),
-                    ([s0] "v"(s0), [ka] "v"(ka), [jb] "v"(jb), [one] "v"(one)));
-}
-ANM_ROW2_TPL __device__ __forceinline__ void row_fold2_lead(Blk<float>& D, float& r0, float& r1, float s0, float& s1, float& l, float ka,
-                                                            float jb, float one) {
-  ANM_ROW2_ASM_LEAD(ANM_ROW2_LEAD_FOLD("f32"), ANM_ROW2_FOLD6_F32,
-                    ([a] "+v"(D.a), [b] "+v"(D.b), [c] "+v"(D.c), [d] "+v"(D.d), [r0] "+v"(r0), [r1] "+v"(r1), [s1] "+v"(s1), [l] "+v"(l)),
-                    ([s0] "v"(s0), [ka] "v"(ka), [jb] "v"(jb), [one] "v"(one)));
+template <ANM_ROW_INTS, class R>
+__device__ __forceinline__ void row_step_lead(R& r0, R& r1, R& p0, R& p1, const Blk<R>& Di, R ja, R jb) {
+  ANM_ROW_ASM_T(R, ANM_ROW_LEAD_STEP, ANM_ROW_FMA4, ([a0] "+v"(r0), [a1] "+v"(r1), [p0] "=&v"(p0), [p1] "=&v"(p1)),
+                ([ia] "v"(Di.a), [ib] "v"(Di.b), [ic] "v"(Di.c), [id] "v"(Di.d), [ja] "v"(ja), [jb] "v"(jb)));
 }
 // Two integer statements of the stop test that the compiler makes longer than the instruction set needs:
 //   row_count   it + 1 on the lanes of the wavefront mask m, it elsewhere: ONE add with carry-in (select and add: two)
@@ -436,44 +402,34 @@ __device__ __forceinline__ unsigned row_pick(unsigned long long m, unsigned glo,
       : [lo] "s"(unsigned(m)), [hi] "s"(unsigned(m >> 32)), [glo] "v"(glo), [ghi] "v"(ghi));
   return d;
 }
-// the tables of codegen.row_plan: PAR (parent -> children), CH (child -> parent, by level), WS (child -> parent, by parent)
-enum : int { ROW_PAR = 0, ROW_CH = 1, ROW_WS = 2 };
+// the tables of codegen.row_plan: PAR (parent -> children), CH (child -> parent, by level), WS (child -> parent, by parent);
+// CH_PAIR: CH on two lanes per bus (codegen.row_pair_plan) -- the source of row 0, the source of row 1, the banks of CH
+enum : int { ROW_PAR = 0, ROW_CH = 1, ROW_WS = 2, ROW_CH_PAIR = 3 };
 template <class T, int W>
 constexpr int row_src(int i, int hi) {
-  return i >= hi ? -1 : (W == ROW_PAR ? T::T_ROW_PAR_SRC[i] : (W == ROW_CH ? T::T_ROW_CH_SRC[i] : T::T_ROW_WS_SRC[i]));
+  return i >= hi ? -1 : (W == ROW_PAR ? T::T_ROW_PAR_SRC[i] : (W == ROW_CH ? T::T_ROW_CH_SRC[i] : (W == ROW_WS ? T::T_ROW_WS_SRC[i] : T::T_ROW2_CH_SRC0[i])));
+}
+template <class T, int W>
+constexpr int row_src1(int i, int hi) {
+  return (W != ROW_CH_PAIR || i >= hi) ? -1 : T::T_ROW2_CH_SRC1[i];
 }
 template <class T, int W>
 constexpr int row_bank(int i, int hi) {
-  return i >= hi ? 0 : (W == ROW_PAR ? T::T_ROW_PAR_BANK[i] : (W == ROW_CH ? T::T_ROW_CH_BANK[i] : T::T_ROW_WS_BANK[i]));
+  return i >= hi ? 0 : (W == ROW_PAR ? T::T_ROW_PAR_BANK[i] : (W == ROW_WS ? T::T_ROW_WS_BANK[i] : T::T_ROW_CH_BANK[i]));
 }
-// the pairs [LO, HI) of table W, four to a statement: f(FIRST, N0, B0, ... N3, B3) with integral constants (FIRST: the
-// point's first statement, the one that takes the lead)
-#define ANM_ROW_PARAMS auto N0, auto B0, auto N1, auto B1, auto N2, auto B2, auto N3, auto B3
-#define ANM_ROW_ARGS N0, B0, N1, B1, N2, B2, N3, B3
+// the hand-overs [LO, HI) of table W, four to a statement: f(FIRST, N0, B0, ... N3, B3, M0, ... M3) with integral constants
+// (FIRST: the point's first statement, the one that takes the lead)
+#define ANM_ROW_PARAMS auto N0, auto B0, auto N1, auto B1, auto N2, auto B2, auto N3, auto B3, auto M0, auto M1, auto M2, auto M3
+#define ANM_ROW_ARGS N0, B0, N1, B1, N2, B2, N3, B3, M0, M1, M2, M3
 template <class T, int W, int LO, int HI, class F>
 __device__ __forceinline__ void row_points(F&& f) {
   static_for<0, (HI - LO + 3) / 4>([&](auto Q) {
     constexpr int i = LO + 4 * int(Q);
-    f(std::bool_constant<int(Q) == 0>{},
-      std::integral_constant<int, row_src<T, W>(i, HI)>{}, std::integral_constant<int, row_bank<T, W>(i, HI)>{},
-      std::integral_constant<int, row_src<T, W>(i + 1, HI)>{}, std::integral_constant<int, row_bank<T, W>(i + 1, HI)>{},
-      std::integral_constant<int, row_src<T, W>(i + 2, HI)>{}, std::integral_constant<int, row_bank<T, W>(i + 2, HI)>{},
-      std::integral_constant<int, row_src<T, W>(i + 3, HI)>{}, std::integral_constant<int, row_bank<T, W>(i + 3, HI)>{});
-  });
-}
-// the folds [LO, HI) of table CH on two lanes per bus (codegen.row_pair_plan): (source of row 0, source of row 1, bank mask)
-#define ANM_ROW2_PARAMS auto N0, auto M0, auto B0, auto N1, auto M1, auto B1, auto N2, auto M2, auto B2, auto N3, auto M3, auto B3
-#define ANM_ROW2_ARGS N0, M0, B0, N1, M1, B1, N2, M2, B2, N3, M3, B3
-template <class T, int LO, int HI, class F>
-__device__ __forceinline__ void row_points2(F&& f) {
-  static_for<0, (HI - LO + 3) / 4>([&](auto Q) {
-    constexpr int i = LO + 4 * int(Q);
-#define ANM_ROW2_TRIPLE(k)                                                                                     \
-  std::integral_constant<int, (k) >= HI ? -1 : T::T_ROW2_CH_SRC0[(k) >= HI ? 0 : (k)]>{},                           \
-  std::integral_constant<int, (k) >= HI ? -1 : T::T_ROW2_CH_SRC1[(k) >= HI ? 0 : (k)]>{},                           \
-  std::integral_constant<int, row_bank<T, ROW_CH>((k), HI)>{}
-    f(std::bool_constant<int(Q) == 0>{}, ANM_ROW2_TRIPLE(i), ANM_ROW2_TRIPLE(i + 1), ANM_ROW2_TRIPLE(i + 2), ANM_ROW2_TRIPLE(i + 3));
-#undef ANM_ROW2_TRIPLE
+#define ANM_ROW_IC(FN, k) std::integral_constant<int, FN<T, W>((k), HI)>{}
+    f(std::bool_constant<int(Q) == 0>{}, ANM_ROW_IC(row_src, i), ANM_ROW_IC(row_bank, i), ANM_ROW_IC(row_src, i + 1),
+      ANM_ROW_IC(row_bank, i + 1), ANM_ROW_IC(row_src, i + 2), ANM_ROW_IC(row_bank, i + 2), ANM_ROW_IC(row_src, i + 3),
+      ANM_ROW_IC(row_bank, i + 3), ANM_ROW_IC(row_src1, i), ANM_ROW_IC(row_src1, i + 1), ANM_ROW_IC(row_src1, i + 2), ANM_ROW_IC(row_src1, i + 3));
+#undef ANM_ROW_IC
   });
 }
 
@@ -568,6 +524,39 @@ constexpr int hyb_slot_base(int h) {
   int n = 0;
   for (int k = 0; k < h && k <= T::T_MAXH; ++k) n += T::T_NLH[k];
   return n;
+}
+
+// The update of the lanes of updm by the Newton step (d0: angle, d1: relative magnitude): rotation of (cos, sin) by d0, path
+// chosen per wavefront exactly as update_angles does (the reduction of a small step returns the same bits as the short
+// path).  The loops where a trip's instruction COUNT is its duration: the polynomials are evaluated on every lane -- a lane
+// that does not update computes on whatever its d0 holds and drops the result -- so that the wave-uniform branch is the only
+// control flow in front of them, and the rotation stands once behind both paths.
+template <class JT>
+__device__ __forceinline__ void update_iterate(unsigned long long updm, JT d0, JT d1, double& vm, double& cs, double& sn) {
+  const bool upd = __builtin_amdgcn_inverse_ballot_w64(updm);
+  const double dth = double(d0);
+  const unsigned long long bigm = __builtin_amdgcn_fcmp(fabs(dth), 0.78, FCMP_UGT) & updm;  // NaN counts
+  double sd_, cd_;
+  if (bigm == 0ull) {
+    sincos_kernel<true>(dth, 0, sd_, cd_);
+  } else {
+    sincos_medium<true>(dth, sd_, cd_);
+    // (beyond the two-stage reduction: a handful of lanes per million solves -- the library routine then runs on every
+    // lane of the wavefront and the lanes it was called for take its result: no divergent region in this tail)
+    const bool ish = !(fabs(dth) < SINCOS_MEDIUM_MAX);
+    if ((__builtin_amdgcn_uicmp(ish ? 1u : 0u, 0u, ICMP_NE) & updm) != 0ull) {
+      const SinCos r = sincos_huge(dth);
+      sd_ = ish ? r.s : sd_;
+      cd_ = ish ? r.c : cd_;
+    }
+  }
+  if (upd) {
+    vm = fma(-double(d1), fabs(vm), vm);
+    // (three-address v_fma_f64 in place of the compiler's v_fmac into a temporary + v_mov_b64 back into the loop's register)
+    const double t1 = sn * sd_, t2 = cs * sd_;
+    cs = fma3<false>(cs, cd_, t1);
+    sn = fma3<true>(sn, cd_, t2);
+  }
 }
 
 // The Newton-Raphson loop of every lane group of the wavefront, from the iterate (vm, cs, sn) each bus lane
@@ -975,32 +964,9 @@ __device__ __forceinline__ void newton_groups(const LaneView<T>& V, bool gvalid,
       const double dth = double(d0);
       const unsigned long long bigm = __builtin_amdgcn_fcmp(fabs(dth), 0.78, FCMP_UGT) & updm;  // NaN counts
       if constexpr (VPOLY) {
-        // (VPOLY: the register hand-over variant = the continuation of the thread family's diverging solves, where a trip's
-        // instruction COUNT is its duration, and the LDS variant where the caller's register budget has room for the
-        // coefficients in vector registers (the radial kernel without per-group classes: 163 of 168): the short path evaluates the polynomials on every lane -- a lane that does not update
-        // computes on whatever its dth holds and drops the result -- so that the wave-uniform branch is the only control
-        // flow in front of them, and the rotation stands once behind both paths)
-        double sd_, cd_;
-        if (bigm == 0ull) {
-          sincos_kernel<true>(dth, 0, sd_, cd_);
-        } else {
-          sincos_medium<true>(dth, sd_, cd_);
-          // (beyond the two-stage reduction: a handful of lanes per million solves -- the library routine then runs on every
-          // lane of the wavefront and the lanes it was called for take its result: no divergent region in this tail)
-          const bool ish = !(fabs(dth) < SINCOS_MEDIUM_MAX);
-          if ((__builtin_amdgcn_uicmp(ish ? 1u : 0u, 0u, ICMP_NE) & updm) != 0ull) {
-            const SinCos r = sincos_huge(dth);
-            sd_ = ish ? r.s : sd_;
-            cd_ = ish ? r.c : cd_;
-          }
-        }
-        if (upd) {
-          vm = fma(-double(d1), fabs(vm), vm);
-          // (three-address v_fma_f64 in place of the compiler's v_fmac into a temporary + v_mov_b64 back into the loop's register)
-          const double t1 = sn * sd_, t2 = cs * sd_;
-          cs = fma3<false>(cs, cd_, t1);
-          sn = fma3<true>(sn, cd_, t2);
-        }
+        // (the register hand-over variant = the continuation of the thread family's diverging solves, and the LDS variant where the
+        // caller's register budget has room for the coefficients in vector registers: the radial kernel without per-group classes, 163 of 168)
+        update_iterate(updm, d0, d1, vm, cs, sn);
       } else
       if (bigm == 0ull) {
         if (upd) {
@@ -1034,6 +1000,51 @@ __device__ __forceinline__ void newton_groups(const LaneView<T>& V, bool gvalid,
   }
 }
 
+// The LDS hand-over of one solve between its owner lane (which holds the whole iterate) and the bus lanes that continue
+// it, through the solve's slot s.  Four phases; the callers put a wavefront barrier behind each:
+//   slot_send     the owner writes the iterate, the injections and the iteration count
+//   slot_load     the lane of bus b reads its bus (every lane of a slot that holds a solve reads the count besides)
+//   slot_store    the lane of bus b writes its iterate back, the lane of bus 1 also the count and the verdict of tb / tn
+//                 (NaN: failed; 0: converged; +inf: still above tol)
+//   slot_receive  the owner takes the final iterate, st.it and the verdict as st.diff
+template <class T>
+__device__ __forceinline__ void slot_send(double* s, const EnvWork<T>& w, const PFState<T>& st) {
+  typedef Slot<T> S;
+  static_for<1, T::NB>([&](auto I) {
+    constexpr int i = I;
+    s[S::VM + i] = w.vm[i]; s[S::CS + i] = st.cs[i]; s[S::SN + i] = st.sn[i];
+    s[S::P + i] = w.bus_p[i]; s[S::Q + i] = w.bus_q[i];
+  });
+  s[S::IT] = double(st.it);
+}
+template <class T>
+__device__ __forceinline__ void slot_load(const double* s, int b, double& vm, double& cs, double& sn, double& bus_p, double& bus_q) {
+  typedef Slot<T> S;
+  vm = s[S::VM + b]; cs = s[S::CS + b]; sn = s[S::SN + b]; bus_p = s[S::P + b]; bus_q = s[S::Q + b];
+}
+template <class T>
+__device__ __forceinline__ void slot_store(double* s, int b, const double& vm, const double& cs, const double& sn, const int& it,
+                                           const unsigned& tb, const unsigned& tn) {
+  typedef Slot<T> S;
+  s[S::VM + b] = vm; s[S::CS + b] = cs; s[S::SN + b] = sn;
+  if (b == 1) {
+    s[S::IT] = double(it);
+    s[S::FLAGS] = (tn != 0u) ? NAN : ((tb != 0u) ? INFINITY : 0.0);
+  }
+}
+template <class T>
+__device__ __forceinline__ void slot_receive(const double* s, EnvWork<T>& w, PFState<T>& st) {
+  typedef Slot<T> S;
+  static_for<1, T::NB>([&](auto I) {
+    constexpr int i = I;
+    w.vm[i] = s[S::VM + i]; st.cs[i] = s[S::CS + i]; st.sn[i] = s[S::SN + i];
+    w.vr[i] = w.vm[i] * st.cs[i];   // the iterate's V, as eval_mismatch leaves it (pf_end reads it)
+    w.vi[i] = w.vm[i] * st.sn[i];
+  });
+  st.it = int(s[S::IT]);
+  st.diff = s[S::FLAGS];
+}
+
 // Continue the Newton-Raphson solves of the lanes with st.active (they have done st.it iterations and
 // hold their iterate in w.vm / st.cs / st.sn) until each converges, fails (NaN) or reaches max_iter --
 // NG solves at a time, one per lane group.  On return the owner lanes hold the final iterate, st.it and
@@ -1047,7 +1058,7 @@ template <class T, class JT, bool WFREE = true>
 __device__ __forceinline__ void continue_in_groups(cptr_t C, EnvWork<T>& w, PFState<T>& st, bool mine, double tol, int max_iter,
                                    double* lds, bool keep = false) {
   typedef Slot<T> S;
-  constexpr int G = Shape<T>::G, NG = Shape<T>::NG, NB = T::NB;
+  constexpr int G = Shape<T>::G, NG = Shape<T>::NG;
   const int lane = threadIdx.x & 63;
   const int grp = lane / G;
   LaneView<T> V;
@@ -1061,50 +1072,24 @@ __device__ __forceinline__ void continue_in_groups(cptr_t C, EnvWork<T>& w, PFSt
   const int rank = __popcll(todo & ((1ull << lane) - 1ull));
   for (int base = 0; base < n_todo; base += NG) {
     const bool send = mine && rank >= base && rank < base + NG;
-    if (send) {
-      double* s = lds + (rank - base) * S::SIZE;
-      static_for<1, NB>([&](auto I) {
-        constexpr int i = I;
-        s[S::VM + i] = w.vm[i]; s[S::CS + i] = st.cs[i]; s[S::SN + i] = st.sn[i];
-        s[S::P + i] = w.bus_p[i]; s[S::Q + i] = w.bus_q[i];
-      });
-      s[S::IT] = double(st.it);
-    }
+    if (send) slot_send<T>(lds + (rank - base) * S::SIZE, w, st);
     ANM_WAVE_SYNC();
     const bool gvalid = base + grp < n_todo;           // this group holds a solve
     const bool isbus = V.lane_bus && gvalid;
     double vm = 1.0, cs = 1.0, sn = 0.0, bus_p = 0.0, bus_q = 0.0;
     int it = 0;
-    {
-      const double* s = lds + grp * S::SIZE;
-      if (isbus) { vm = s[S::VM + b]; cs = s[S::CS + b]; sn = s[S::SN + b]; bus_p = s[S::P + b]; bus_q = s[S::Q + b]; }
-      if (gvalid) it = int(s[S::IT]);
-    }
+    if (isbus) slot_load<T>(lds + grp * S::SIZE, b, vm, cs, sn, bus_p, bus_q);
+    if (gvalid) it = int(lds[grp * S::SIZE + S::IT]);
     ANM_WAVE_SYNC();
     unsigned tb, tn;
     newton_groups<T, JT, 0, false, LDSX_FETCH, WFREE>(V, gvalid, vm, cs, sn, bus_p, bus_q, it, tb, tn, tol, max_iter);
 
     // ---- results back to the owner lanes
-    if (isbus) {
-      double* s = lds + grp * S::SIZE;
-      s[S::VM + b] = vm; s[S::CS + b] = cs; s[S::SN + b] = sn;
-      if (b == 1) {
-        s[S::IT] = double(it);
-        s[S::FLAGS] = (tn != 0u) ? NAN : ((tb != 0u) ? INFINITY : 0.0);
-      }
-    }
+    if (isbus) slot_store<T>(lds + grp * S::SIZE, b, vm, cs, sn, it, tb, tn);
     ANM_WAVE_SYNC();
     if (send) {
-      const double* s = lds + (rank - base) * S::SIZE;
-      static_for<1, NB>([&](auto I) {
-        constexpr int i = I;
-        w.vm[i] = s[S::VM + i]; st.cs[i] = s[S::CS + i]; st.sn[i] = s[S::SN + i];
-        w.vr[i] = w.vm[i] * st.cs[i];   // the iterate's V, as eval_mismatch leaves it (pf_end reads it)
-        w.vi[i] = w.vm[i] * st.sn[i];
-      });
-      st.it = int(s[S::IT]);
-      st.diff = s[S::FLAGS];
-      st.active = keep && s[S::FLAGS] == INFINITY;
+      slot_receive<T>(lds + (rank - base) * S::SIZE, w, st);
+      st.active = keep && st.diff == INFINITY;
     }
     ANM_WAVE_SYNC();
   }
@@ -1145,11 +1130,26 @@ struct RowView {
   }
 };
 
+// The sign of x flipped on the lanes whose `flip` holds the sign bit (0 elsewhere): one v_xor_b32 on the high word.
+__device__ __forceinline__ double row_flip(double x, unsigned flip) {
+  return __hiloint2double(__double2hiint(x) ^ int(flip), __double2loint(x));
+}
+__device__ __forceinline__ float row_flip(float x, unsigned flip) { return __uint_as_float(__float_as_uint(x) ^ flip); }
+
 // newton_groups with rows for groups: same arguments, same results (rvalid: the row holds a solve, uniform per row).
-template <class T, class JT>
+// PAIRS: TWO lanes per bus (codegen.row_pair_plan; V initialised for pairs).  Both lanes of a bus are full replicas -- the
+// same loads, W products, Dg, Di, step and update, so nothing ever moves between them, and they hold identical F, so every
+// ballot says what it says with one lane per bus -- except that each forms ONE row of Lk = Jpb Di, Sc = Lk Jbp and Lr = Lk r:
+// replica 0 row 0, replica 1 row 1, by the source expressions of blk_mul and of the one-lane form's Lr0 / Lr1 restricted to
+// that row.  A fold names replica 0 of the child for Sc.a, Sc.b and Lr0 and replica 1 for Sc.c, Sc.d and Lr1
+// (row_pair_fold); every other hand-over names replica 0.  Every floating-point operation that reaches a result is that of
+// one lane per bus on the same operands in the same order: the same bits.  PAIRS guards three places: my row of Jpb, the
+// products behind the pivot, the fold statement.
+template <class T, class JT, bool PAIRS = false>
 __device__ __forceinline__ void newton_rows(const RowView<T>& V, bool rvalid, double& vm, double& cs, double& sn, double bus_p,
                                             double bus_q, int& it, unsigned& tb, unsigned& tn, double tol, int max_iter) {
   static_assert(T::T_ROW != 0, "codegen.row_plan: the topology has no row layout");
+  static_assert(!PAIRS || T::T_ROW2 != 0, "codegen.row_pair_plan: the topology has no row layout with two lanes per bus");
   const double ybb_r = V.ybb_r, ybb_i = V.ybb_i, ybp_r = V.ybp_r, ybp_i = V.ybp_i, ypb_r = V.ypb_r, ypb_i = V.ypb_i;
   const bool isbus = V.lane_bus && rvalid;
   const unsigned long long busm = __builtin_amdgcn_uicmp(isbus ? 1u : 0u, 0u, ICMP_NE);
@@ -1159,6 +1159,8 @@ __device__ __forceinline__ void newton_rows(const RowView<T>& V, bool rvalid, do
   // what an unused lane holds reaches no decision and no result.
   unsigned long long runm = busm;
   const unsigned glo = unsigned(V.rmask & busm), ghi = unsigned((V.rmask & busm) >> 32);   // bus lanes of my row
+  [[maybe_unused]] const bool rep = V.rep;                          // (PAIRS: this lane forms row 1)
+  [[maybe_unused]] const unsigned flip = rep ? 0x80000000u : 0u;
   tb = 0u; tn = 0u;
   it -= rvalid ? 1 : 0;        // the first trip only evaluates: its `it += running` is undone here
   // the voltage of the parent: a bus attached to the slack keeps 1 + 0j, every other bus receives its parent's every trip
@@ -1207,10 +1209,18 @@ __device__ __forceinline__ void newton_rows(const RowView<T>& V, bool rvalid, do
             __builtin_amdgcn_sicmp(it, max_iter, ICMP_SLT);   // NaN > tol is false, like the reference
     const bool all_done = runm == 0ull;   // (the loop is left at the END of the trip, see newton_groups)
 
-    // ---- Jacobian blocks: own diagonal and the two couplings with the parent
+    // ---- Jacobian blocks: own diagonal and the two couplings with the parent.  PAIRS: of Jpb MY ROW alone, (ja, jb),
+    // selected once per trip: row 0 is (-nwpb_i, wpb_r), row 1 (-wpb_r, -nwpb_i)
     Blk<JT> Dg = Blk<JT>{JT(wbb_i - si), JT(sr + wbb_r), JT(sr - wbb_r), JT(si + wbb_i)};
     const Blk<JT> Jbp = Blk<JT>{JT(wbp_i), JT(wbp_r), JT(-wbp_r), JT(wbp_i)};
-    const Blk<JT> Jpb = Blk<JT>{JT(-nwpb_i), JT(wpb_r), JT(-wpb_r), JT(-nwpb_i)};
+    [[maybe_unused]] Blk<JT> Jpb;
+    [[maybe_unused]] JT ja, jb;
+    if constexpr (PAIRS) {
+      const JT jpr = JT(wpb_r), jpi = JT(nwpb_i);
+      ja = -(rep ? jpr : jpi); jb = row_flip(rep ? jpi : jpr, flip);
+    } else {
+      Jpb = Blk<JT>{JT(-nwpb_i), JT(wpb_r), JT(-wpb_r), JT(-nwpb_i)};
+    }
     JT r0 = JT(fr), r1 = JT(fi);
     // ---- The unconditional schedule.  EVERY lane runs every level's pivot code and every depth's step code; no level and
     // no depth is a region.  A bus still ends with the bits of "pivot at my height, step at my depth":
@@ -1223,23 +1233,38 @@ __device__ __forceinline__ void newton_rows(const RowView<T>& V, bool rvalid, do
     // after the last level, whatever their heights.
     // ---- elimination by height: the folds of a level (every child of height h - 1 into its parent, whatever the parent's
     // height), then the pivot.  Lr = Lk r is finished by the lead of the next level's folds (Lr0 / Lr1 hold Lk.b r1, Lk.d r1).
+    // PAIRS: (Sc.a, Sc.b) is MY ROW of Sc, Lr0 my entry of Lr and Lka my Lk.a, resp. Lk.c; Sc.c, Sc.d, Lr1 and Lkc are not
+    // used.  Sc.b is finished by the lead as well (it holds Lk.b Jbp.d, resp. Lk.d Jbp.d).
     Blk<JT> Di = Dg, Sc = Dg;
     JT Lr0 = JT(0), Lr1 = JT(0), Lka = JT(0), Lkc = JT(0);
     static_for<0, T::T_MAXH + 1>([&](auto H) {
       constexpr int h = H;
       if constexpr (h > 0) {
         static_assert(T::T_ROW_CH_OFF[h + 1] > T::T_ROW_CH_OFF[h], "a level above 0 folds the child that makes it one");
-        row_points<T, ROW_CH, T::T_ROW_CH_OFF[h], T::T_ROW_CH_OFF[h + 1]>([&](auto FIRST, ANM_ROW_PARAMS) {
-          if constexpr (FIRST) row_fold_lead<ANM_ROW_ARGS>(Dg, r0, r1, Sc, Lr0, Lr1, Lka, Lkc, onej);
-          else row_fold<ANM_ROW_ARGS>(Dg, r0, r1, Sc, Lr0, Lr1, onej);
+        row_points<T, PAIRS ? ROW_CH_PAIR : ROW_CH, T::T_ROW_CH_OFF[h], T::T_ROW_CH_OFF[h + 1]>([&](auto FIRST, ANM_ROW_PARAMS) {
+          if constexpr (PAIRS) {
+            if constexpr (FIRST) row_pair_fold_lead<ANM_ROW_ARGS>(Dg, r0, r1, Sc.a, Sc.b, Lr0, Lka, Jbp.b, onej);
+            else row_pair_fold<ANM_ROW_ARGS>(Dg, r0, r1, Sc.a, Sc.b, Lr0, onej);
+          } else {
+            if constexpr (FIRST) row_fold_lead<ANM_ROW_ARGS>(Dg, r0, r1, Sc, Lr0, Lr1, Lka, Lkc, onej);
+            else row_fold<ANM_ROW_ARGS>(Dg, r0, r1, Sc, Lr0, Lr1, onej);
+          }
         });
       }
       Di = blk_inv_fast(Dg);
       if constexpr (h < T::T_MAXH) {
-        const Blk<JT> Lk = blk_mul(Jpb, Di);
-        Sc = blk_mul(Lk, Jbp);
-        Lr0 = Lk.b * r1; Lka = Lk.a;
-        Lr1 = Lk.d * r1; Lkc = Lk.c;
+        if constexpr (PAIRS) {
+          Lka = fm(ja, Di.a, jb * Di.c);                 // blk_mul(Jpb, Di), my row
+          const JT Lkb = fm(ja, Di.b, jb * Di.d);
+          Sc.a = fm(Lka, Jbp.a, Lkb * Jbp.c);            // blk_mul(Lk, Jbp), my row
+          Sc.b = Lkb * Jbp.d;
+          Lr0 = Lkb * r1;
+        } else {
+          const Blk<JT> Lk = blk_mul(Jpb, Di);
+          Sc = blk_mul(Lk, Jbp);
+          Lr0 = Lk.b * r1; Lka = Lk.a;
+          Lr1 = Lk.d * r1; Lkc = Lk.c;
+        }
       }
     });
     // ---- back substitution by depth (Di holds the inverted pivots).  The step d = Di r of every lane leads the hand-over of
@@ -1256,172 +1281,21 @@ __device__ __forceinline__ void newton_rows(const RowView<T>& V, bool rvalid, do
     });
     d0 = fm(Di.a, r0, Di.b * r1);
     d1 = fm(Di.c, r0, Di.d * r1);
-    // ---- update of the running rows (see newton_groups, VPOLY)
-    const bool upd = __builtin_amdgcn_inverse_ballot_w64(runm);
-    const double dth = double(d0);
-    const unsigned long long bigm = __builtin_amdgcn_fcmp(fabs(dth), 0.78, FCMP_UGT) & runm;  // NaN counts
-    double sd_, cd_;
-    if (bigm == 0ull) {
-      sincos_kernel<true>(dth, 0, sd_, cd_);
-    } else {
-      sincos_medium<true>(dth, sd_, cd_);
-      const bool ish = !(fabs(dth) < SINCOS_MEDIUM_MAX);
-      if ((__builtin_amdgcn_uicmp(ish ? 1u : 0u, 0u, ICMP_NE) & runm) != 0ull) {
-        const SinCos r = sincos_huge(dth);
-        sd_ = ish ? r.s : sd_;
-        cd_ = ish ? r.c : cd_;
-      }
-    }
-    if (upd) {
-      vm = fma(-double(d1), fabs(vm), vm);
-      const double t1 = sn * sd_, t2 = cs * sd_;
-      cs = fma3<false>(cs, cd_, t1);
-      sn = fma3<true>(sn, cd_, t2);
-    }
-    if (all_done) break;
-  }
-}
-
-// The sign of x flipped on the lanes whose `flip` holds the sign bit (0 elsewhere): one v_xor_b32 on the high word.
-__device__ __forceinline__ double row_flip(double x, unsigned flip) {
-  return __hiloint2double(__double2hiint(x) ^ int(flip), __double2loint(x));
-}
-__device__ __forceinline__ float row_flip(float x, unsigned flip) { return __uint_as_float(__float_as_uint(x) ^ flip); }
-
-// newton_rows on TWO lanes per bus (codegen.row_pair_plan): same arguments, same results.  Both lanes of a bus are full
-// replicas -- the same loads, W products, Dg, Di, step and update, so nothing ever moves between them -- except that each
-// forms ONE row of Lk = Jpb Di, Sc = Lk Jbp and Lr = Lk r: replica 0 row 0, replica 1 row 1, by the source expressions of
-// blk_mul and of newton_rows' Lr0 / Lr1 restricted to that row.  A fold names replica 0 of the child for Sc.a, Sc.b and Lr0
-// and replica 1 for Sc.c, Sc.d and Lr1 (row_fold2); every other hand-over names replica 0.  Every floating-point operation
-// that reaches a result is that of newton_rows on the same operands in the same order: the same bits.
-template <class T, class JT>
-__device__ __forceinline__ void newton_row_pairs(const RowView<T>& V, bool rvalid, double& vm, double& cs, double& sn, double bus_p,
-                                                 double bus_q, int& it, unsigned& tb, unsigned& tn, double tol, int max_iter) {
-  static_assert(T::T_ROW != 0 && T::T_ROW2 != 0, "codegen.row_pair_plan: the topology has no row layout with two lanes per bus");
-  const double ybb_r = V.ybb_r, ybb_i = V.ybb_i, ybp_r = V.ybp_r, ybp_i = V.ybp_i, ypb_r = V.ypb_r, ypb_i = V.ypb_i;
-  const bool isbus = V.lane_bus && rvalid;
-  // both replicas are bus lanes: they hold identical F, so every ballot says what it says with one lane per bus
-  const unsigned long long busm = __builtin_amdgcn_uicmp(isbus ? 1u : 0u, 0u, ICMP_NE);
-  unsigned long long runm = busm;   // (see newton_rows: what an unused lane holds reaches no decision and no result)
-  const unsigned glo = unsigned(V.rmask & busm), ghi = unsigned((V.rmask & busm) >> 32);   // bus lanes of my row
-  const bool rep = V.rep;
-  const unsigned flip = rep ? 0x80000000u : 0u;
-  tb = 0u; tn = 0u;
-  it -= rvalid ? 1 : 0;        // the first trip only evaluates: its `it += running` is undone here
-  double vpr = 1.0, vpi = 0.0;
-  double one = 1.0;
-  asm volatile("" : "+v"(one));
-  const JT onej = JT(one);
-  __builtin_amdgcn_s_waitcnt(0);
-  for (;;) {
-    double vr, vi, m2;
-    if constexpr (T::T_ROW_PAR_N == 0) {
-      vr = vm * cs; vi = vm * sn; m2 = vm * vm;
-    } else {
-      row_points<T, ROW_PAR, 0, T::T_ROW_PAR_N>([&](auto FIRST, ANM_ROW_PARAMS) {
-        if constexpr (FIRST) row_mov_lead<ANM_ROW_ARGS>(vpr, vpi, vr, vi, m2, vm, cs, sn);
-        else row_mov<ANM_ROW_ARGS>(vpr, vpi, vr, vi);
-      });
-    }
-    const double wbb_r = ybb_r * m2, wbb_i = -(ybb_i * m2);
-    const double pr = fma(vr, vpr, vi * vpi), pim = fma(vi, vpr, -(vr * vpi));
-    const double wbp_r = fma(ybp_r, pr, ybp_i * pim), wbp_i = fma(ybp_r, pim, -(ybp_i * pr));
-    const double wpb_r = fma(ypb_r, pr, -(ypb_i * pim)), nwpb_i = fma(ypb_r, pim, ypb_i * pr);   // (imaginary part: sign flipped)
-    double sr, si;
-    if constexpr (T::T_ROW_CH_N == 0) {
-      sr = wbb_r + wbp_r; si = wbb_i + wbp_i;
-    } else {
-      row_points<T, ROW_WS, 0, T::T_ROW_CH_N>([&](auto FIRST, ANM_ROW_PARAMS) {
-        if constexpr (FIRST) row_wsum_lead<ANM_ROW_ARGS>(sr, si, wbb_r, wbp_r, wbb_i, wbp_i, wpb_r, nwpb_i, one);
-        else row_wsum<ANM_ROW_ARGS>(sr, si, wpb_r, nwpb_i, one);
-      });
-    }
-    const double fr = sr - bus_p, fi = si - bus_q;
-    const unsigned long long badm = __builtin_amdgcn_fcmp(fmax(fabs(fr), fabs(fi)), tol, FCMP_UGT);
-    const unsigned long long nanm = __builtin_amdgcn_fcmp(fr, fi, FCMP_UNO);
-    tb = row_pick(badm, glo, ghi);
-    tn = row_pick(nanm, glo, ghi);
-    it = row_count(it, runm);   // the update applied in the previous trip
-    runm &= __builtin_amdgcn_uicmp(tb, 0u, ICMP_NE) & ~__builtin_amdgcn_uicmp(tn, 0u, ICMP_NE) &
-            __builtin_amdgcn_sicmp(it, max_iter, ICMP_SLT);   // NaN > tol is false, like the reference
-    const bool all_done = runm == 0ull;
-
-    // ---- Jacobian blocks: own diagonal, the coupling Jbp, and MY ROW of Jpb = {-nwpb_i, wpb_r, -wpb_r, -nwpb_i}, selected
-    // once per trip: row 0 is (-nwpb_i, wpb_r), row 1 (-wpb_r, -nwpb_i)
-    Blk<JT> Dg = Blk<JT>{JT(wbb_i - si), JT(sr + wbb_r), JT(sr - wbb_r), JT(si + wbb_i)};
-    const Blk<JT> Jbp = Blk<JT>{JT(wbp_i), JT(wbp_r), JT(-wbp_r), JT(wbp_i)};
-    const JT jpr = JT(wpb_r), jpi = JT(nwpb_i);
-    const JT ja = -(rep ? jpr : jpi), jb = row_flip(rep ? jpi : jpr, flip);
-    JT r0 = JT(fr), r1 = JT(fi);
-    // ---- the unconditional schedule of newton_rows: every lane runs every level's pivot and every depth's step.
-    // S0 / S1: my row of Sc (S1 is finished by the lead of the next level's folds: it holds Lk.b Jbp.d, resp. Lk.d Jbp.d);
-    // Lr: my entry of Lr = Lk r (finished there as well: it holds Lk.b r1, resp. Lk.d r1); Lka: Lk.a, resp. Lk.c.
-    Blk<JT> Di = Dg;
-    JT S0 = JT(0), S1 = JT(0), Lr = JT(0), Lka = JT(0);
-    static_for<0, T::T_MAXH + 1>([&](auto H) {
-      constexpr int h = H;
-      if constexpr (h > 0) {
-        static_assert(T::T_ROW_CH_OFF[h + 1] > T::T_ROW_CH_OFF[h], "a level above 0 folds the child that makes it one");
-        row_points2<T, T::T_ROW_CH_OFF[h], T::T_ROW_CH_OFF[h + 1]>([&](auto FIRST, ANM_ROW2_PARAMS) {
-          if constexpr (FIRST) row_fold2_lead<ANM_ROW2_ARGS>(Dg, r0, r1, S0, S1, Lr, Lka, Jbp.b, onej);
-          else row_fold2<ANM_ROW2_ARGS>(Dg, r0, r1, S0, S1, Lr, onej);
-        });
-      }
-      Di = blk_inv_fast(Dg);
-      if constexpr (h < T::T_MAXH) {
-        Lka = fm(ja, Di.a, jb * Di.c);                 // blk_mul(Jpb, Di), my row
-        const JT Lkb = fm(ja, Di.b, jb * Di.d);
-        S0 = fm(Lka, Jbp.a, Lkb * Jbp.c);              // blk_mul(Lk, Jbp), my row
-        S1 = Lkb * Jbp.d;
-        Lr = Lkb * r1;
-      }
-    });
-    JT d0, d1;
-    static_for<1, T::T_MAXD + 1>([&](auto Dd) {
-      constexpr int dd = Dd;
-      static_assert(T::T_ROW_PAR_OFF[dd + 1] > T::T_ROW_PAR_OFF[dd], "a depth above 0 has a parent's step to receive");
-      row_points<T, ROW_PAR, T::T_ROW_PAR_OFF[dd], T::T_ROW_PAR_OFF[dd + 1]>([&](auto FIRST, ANM_ROW_PARAMS) {
-        if constexpr (FIRST) row_step_lead<ANM_ROW_ARGS>(r0, r1, d0, d1, Di, Jbp.a, Jbp.b);
-        else row_fma<ANM_ROW_ARGS>(r0, r1, d0, d1, Jbp.a, Jbp.b);
-      });
-    });
-    d0 = fm(Di.a, r0, Di.b * r1);
-    d1 = fm(Di.c, r0, Di.d * r1);
-    // ---- update of the running rows (see newton_groups, VPOLY)
-    const bool upd = __builtin_amdgcn_inverse_ballot_w64(runm);
-    const double dth = double(d0);
-    const unsigned long long bigm = __builtin_amdgcn_fcmp(fabs(dth), 0.78, FCMP_UGT) & runm;  // NaN counts
-    double sd_, cd_;
-    if (bigm == 0ull) {
-      sincos_kernel<true>(dth, 0, sd_, cd_);
-    } else {
-      sincos_medium<true>(dth, sd_, cd_);
-      const bool ish = !(fabs(dth) < SINCOS_MEDIUM_MAX);
-      if ((__builtin_amdgcn_uicmp(ish ? 1u : 0u, 0u, ICMP_NE) & runm) != 0ull) {
-        const SinCos r = sincos_huge(dth);
-        sd_ = ish ? r.s : sd_;
-        cd_ = ish ? r.c : cd_;
-      }
-    }
-    if (upd) {
-      vm = fma(-double(d1), fabs(vm), vm);
-      const double t1 = sn * sd_, t2 = cs * sd_;
-      cs = fma3<false>(cs, cd_, t1);
-      sn = fma3<true>(sn, cd_, t2);
-    }
+    // ---- update of the running rows
+    update_iterate(runm, d0, d1, vm, cs, sn);
     if (all_done) break;
   }
 }
 
 // continue_in_groups with four solves a pass, one per row: the same LDS slots, the same results in st.it / st.diff.
-// PAIRS: the topology has a pair plan, and the pass runs on two lanes per bus (newton_row_pairs; only replica 0 of a bus
-// writes its results back) unless one_lane (uniform) asks for newton_rows.  The hand-over around the loop is ONE copy for
-// both: a second copy of it costs the kernels that hold an environment per lane 20 and more registers.
+// PAIRS: the topology has a pair plan, and the pass runs on two lanes per bus (newton_rows<.., true>; only replica 0 of a
+// bus writes its results back) unless one_lane (uniform) asks for one.  The hand-over around the loop is instantiated ONCE
+// for both: a second instantiation costs the kernels that hold an environment per lane 20 and more registers.
 template <class T, class JT, bool PAIRS = false>
 __device__ __forceinline__ void continue_in_rows(cptr_t C, EnvWork<T>& w, PFState<T>& st, bool mine, double tol, int max_iter,
                                                  double* lds, bool one_lane = true) {
   typedef Slot<T> S;
-  constexpr int NR = 4, NB = T::NB;
+  constexpr int NR = 4;
   static_assert(Shape<T>::NG >= NR, "the hand-over slots of the wavefront hold a solve per row");
   const int lane = threadIdx.x & 63;
   const int row = lane >> 4;
@@ -1434,54 +1308,28 @@ __device__ __forceinline__ void continue_in_rows(cptr_t C, EnvWork<T>& w, PFStat
   const int rank = __popcll(todo & ((1ull << lane) - 1ull));
   for (int base = 0; base < n_todo; base += NR) {
     const bool send = mine && rank >= base && rank < base + NR;
-    if (send) {
-      double* s = lds + (rank - base) * S::SIZE;
-      static_for<1, NB>([&](auto I) {
-        constexpr int i = I;
-        s[S::VM + i] = w.vm[i]; s[S::CS + i] = st.cs[i]; s[S::SN + i] = st.sn[i];
-        s[S::P + i] = w.bus_p[i]; s[S::Q + i] = w.bus_q[i];
-      });
-      s[S::IT] = double(st.it);
-    }
+    if (send) slot_send<T>(lds + (rank - base) * S::SIZE, w, st);
     ANM_WAVE_SYNC();
     const bool rvalid = base + row < n_todo;           // this row holds a solve
     const bool isbus = V.lane_bus && rvalid;
     double vm = 1.0, cs = 1.0, sn = 0.0, bus_p = 0.0, bus_q = 0.0;
     int it = 0;
-    {
-      const double* s = lds + row * S::SIZE;
-      if (isbus) { vm = s[S::VM + b]; cs = s[S::CS + b]; sn = s[S::SN + b]; bus_p = s[S::P + b]; bus_q = s[S::Q + b]; }
-      if (rvalid) it = int(s[S::IT]);
-    }
+    if (isbus) slot_load<T>(lds + row * S::SIZE, b, vm, cs, sn, bus_p, bus_q);
+    if (rvalid) it = int(lds[row * S::SIZE + S::IT]);
     ANM_WAVE_SYNC();
     unsigned tb, tn;
     if constexpr (PAIRS) {
-      if (pairs) newton_row_pairs<T, JT>(V, rvalid, vm, cs, sn, bus_p, bus_q, it, tb, tn, tol, max_iter);
-      else newton_rows<T, JT>(V, rvalid, vm, cs, sn, bus_p, bus_q, it, tb, tn, tol, max_iter);
+      if (pairs) newton_rows<T, JT, true>(V, rvalid, vm, cs, sn, bus_p, bus_q, it, tb, tn, tol, max_iter);
+      else newton_rows<T, JT, false>(V, rvalid, vm, cs, sn, bus_p, bus_q, it, tb, tn, tol, max_iter);
     } else {
-      newton_rows<T, JT>(V, rvalid, vm, cs, sn, bus_p, bus_q, it, tb, tn, tol, max_iter);
+      newton_rows<T, JT, false>(V, rvalid, vm, cs, sn, bus_p, bus_q, it, tb, tn, tol, max_iter);
     }
 
     // ---- results back to the owner lanes (V.rep: never set on one lane per bus)
-    if (isbus && !V.rep) {
-      double* s = lds + row * S::SIZE;
-      s[S::VM + b] = vm; s[S::CS + b] = cs; s[S::SN + b] = sn;
-      if (b == 1) {
-        s[S::IT] = double(it);
-        s[S::FLAGS] = (tn != 0u) ? NAN : ((tb != 0u) ? INFINITY : 0.0);
-      }
-    }
+    if (isbus && !V.rep) slot_store<T>(lds + row * S::SIZE, b, vm, cs, sn, it, tb, tn);
     ANM_WAVE_SYNC();
     if (send) {
-      const double* s = lds + (rank - base) * S::SIZE;
-      static_for<1, NB>([&](auto I) {
-        constexpr int i = I;
-        w.vm[i] = s[S::VM + i]; st.cs[i] = s[S::CS + i]; st.sn[i] = s[S::SN + i];
-        w.vr[i] = w.vm[i] * st.cs[i];   // the iterate's V, as eval_mismatch leaves it (pf_end reads it)
-        w.vi[i] = w.vm[i] * st.sn[i];
-      });
-      st.it = int(s[S::IT]);
-      st.diff = s[S::FLAGS];
+      slot_receive<T>(lds + (rank - base) * S::SIZE, w, st);
       st.active = false;
     }
     ANM_WAVE_SYNC();
@@ -1495,9 +1343,9 @@ __device__ __forceinline__ void continue_in_rows(cptr_t C, EnvWork<T>& w, PFStat
 //    0  n <= 4 solves: rows.  More: groups up to iteration ANM_MID_CAP_DEFAULT (every converging solve seen needs <= 9),
 //       then the survivors on rows if at most 4 are left, else on groups to the cap;
 //    1  always rows;   -1  never;
-//    2  the policy of 0 with the rows on ONE lane per bus (newton_rows) even where the topology has a pair plan.
-// A row pass runs on two lanes per bus (newton_row_pairs: a shorter trip) where the topology has a pair plan (T_ROW2), else
-// on one.  A topology without a row plan (T_ROW = 0) keeps groups.
+//    2  the policy of 0 with the rows on ONE lane per bus even where the topology has a pair plan.
+// A row pass runs on two lanes per bus (newton_rows<.., true>: a shorter trip) where the topology has a pair plan (T_ROW2),
+// else on one.  A topology without a row plan (T_ROW = 0) keeps groups.
 template <class T, class JT, bool ROWS = true>
 __device__ __forceinline__ void continue_collective(cptr_t C, EnvWork<T>& w, PFState<T>& st, bool mine, double tol, int max_iter,
                                                     int rowc, double* lds) {

@@ -1,5 +1,5 @@
-"""GPU tier: the row continuation on TWO lanes per bus (group::newton_row_pairs: each replica of a bus forms one row of Lk,
-Sc and Lr) against one lane per bus (group::newton_rows, row_continuation=2) and against lane groups (-1).  The contract
+"""GPU tier: the row continuation on TWO lanes per bus (group::newton_rows<.., PAIRS = true>: each replica of a bus forms one row of Lk,
+Sc and Lr) against one lane per bus (PAIRS = false, row_continuation=2) and against lane groups (-1).  The contract
 is bit-identity of every output, on every entry point that inlines group::continue_collective.
 
 Where the diverging solves come from.  A series-mode step takes its loads from the task's table, the same for every

@@ -1,4 +1,4 @@
-"""CPU tier: codegen.row_pair_plan -- the row layout with TWO lanes per bus (csrc/anm_group.hpp: newton_row_pairs), each
+"""CPU tier: codegen.row_pair_plan -- the row layout with TWO lanes per bus (csrc/anm_group.hpp: newton_rows<.., PAIRS = true>), each
 replica forming one row of Lk = Jpb Di, Sc = Lk Jbp and Lr = Lk r -- checked as DATA: when a pair plan exists, who sits in
 the destination banks of every hand-over, and one trip's elimination and back substitution replayed from the tables in
 NumPy (row_newbcast emulated with bank masks, every lane running every level, unused lanes seeded with NaN) against the
