@@ -14,6 +14,8 @@ _TOP_LEVEL = {  # the names gym_anm exports at top level (gym_anm/__init__.py:5-
     "MPCAgentPerfectStream": ("gym_anm_amd.agents", "MPCAgentPerfectStream"),
     # (... and of the series-noise task with correlated noise)
     "MPCAgentPerfectChain": ("gym_anm_amd.agents", "MPCAgentPerfectChain"),
+    # (... and the informed baseline of both that does not know the future draws)
+    "MPCAgentExpected": ("gym_anm_amd.agents", "MPCAgentExpected"),
 }
 
 

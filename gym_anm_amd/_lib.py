@@ -117,6 +117,13 @@ class MpcChain(MpcStream):
     _fields_ = [("exo_rho", C.c_void_p), ("exo_innov", C.c_void_p), ("exo_z", C.c_void_p)]
 
 
+class MpcExpect(C.Structure):
+    """anm_mpc_expect: the tables and noise states the expected forecast reads (anm_mpc_act_expect_f64; every pointer a device
+    pointer, exo_rho and exo_z null for a task without correlated noise)"""
+    _fields_ = [("exo_mode", C.c_int32), ("exo_low", C.c_void_p), ("exo_high", C.c_void_p), ("exo_noise", C.c_void_p),
+                ("exo_rho", C.c_void_p), ("exo_z", C.c_void_p)]
+
+
 class SolverOpts(C.Structure):
     """anm_solver_opts.  row_continuation: 0 the library's policy, 1 always rows, -1 always lane groups, 2 the policy with
     the row passes on one lane per bus even where the topology has a pair layout (include/anm_mi355x.h)"""
@@ -183,6 +190,8 @@ ABI = {
                                + [C.POINTER(MpcOpts), C.POINTER(MpcStream), _P]),
     "anm_mpc_act_chain_f64": (C.c_int, [C.c_void_p, C.c_int64, _P, _P, _P, C.c_int32, _P, _P, C.c_int32] + [_P] * 8
                               + [C.POINTER(MpcOpts), C.POINTER(MpcChain), _P]),
+    "anm_mpc_act_expect_f64": (C.c_int, [C.c_void_p, C.c_int64, _P, _P, _P, C.c_int32, _P, _P, C.c_int32] + [_P] * 8
+                               + [C.POINTER(MpcOpts), C.POINTER(MpcExpect), _P]),
     "anm_gather_obs_f64": (C.c_int, [C.c_int64, C.c_int32, _P, C.c_int32, C.c_int32, _P, _P, C.c_int32, _P, _P, _P, _P, _P,
                                      _P]),
     "anm_test_row_dpp": (C.c_int, [_P, _P, _P, _P]),
@@ -195,7 +204,7 @@ ABI = {
 
 # entry points of modes that live in the GPU kernels alone: a backend that is not the GPU library (the host test double)
 # may lack them -- the host layer refuses those modes on such a backend before it would call them
-GPU_ONLY = ("anm_model_set_io", "anm_mpc_act_stream_f64", "anm_mpc_act_chain_f64", "anm_test_row_dpp")
+GPU_ONLY = ("anm_model_set_io", "anm_mpc_act_stream_f64", "anm_mpc_act_chain_f64", "anm_mpc_act_expect_f64", "anm_test_row_dpp")
 
 
 def bind(cdll, optional=()):
@@ -301,8 +310,9 @@ def load_for_topology(topo, impl=None) -> Backend:
 
 
 MPC_ABI = ("anm_last_error", "anm_topology_signature", "anm_mpc_create", "anm_mpc_destroy", "anm_mpc_dims_of", "anm_mpc_get_tables",
-           "anm_mpc_solve_f64", "anm_mpc_act_f64", "anm_mpc_act_stream_f64", "anm_mpc_act_chain_f64")
-MPC_FORECAST_CONSTANT, MPC_FORECAST_PERFECT, MPC_FORECAST_STREAM, MPC_FORECAST_CHAIN = 1, 2, 3, 4
+           "anm_mpc_solve_f64", "anm_mpc_act_f64", "anm_mpc_act_stream_f64", "anm_mpc_act_chain_f64",
+           "anm_mpc_act_expect_f64")
+MPC_FORECAST_CONSTANT, MPC_FORECAST_PERFECT, MPC_FORECAST_STREAM, MPC_FORECAST_CHAIN, MPC_FORECAST_EXPECT = 1, 2, 3, 4, 5
 
 
 class MpcBackend:

@@ -1,2 +1,3 @@
 """Batched MPC baseline policies (the reference's ``gym_anm/agents``)."""
-from .mpc import MPCAgent, MPCAgentConstant, MPCAgentPerfect, MPCAgentPerfectChain, MPCAgentPerfectStream  # noqa: F401
+from .mpc import (MPCAgent, MPCAgentConstant, MPCAgentExpected, MPCAgentPerfect, MPCAgentPerfectChain,  # noqa: F401
+                  MPCAgentPerfectStream)

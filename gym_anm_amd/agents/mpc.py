@@ -15,6 +15,8 @@ of charge (``mpc.py:390-417``).  So here
   the step kernels (``exogenous="uniform"`` / ``"series_noise"``): its forecast is the tasks' own random stream,
   evaluated ahead; :class:`MPCAgentPerfectChain` is the same for the series-noise task with correlated noise
   (``exo_corr=``): the step's AR(1) recurrence rolled forward from the environment's noise states;
+* :class:`MPCAgentExpected` is the informed baseline of those drawn tasks that does not know the future draws: the
+  conditional mean of the noise given the task's current state, mapped like a draw;
 * :class:`DCOPFProgram` spells the reference's program out row by row (``min q.x, l <= A x <= u``); nothing in
   the solve uses it -- it is what the tests check a solution's feasibility against.
 
@@ -237,7 +239,8 @@ class BatchedDCOPF:
         """``MPCAgent.act`` as ONE launch (``anm_mpc_act_f64``): the forecasts are gathered inside the kernel -- ``forecast``
         1: constant, from the state rows of ``env``; 2: perfect, from its periodic tables; 3: the stream of a task drawn
         inside the step kernels, evaluated ahead (``anm_mpc_act_stream_f64``); 4: the same for the correlated series-noise
-        task, rolled forward from ``env.exo_z`` (``anm_mpc_act_chain_f64``) -- and the first stage's set-points come back
+        task, rolled forward from ``env.exo_z`` (``anm_mpc_act_chain_f64``); 5: the expected forecast of a drawn task, the
+        noise states rolled forward without draws (``anm_mpc_act_expect_f64``) -- and the first stage's set-points come back
         as the clipped MW action rows ``[E, 2 n_gen + 2 n_des]`` (a persistent buffer)."""
         d = self.dims
         E = int(env.num_envs)
@@ -245,7 +248,7 @@ class BatchedDCOPF:
         if getattr(self, "_action", None) is None or self._action.shape[0] != E:
             self._action = torch.zeros((E, 2 * d.n_gen + 2 * d.n_des), dtype=torch.float64, device=self.device)
         series_ptr, period = None, 0
-        if forecast == 2 or (forecast in (3, 4) and getattr(env, "_series", None) is not None):
+        if forecast == 2 or (forecast in (3, 4, 5) and getattr(env, "_series", None) is not None):
             if getattr(self, "_series_src", None) is not env._series:
                 self._series_src = env._series
                 self._series_dev = torch.as_tensor(env._series, dtype=torch.float64, device=self.device).contiguous()
@@ -257,6 +260,8 @@ class BatchedDCOPF:
             return self._act_stream(env, E, same, aux, series_ptr, period, soc, act_low, act_high)
         if forecast == 4:
             return self._act_chain(env, E, same, aux, series_ptr, period, soc, act_low, act_high)
+        if forecast == 5:
+            return self._act_expect(env, E, same, aux, series_ptr, period, soc, act_low, act_high)
         with self._device_ctx():
             rc = self.backend.lib.anm_mpc_act_f64(
                 self._handle, E, int(forecast), env._state_buf.data_ptr(), None if same is None else env._state_obs.data_ptr(),
@@ -317,6 +322,30 @@ class BatchedDCOPF:
                 self.u0.data_ptr(), self.objective.data_ptr(), self.iters.data_ptr(), self.info.data_ptr(), C.byref(self.opts),
                 C.byref(st), self._stream_ptr())
         self.backend.check(rc, "anm_mpc_act_chain_f64")
+        return self._action
+
+    def _act_expect(self, env, E, same, aux, series_ptr, period, soc, act_low, act_high):
+        from .. import _lib
+
+        if not getattr(env, "_drawn", False):
+            raise E_.ArgsError("the expected forecast needs an environment with exogenous='uniform' or 'series_noise'")
+        # device copies of the ends, the amplitude table and rho (host arrays of the environment; None where the task has
+        # none), cached per environment; exo_z is the environment's own tensor, read in place
+        if getattr(self, "_expect_src", None) is not env:
+            dev = lambda a: None if a is None else torch.tensor(np.array(a, dtype=np.float64), device=self.device)  # noqa: E731
+            self._expect_src, self._expect_dev = env, tuple(dev(a) for a in (env.exo_low, env.exo_high, env.exo_noise, env.exo_corr))
+        lo, hi, amp, rho = self._expect_dev
+        ptr = lambda t: None if t is None else t.data_ptr()  # noqa: E731
+        st = _lib.MpcExpect(exo_mode=_lib.EXO_SERIES_NOISE if env._noisy else _lib.EXO_UNIFORM, exo_low=lo.data_ptr(),
+                            exo_high=hi.data_ptr(), exo_noise=ptr(amp), exo_rho=ptr(rho), exo_z=None if rho is None else env.exo_z.data_ptr())
+        with self._device_ctx():
+            rc = self.backend.lib.anm_mpc_act_expect_f64(
+                self._handle, E, env._state_buf.data_ptr(), None if same is None else env._state_obs.data_ptr(),
+                None if same is None else same.data_ptr(), int(env._state_buf.shape[1]), None if aux is None else aux.data_ptr(),
+                series_ptr, period, soc.data_ptr(), act_low.data_ptr(), act_high.data_ptr(), self._action.data_ptr(),
+                self.u0.data_ptr(), self.objective.data_ptr(), self.iters.data_ptr(), self.info.data_ptr(), C.byref(self.opts),
+                C.byref(st), self._stream_ptr())
+        self.backend.check(rc, "anm_mpc_act_expect_f64")
         return self._action
 
     @property
@@ -387,13 +416,15 @@ class MPCAgent:
         state of charge, a batched environment of this package that has what the kernel reads."""
         cls = type(self)
         mode = self.FUSED_FORECAST
-        stock = {1: MPCAgentConstant, 2: MPCAgentPerfect, 3: MPCAgentPerfectStream, 4: MPCAgentPerfectChain}.get(mode)
-        symbol = {3: "anm_mpc_act_stream_f64", 4: "anm_mpc_act_chain_f64"}.get(mode, "anm_mpc_act_f64")
-        # what the kernel reads: the tables (2), a drawn mode (3), the noise states (4); the time index in the last column
-        # where a table is indexed
+        stock = {1: MPCAgentConstant, 2: MPCAgentPerfect, 3: MPCAgentPerfectStream, 4: MPCAgentPerfectChain,
+                 5: MPCAgentExpected}.get(mode)
+        symbol = {3: "anm_mpc_act_stream_f64", 4: "anm_mpc_act_chain_f64", 5: "anm_mpc_act_expect_f64"}.get(mode, "anm_mpc_act_f64")
+        # what the kernel reads: the tables (2), a drawn mode (3, 5), the noise states (4); the time index in the last
+        # column where a table is indexed
         has = {1: True, 2: getattr(env, "_series", None) is not None, 3: bool(getattr(env, "_drawn", False)),
-               4: bool(getattr(env, "_noisy", False)) and getattr(env, "exo_z", None) is not None}.get(mode, False)
-        indexed = mode in (2, 4) or (mode == 3 and getattr(env, "_noisy", False))
+               4: bool(getattr(env, "_noisy", False)) and getattr(env, "exo_z", None) is not None,
+               5: bool(getattr(env, "_drawn", False))}.get(mode, False)
+        indexed = mode in (2, 4) or (mode in (3, 5) and getattr(env, "_noisy", False))
         return (stock is not None and cls.forecast is stock.forecast and cls.solve is MPCAgent.solve and cls._soc is MPCAgent._soc
                 and hasattr(self.solver.backend.lib, symbol) and hasattr(env, "_state_buf") and has
                 and env._state_buf.shape[1] >= 2 * env.simulator.model.N_device + env.simulator.model.N_des
@@ -464,7 +495,10 @@ class MPCAgentPerfect(MPCAgent):
     (``mpc_perfect.py:24-40``).
 
     On a ``exogenous="series_noise"`` task this is the PROFILE forecast -- the noise-free table the noise is added to --
-    not a perfect one: the agent that knows the draws too is :class:`MPCAgentPerfectStream`.  A task without tables
+    not a perfect one: the agent that knows the draws too is :class:`MPCAgentPerfectStream`
+    (:class:`MPCAgentPerfectChain` with ``exo_corr=``), and the informed baseline that does NOT know them -- the profile
+    plus the conditional mean of the noise given the task's current noise state, which this forecast ignores -- is
+    :class:`MPCAgentExpected`.  A task without tables
     (``exogenous="uniform"``, a host hook) has no such forecast: ``ArgsError``."""
 
     FUSED_FORECAST = 2
@@ -585,6 +619,58 @@ class MPCAgentPerfectChain(MPCAgent):
             env.rng_seed, env.env_offset, env._reset_count.cpu().numpy(), env.timestep.cpu().numpy(), self.planning_steps,
             env.state[:, -1].cpu().numpy().astype(np.int64), env.exo_z.cpu().numpy(), env._series, env.exo_noise, env.exo_corr,
             env._exo_innov, env.exo_low, env.exo_high)
+        f = torch.as_tensor(f, dtype=torch.float64, device=self.device)   # [E, n_load + n_gen, N] MW
+        nl = env.simulator.N_load
+        return f[:, :nl] / self._base_t, f[:, nl:] / self._base_t
+
+
+class MPCAgentExpected(MPCAgent):
+    """Conditional-mean forecasts for the tasks drawn INSIDE the step kernels (``exogenous="uniform"``, ``"series_noise"``,
+    with or without ``exo_corr=``): the forecast of an operator who knows the task's noise model and its current state, but
+    not the future draws.  The innovations have mean 0, so with correlated noise stage ``i`` maps the noise state
+    ``rho^(i+1) exo_z`` -- the step kernels' own recurrence with the innovation at its mean, applied ``i + 1`` times -- at
+    table index ``aux + 1 + i``; without correlation it maps a noise of 0, and in uniform mode every stage is the middle of
+    the ends (``rng.exo_forecast_expected`` is the specification).  The stages are the lanes of the solve and the states
+    travel up the group like the chain agent's, without any draw (``anm_mpc_act_expect_f64``, ONE launch per ``act``;
+    ``exo_z`` is only read).
+
+    This is the honest baseline of these tasks: :class:`MPCAgentConstant` ignores the daily profile, :class:`MPCAgentPerfect`
+    ignores the noise state, and the perfect agents (:class:`MPCAgentPerfectStream`, :class:`MPCAgentPerfectChain`) know
+    draws nobody can know.  A pure function of the table index and the row of ``exo_z``: the same for an environment that
+    is terminated or past its limit, and the horizon is not cut at ``max_episode_steps``.  A series-mode or host-hook task
+    draws nothing inside the kernels: ``ArgsError``."""
+
+    FUSED_FORECAST = 5
+
+    @staticmethod
+    def _check_task(exogenous, what):
+        if exogenous not in ("uniform", "series_noise"):
+            raise E_.ArgsError("MPCAgentExpected needs %s with exogenous='uniform' or 'series_noise' (the modes drawn inside the "
+                               "step kernels); this one is in mode %r: a series-mode task is forecast by MPCAgentPerfect, any "
+                               "task by MPCAgentConstant" % (what, exogenous))
+
+    def __init__(self, simulator, *args, **kw):
+        self._check_task(getattr(simulator, "exogenous", None), "the simulator of an environment")
+        super().__init__(simulator, *args, **kw)
+
+    def _drawn_env(self, env):
+        self._check_task(getattr(env, "exogenous", None), "an environment")
+
+    def act(self, env):
+        if not hasattr(env, "vec"):
+            self._drawn_env(env)
+        return super().act(env)
+
+    def forecast(self, env):
+        """The unfused path: the specification itself (``rng.exo_forecast_expected_v``, exact) on the host."""
+        from .. import rng
+
+        self._drawn_env(env)
+        noisy, corr = bool(env._noisy), env.exo_corr is not None
+        f = rng.exo_forecast_expected_v(
+            env.num_envs, self.planning_steps, env.exo_low, env.exo_high,
+            aux=env.state[:, -1].cpu().numpy().astype(np.int64) if noisy else None, z=env.exo_z.cpu().numpy() if corr else None,
+            series=env._series if noisy else None, noise=env.exo_noise if noisy else None, rho=env.exo_corr if corr else None)
         f = torch.as_tensor(f, dtype=torch.float64, device=self.device)   # [E, n_load + n_gen, N] MW
         nl = env.simulator.N_load
         return f[:, :nl] / self._base_t, f[:, nl:] / self._base_t

@@ -120,7 +120,8 @@ struct Opts {
 // from the state row, mpc_constant.py:24-35; perfect: from the task's periodic tables, mpc_perfect.py:24-40) and the
 // first stage's set-points leave as the clipped MW action row -- no forecast tensors, no permute / scale / cat / clip launches.
 struct Act {
-  int mode;                   // 0: off (forecast arrays given); 1: constant forecast; 2: perfect forecast; 3: the stream, 4: the chain (below)
+  int mode;                   // 0: off (forecast arrays given); 1: constant forecast; 2: perfect forecast; 3: the stream, 4: the chain,
+                              // 5: the expected forecast (below)
   const double* state;        // [E][state_dim] state rows, MW: dev_p of the loads, gen_p_max; the time index in the last column
   const double* state_alt;    // rows to read where state_same[e] != 0 (the observation rows: anm_model_bind_state_same), or null
   const uint8_t* state_same;  // [E] or null
@@ -152,6 +153,10 @@ struct Act {
   const double* exo_rho;      // [NL + NG] dev
   const double* exo_innov;    // [NL + NG] dev
   const double* exo_z;        // [E][NL + NG] dev, read only
+  // mode 5 (ANM_MPC_FORECAST_EXPECT, anm_mpc_act_expect_f64): the conditional-mean forecast of a drawn task -- the chain with
+  // every innovation at its mean 0 (act_expect_value below; specification: rng.py, exo_forecast_expected).  Of the fields
+  // above it reads exo_mode, exo_low, exo_high, exo_noise, exo_rho and exo_z (both null: an uncorrelated or a uniform task);
+  // no seed, no timestep, no reset_count, no exo_innov -- it draws nothing.
   // (keeps the tail a multiple of 32 bytes: Act sits inside the kernel argument block, and what follows it there keeps its
   // alignment -- the scalar loads of the arguments are merged by alignment, and with a tail of 24 bytes two of the existing
   // stream instantiations came out 22 and 2 instructions longer; profiles/mpc_chain_kernels.txt)
@@ -167,16 +172,18 @@ struct StreamAt {
   uint32_t t;
   int aux;
 };
+// the table index of stage `stage` (the series-noise mode): series mode's update applied stage + 1 times
+ANM_HD int act_table_at(const Act& a, int64_t env, int stage) {
+  const double* row = ((a.state_same && a.state_same[env]) ? a.state_alt : a.state) + env * a.state_dim;
+  const int t0 = (a.aux_index ? int(a.aux_index[env]) : int(row[a.state_dim - 1])) + 1;
+  return (t0 + stage) % a.period;
+}
 ANM_HD StreamAt act_stream_at(const Act& a, int64_t env, int stage) {
   StreamAt s;
   s.key = ExoUniform::episode_key(a.seed, a.env_offset + uint64_t(env), uint32_t(a.reset_count[env]) - 1u);
   s.t = uint32_t(a.timestep[env]) + 1u + uint32_t(stage);
   s.aux = 0;
-  if (a.exo_mode == ANM_EXO_SERIES_NOISE) {
-    const double* row = ((a.state_same && a.state_same[env]) ? a.state_alt : a.state) + env * a.state_dim;
-    const int t0 = (a.aux_index ? int(a.aux_index[env]) : int(row[a.state_dim - 1])) + 1;
-    s.aux = (t0 + stage) % a.period;
-  }
+  if (a.exo_mode == ANM_EXO_SERIES_NOISE) s.aux = act_table_at(a, env, stage);
   return s;
 }
 // unit: loads by slot, then the non-slack generators (nl + k, with the network's own nl); p.u.
@@ -223,6 +230,26 @@ ANM_HD double act_chain_value(const Act& a, const StreamAt& s, bool on, int64_t 
   const double z = chain_sweep(x, N, a.exo_rho[unit], a.exo_innov[unit], z0, w);
   if (!on) return 0.0;
   const int64_t at = int64_t(unit) * a.period + s.aux;
+  return ExoNoise::map_state(a.exo_noise[at], z, a.series[at], a.exo_low[unit], a.exo_high[unit]) / a.base;
+}
+
+// Expected forecast (mode 5): the conditional mean of the task's draws given what the environment holds now.  The
+// innovations have mean 0, so the mean of the chain is the recurrence itself with w = 0: chain_sweep with w = 0.0 (c w is
+// +0.0 whatever c is: exo_innov is not read), then the mode's map -- the same two functions as the chain forecast, no Philox
+// block, no episode key.  A task without noise states (exo_rho and exo_z null -- wave-uniform: kernel arguments) has z = +0.0
+// at every stage and skips the sweep; the uniform mode is ExoUniform::map at u = 0.5.  `aux`: act_table_at of the lane (0
+// where it is not `on`).  To be called by EVERY lane of the wavefront, outside divergent code; a lane that is not `on`
+// dereferences nothing per environment and returns 0.
+template <class X>
+ANM_HD double act_expect_value(const Act& a, int aux, bool on, int64_t env, int unit, int n_exo, int N, const X& x) {
+  if (a.exo_mode != ANM_EXO_SERIES_NOISE) return on ? ExoUniform::map(a.exo_low[unit], a.exo_high[unit], 0.5) / a.base : 0.0;
+  double z = 0.0;
+  if (a.exo_rho) {
+    const double z0 = on ? a.exo_z[env * n_exo + unit] : 0.0;
+    z = chain_sweep(x, N, a.exo_rho[unit], 1.0, z0, 0.0);
+  }
+  if (!on) return 0.0;
+  const int64_t at = int64_t(unit) * a.period + aux;
   return ExoNoise::map_state(a.exo_noise[at], z, a.series[at], a.exo_low[unit], a.exo_high[unit]) / a.base;
 }
 
@@ -749,6 +776,7 @@ struct Step {
 // One lane's run of the whole solve.  STREAM: the forecasts are the stream's (Act, mode 3), drawn by the lane in the
 // prologue -- the episode key once, then the units; nothing of the draws lives on into the iterations.  STREAM == 2: the
 // chain (Act, mode 4): the same draws, rolled through the AR(1) recurrence from exo_z by a sweep over the group's lanes.
+// STREAM == 3: the expected forecast (Act, mode 5): that sweep with the innovations at their mean, no draws at all.
 template <class T, int STREAM = 0, class X>
 ANM_HD void solve(cptr_t C, const IO& io, const Opts& opt, int64_t env, bool valid, int N, X& x, double* lane_lds = nullptr) {
   typedef Sz<T> S;
@@ -773,7 +801,15 @@ ANM_HD void solve(cptr_t C, const IO& io, const Opts& opt, int64_t env, bool val
     double pl[pos(NL)];
     constexpr bool PAD = is_padded<T>::value;
     const int nl = PAD ? io.nl : NL, ng = PAD ? io.ng : NG;   // (a topology's kernel: compile-time constants)
-    if constexpr (STREAM == 2) {
+    if constexpr (STREAM == 3) {
+      const int aux = (on && io.act.exo_mode == ANM_EXO_SERIES_NOISE) ? act_table_at(io.act, env, i) : 0;
+      // (l >= nl, g >= ng: wave-uniform -- the exchanges inside stay outside divergent code)
+      ANM_UFOR (int l = 0; l < NL; ++l) pl[l] = l >= nl ? 0.0 : act_expect_value(io.act, aux, on, env, l, nl + ng, N, x);
+      ANM_UFOR (int g = 0; g < NG; ++g) {
+        const double fc = g >= ng ? 0.0 : act_expect_value(io.act, aux, on, env, nl + g, nl + ng, N, x);
+        ln.wd[g] = fmax(fmin(C[S::T_GPMAX + g], fc) - C[S::T_GPMIN + g], 0.0);
+      }
+    } else if constexpr (STREAM == 2) {
       StreamAt at{0, 0, 0};
       if (on) at = act_stream_at(io.act, env, i);
       // (l >= nl, g >= ng: wave-uniform -- the exchanges inside stay outside divergent code)
@@ -1180,7 +1216,8 @@ struct WaveGroup {
 };
 
 // STREAM 1: the instantiations of anm_mpc_act_stream_f64 (solve: the lanes draw their forecasts from the tasks' stream);
-// 2: those of anm_mpc_act_chain_f64 (... and roll the noise states forward from exo_z)
+// 2: those of anm_mpc_act_chain_f64 (... and roll the noise states forward from exo_z); 3: those of anm_mpc_act_expect_f64
+// (the noise states rolled forward with the innovations at their mean: no draws)
 template <class T, int MODE, int STREAM = 0>
 __global__ __launch_bounds__(64) void k_mpc(cptr_t C, IO io, Opts opt, int64_t n_envs, int N, int G) {
   if constexpr (Sz<T>::FITS) {

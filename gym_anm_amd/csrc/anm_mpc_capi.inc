@@ -15,12 +15,16 @@ bool mpc_lds_attribute() {   // above the default per-workgroup limit: ask for t
          hipFuncSetAttribute((const void*)mpc::k_mpc<TT, 2, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) == hipSuccess &&
          hipFuncSetAttribute((const void*)mpc::k_mpc<TT, 0, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) == hipSuccess &&
          hipFuncSetAttribute((const void*)mpc::k_mpc<TT, 1, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) == hipSuccess &&
-         hipFuncSetAttribute((const void*)mpc::k_mpc<TT, 2, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) == hipSuccess;
+         hipFuncSetAttribute((const void*)mpc::k_mpc<TT, 2, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) == hipSuccess &&
+         hipFuncSetAttribute((const void*)mpc::k_mpc<TT, 0, 3>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) == hipSuccess &&
+         hipFuncSetAttribute((const void*)mpc::k_mpc<TT, 1, 3>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) == hipSuccess &&
+         hipFuncSetAttribute((const void*)mpc::k_mpc<TT, 2, 3>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) == hipSuccess;
 }
 
 // one group of G lanes per environment: one thread (N = 1), a part of a DPP row (N <= 16), half or all of a wavefront
 // STREAM 1: the instantiations whose lanes draw the forecasts from the tasks' stream (anm_mpc_act_stream_f64); 2: ... and
-// roll the correlated task's noise states forward from exo_z (anm_mpc_act_chain_f64)
+// roll the correlated task's noise states forward from exo_z (anm_mpc_act_chain_f64); 3: the expected forecast, the noise
+// states rolled forward without draws (anm_mpc_act_expect_f64)
 extern "C++" template <class TT, int STREAM = 0>
 void launch_mpc(unsigned grid, hipStream_t s, anm_mpc* m, const mpc::IO& io, const mpc::Opts& o, int64_t num_envs, int G) {
   const size_t lds_bytes = mpc::Sz<TT>::LDS_BYTES;
@@ -126,7 +130,8 @@ int anm_mpc_get_tables(const anm_mpc* m, double* out) {
 }
 
 static int mpc_launch(anm_mpc* m, int64_t num_envs, mpc::IO io, const anm_mpc_opts* opts, void* stream, const char* who) {
-  const bool drawn = io.act.mode == ANM_MPC_FORECAST_STREAM, chain = io.act.mode == ANM_MPC_FORECAST_CHAIN;
+  const bool drawn = io.act.mode == ANM_MPC_FORECAST_STREAM, chain = io.act.mode == ANM_MPC_FORECAST_CHAIN,
+             expect = io.act.mode == ANM_MPC_FORECAST_EXPECT;
   typedef mpc::Sz<Topo> S;
   mpc::Opts o{1e-11, 40};
   if (opts) {
@@ -146,10 +151,13 @@ static int mpc_launch(anm_mpc* m, int64_t num_envs, mpc::IO io, const anm_mpc_op
   hipStream_t s = static_cast<hipStream_t>(stream);
   if (full) {
     if constexpr (S::FITS) {
-      if (chain) launch_mpc<Topo, 2>(grid, s, m, io, o, num_envs, G);
+      if (expect) launch_mpc<Topo, 3>(grid, s, m, io, o, num_envs, G);
+      else if (chain) launch_mpc<Topo, 2>(grid, s, m, io, o, num_envs, G);
       else if (drawn) launch_mpc<Topo, 1>(grid, s, m, io, o, num_envs, G);
       else launch_mpc<Topo>(grid, s, m, io, o, num_envs, G);
     } else { g_err = std::string(who) + ": with its angle rows this network has too many rows per stage for the MPC kernel"; return -1; }
+  } else if (expect) {
+    launch_mpc<TopoNoTheta, 3>(grid, s, m, io, o, num_envs, G);
   } else if (chain) {
     launch_mpc<TopoNoTheta, 2>(grid, s, m, io, o, num_envs, G);
   } else if (drawn) {
@@ -174,13 +182,15 @@ int anm_mpc_solve_f64(anm_mpc* m, int64_t num_envs, const double* p_load_forecas
   return mpc_launch(m, num_envs, io, opts, stream, "anm_mpc_solve_f64");
 }
 
-// what anm_mpc_act_f64, anm_mpc_act_stream_f64 and anm_mpc_act_chain_f64 share: the checks of the common arguments, the
-// Act, the launch.  `chain`: the three device arrays of the correlated task (with `exo` its stream part), or null
+// what anm_mpc_act_f64, anm_mpc_act_stream_f64, anm_mpc_act_chain_f64 and anm_mpc_act_expect_f64 share: the checks of the
+// common arguments, the Act, the launch.  `chain`: the three device arrays of the correlated task (with `exo` its stream
+// part), or null; `expect`: the arrays of the expected forecast (then `exo` and `chain` are null), or null
 static int mpc_act(anm_mpc* m, int64_t num_envs, int32_t forecast, const double* state, const double* state_alt,
                    const uint8_t* state_same, int32_t state_dim, const int32_t* aux_index, const double* series,
                    int32_t period, const double* soc, const double* act_low, const double* act_high, double* action,
                    double* u0, double* objective, int32_t* iters, double* info, const anm_mpc_opts* opts,
-                   const anm_mpc_stream* exo, const anm_mpc_chain* chain, void* stream, const char* who) {
+                   const anm_mpc_stream* exo, const anm_mpc_chain* chain, const anm_mpc_expect* expect, void* stream,
+                   const char* who) {
   typedef mpc::Sz<Topo> S;
   const std::string w(who);
   if (!m || !state || !action || !act_low || !act_high || (m->ng + m->ns > 0 && !u0) || !objective || !iters)
@@ -189,7 +199,8 @@ static int mpc_act(anm_mpc* m, int64_t num_envs, int32_t forecast, const double*
   if (state_same && !state_alt) return fail((w + ": state_same given without the rows to read instead").c_str());
   const int sdim = 2 * m->nd + m->ns + m->ng;
   if (state_dim < sdim) return fail((w + ": state_dim is smaller than the state vector").c_str());
-  const bool table = forecast == ANM_MPC_FORECAST_PERFECT || (exo && exo->exo_mode == ANM_EXO_SERIES_NOISE);
+  const bool table = forecast == ANM_MPC_FORECAST_PERFECT || (exo && exo->exo_mode == ANM_EXO_SERIES_NOISE) ||
+                     (expect && expect->exo_mode == ANM_EXO_SERIES_NOISE);
   if (forecast == ANM_MPC_FORECAST_PERFECT && (!series || period <= 0))
     return fail((w + ": a perfect forecast needs the task's periodic tables").c_str());
   if (exo) {
@@ -202,8 +213,18 @@ static int mpc_act(anm_mpc* m, int64_t num_envs, int32_t forecast, const double*
   }
   if (chain && (!chain->exo_rho || !chain->exo_innov || !chain->exo_z))
     return fail((w + ": the chain forecast needs exo_rho, exo_innov and exo_z (device arrays)").c_str());
+  if (expect) {
+    if (expect->exo_mode != ANM_EXO_UNIFORM && expect->exo_mode != ANM_EXO_SERIES_NOISE)
+      return fail((w + ": exo_mode must be ANM_EXO_UNIFORM or ANM_EXO_SERIES_NOISE (the modes drawn inside the step kernels)").c_str());
+    if (!expect->exo_low || !expect->exo_high) return fail((w + ": the expected forecast needs exo_low and exo_high (device arrays)").c_str());
+    if (table && (!series || period <= 0 || !expect->exo_noise))
+      return fail((w + ": the series-noise mode needs the task's table (series, period) and its amplitudes (exo_noise)").c_str());
+    if (!expect->exo_rho != !expect->exo_z)
+      return fail((w + ": exo_rho and exo_z go together (both device arrays: correlated noise; both null: none)").c_str());
+    if (!table && expect->exo_rho) return fail((w + ": the uniform mode has no noise states (exo_rho and exo_z must be null)").c_str());
+  }
   if (table && !aux_index && state_dim < sdim + 1)
-    return fail((w + (exo ? ": the series-noise mode" : ": a perfect forecast") + " needs the time index (aux_index, or the last column of the state)").c_str());
+    return fail((w + ((exo || expect) ? ": the series-noise mode" : ": a perfect forecast") + " needs the time index (aux_index, or the last column of the state)").c_str());
   if (num_envs <= 0) return 0;
   mpc::Act a{forecast, state, state_alt, state_same, state_dim, aux_index, series, period, m->base_mva, action, act_low, act_high, {0}, 0};
   for (int l = 0; l < m->nl && l < 32; ++l) a.load_col[l] = m->load_col[l];
@@ -223,6 +244,14 @@ static int mpc_act(anm_mpc* m, int64_t num_envs, int32_t forecast, const double*
     a.exo_innov = chain->exo_innov;
     a.exo_z = chain->exo_z;
   }
+  if (expect) {
+    a.exo_mode = expect->exo_mode;
+    a.exo_low = expect->exo_low;
+    a.exo_high = expect->exo_high;
+    a.exo_noise = expect->exo_noise;
+    a.exo_rho = expect->exo_rho;
+    a.exo_z = expect->exo_z;
+  }
   mpc::IO io{nullptr, nullptr, soc, u0, objective, iters, info, nullptr, nullptr, a, 0, 0};
   return mpc_launch(m, num_envs, io, opts, stream, who);
 }
@@ -233,7 +262,7 @@ int anm_mpc_act_f64(anm_mpc* m, int64_t num_envs, int32_t forecast, const double
                     double* u0, double* objective, int32_t* iters, double* info, const anm_mpc_opts* opts, void* stream) {
   if (forecast != ANM_MPC_FORECAST_CONSTANT && forecast != ANM_MPC_FORECAST_PERFECT) return fail("anm_mpc_act_f64: unknown forecast");
   return mpc_act(m, num_envs, forecast, state, state_alt, state_same, state_dim, aux_index, series, period, soc, act_low, act_high,
-                 action, u0, objective, iters, info, opts, nullptr, nullptr, stream, "anm_mpc_act_f64");
+                 action, u0, objective, iters, info, opts, nullptr, nullptr, nullptr, stream, "anm_mpc_act_f64");
 }
 
 int anm_mpc_act_stream_f64(anm_mpc* m, int64_t num_envs, const double* state, const double* state_alt,
@@ -243,7 +272,8 @@ int anm_mpc_act_stream_f64(anm_mpc* m, int64_t num_envs, const double* state, co
                            const anm_mpc_stream* exo, void* stream) {
   if (!exo) return fail("anm_mpc_act_stream_f64: null argument (anm_mpc_stream)");
   return mpc_act(m, num_envs, ANM_MPC_FORECAST_STREAM, state, state_alt, state_same, state_dim, aux_index, series, period, soc,
-                 act_low, act_high, action, u0, objective, iters, info, opts, exo, nullptr, stream, "anm_mpc_act_stream_f64");
+                 act_low, act_high, action, u0, objective, iters, info, opts, exo, nullptr, nullptr, stream,
+                 "anm_mpc_act_stream_f64");
 }
 
 int anm_mpc_act_chain_f64(anm_mpc* m, int64_t num_envs, const double* state, const double* state_alt,
@@ -255,5 +285,17 @@ int anm_mpc_act_chain_f64(anm_mpc* m, int64_t num_envs, const double* state, con
   if (exo->exo.exo_mode != ANM_EXO_SERIES_NOISE)
     return fail("anm_mpc_act_chain_f64: exo_mode must be ANM_EXO_SERIES_NOISE (the mode that has correlated noise)");
   return mpc_act(m, num_envs, ANM_MPC_FORECAST_CHAIN, state, state_alt, state_same, state_dim, aux_index, series, period, soc,
-                 act_low, act_high, action, u0, objective, iters, info, opts, &exo->exo, exo, stream, "anm_mpc_act_chain_f64");
+                 act_low, act_high, action, u0, objective, iters, info, opts, &exo->exo, exo, nullptr, stream,
+                 "anm_mpc_act_chain_f64");
+}
+
+int anm_mpc_act_expect_f64(anm_mpc* m, int64_t num_envs, const double* state, const double* state_alt,
+                           const uint8_t* state_same, int32_t state_dim, const int32_t* aux_index, const double* series,
+                           int32_t period, const double* soc, const double* act_low, const double* act_high, double* action,
+                           double* u0, double* objective, int32_t* iters, double* info, const anm_mpc_opts* opts,
+                           const anm_mpc_expect* exo, void* stream) {
+  if (!exo) return fail("anm_mpc_act_expect_f64: null argument (anm_mpc_expect)");
+  return mpc_act(m, num_envs, ANM_MPC_FORECAST_EXPECT, state, state_alt, state_same, state_dim, aux_index, series, period, soc,
+                 act_low, act_high, action, u0, objective, iters, info, opts, nullptr, nullptr, exo, stream,
+                 "anm_mpc_act_expect_f64");
 }

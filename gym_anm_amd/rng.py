@@ -595,3 +595,73 @@ def exo_forecast_corr_v(seed, env_offset, reset_count, timestep, N, aux, z, seri
         out[:, :, i], z = exo_series_corr_v(seed, env, epoch, ((t + 1 + i) & MASK).astype(np.uint64), (aux + 1 + i) % period, z,
                                             series, noise, rho, innov, low, high)
     return out
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# Expected forecast of the tasks drawn inside the step kernels (``MPCAgentExpected``, anm_mpc_act_expect_f64;
+# csrc/anm_mpc.hpp, Act mode 5): what an operator forecasts who knows the task's noise model and its current state, but
+# not the future draws -- the conditional mean of the noise, mapped like a draw.
+#
+# The innovations w = fma(2, u, -1) have mean 0 (u is uniform on the 53-bit grid of [0, 1), so the mean is -2^-53: nothing),
+# hence the conditional mean of the chain is the step's own recurrence with the innovation at its mean,
+# E[z_(t+1+i) | z_t] = rho^(i+1) z_t.  NORMATIVE, for stage i = 0 .. N-1 and unit u (loads by slot, then the non-slack
+# generators), MW before the division by baseMVA, from the current table index aux and the environment's row z of ``exo_z``
+# at the time of ``act()``:
+#
+# * ``series_noise`` with ``exo_corr``:  zb_(-1) = z_u;  zb_i = fma(rho_u, zb_(i-1), 0.0) -- the recurrence of the mode
+#   (``exo_series_corr``) with w = 0.0: the rounded product c * 0.0 is +0.0 for every valid c, so ``exo_innov`` is no input;
+#   at_i = (aux + 1 + i) % period;  P_i = noise_clip(fma(noise[u, at_i], zb_i, series[u, at_i]), low_u, high_u) -- the one
+#   fma and the compare-select clip of the mode's map;
+# * ``series_noise`` with ``exo_corr=None``:  zb_i = +0.0 at every stage, the same map.  ``exo_corr=0.0`` gives this bit for
+#   bit: fma(0, z, +0.0) = +0.0 for every finite z (an exact zero sum of -0 and +0 is +0);
+# * ``uniform``:  P_i = fma(high_u - low_u, 0.5, low_u) at every stage: the mode's map at u = 0.5.
+#
+# The conditional mean of the NOISE is mapped, so where the clip bites P_i is not the mean of the clipped draw; with ends
+# the noise does not reach it is (up to the rounding of the recurrence).  A pure function of (aux, the row of exo_z): no
+# RNG, ``timestep``, ``reset_count`` or ``env_offset``; an environment that is terminated or past its limit gets the same
+# function, the horizon is not cut at ``max_episode_steps``, and ``exo_z`` is only read.
+# ---------------------------------------------------------------------------------------------------------------------
+def exo_forecast_expected(N, low, high, aux=None, z=None, series=None, noise=None, rho=None):
+    """Expected loads / generator potentials (MW, ``[n_load + n_gen, N]``) of the next N steps of a drawn task: the uniform
+    mode (``series`` None), the series-noise mode from the table index ``aux`` (``rho`` None: no correlation), and with
+    correlated noise from the noise states ``z`` ``[n_exo]`` too."""
+    low, high = np.asarray(low, dtype=np.float64), np.asarray(high, dtype=np.float64)
+    n, N = len(low), int(N)
+    out = np.empty((n, N))
+    if series is None:
+        for u in range(n):
+            out[u, :] = fma(float(high[u]) - float(low[u]), 0.5, float(low[u]))
+        return out
+    series, noise = np.asarray(series, dtype=np.float64), np.asarray(noise, dtype=np.float64)
+    period = series.shape[1]
+    for u in range(n):
+        zb = 0.0 if rho is None else float(z[u])
+        for i in range(N):
+            if rho is not None:
+                zb = fma(float(rho[u]), zb, 0.0)
+            at = (int(aux) + 1 + i) % period
+            out[u, i] = noise_clip(fma(float(noise[u, at]), zb, float(series[u, at])), float(low[u]), float(high[u]))
+    return out
+
+
+def exo_forecast_expected_v(E, N, low, high, aux=None, z=None, series=None, noise=None, rho=None):
+    """``exo_forecast_expected`` for the ``E`` environments of a batch: ``[E, n_load + n_gen, N]`` MW from the per-environment
+    table indices ``aux`` ``[E]`` and noise states ``z`` ``[E, n_exo]``.  EXACT (``fma_v``): it is what the unfused path of
+    the agent feeds the solver, which has to see the bits the fused kernel computes."""
+    low, high = np.asarray(low, dtype=np.float64), np.asarray(high, dtype=np.float64)
+    E, n, N = int(E), len(low), int(N)
+    out = np.empty((E, n, N))
+    if series is None:
+        out[:] = fma_v(high - low, 0.5, low)[None, :, None]
+        return out
+    series, noise = np.asarray(series, dtype=np.float64), np.asarray(noise, dtype=np.float64)
+    aux = np.asarray(aux).astype(np.int64).reshape(-1)
+    zb = np.zeros((E, n)) if rho is None else np.array(z, dtype=np.float64).reshape(E, n)
+    for i in range(N):
+        if rho is not None:
+            zb = fma_v(np.asarray(rho, dtype=np.float64)[None, :], zb, 0.0)
+        at = (aux + 1 + i) % series.shape[1]                               # [E]
+        for u in range(n):
+            x = fma_v(noise[u][at], zb[:, u], series[u][at])
+            out[:, u, i] = np.where(x < low[u], low[u], np.where(x > high[u], high[u], x))
+    return out

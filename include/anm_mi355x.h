@@ -620,6 +620,37 @@ int anm_mpc_act_chain_f64(anm_mpc* m, int64_t num_envs, const double* state, con
                           double* u0, double* objective, int32_t* iters, double* info, const anm_mpc_opts* opts,
                           const anm_mpc_chain* exo, void* stream);
 
+/* The EXPECTED forecast of a task drawn inside the step kernels: the conditional mean of its draws given what the
+ * environment holds now -- the forecast of an operator who knows the task's noise model and its current state but not the
+ * future draws.  The innovations w = 2 u - 1 have mean 0, so the mean of the noise states is the step kernels' recurrence
+ * with the innovation at its mean, E[z_(t+1+i) | z_t] = rho^(i+1) z_t.  Stage i of environment e, unit u, MW:
+ *     series-noise mode, exo_rho and exo_z given:  zb_(-1) = exo_z[e][u],  zb_i = fma(exo_rho[u], zb_(i-1), 0.0)
+ *     series-noise mode, both NULL (no correlation):  zb_i = +0.0
+ *         P_i = clip(fma(exo_noise[u][at_i], zb_i, series[u][at_i]), exo_low[u], exo_high[u]),  at_i = (t + 1 + i) mod period
+ *     uniform mode:  P_i = fma(exo_high[u] - exo_low[u], 0.5, exo_low[u])
+ * by the sweep of anm_mpc_act_chain_f64 over the lanes of the solve, with w = 0 and without any draw: no seed, step index,
+ * epoch or exo_innov enters.  ONE launch, exo_z is only read; the same pure function of the table index and the row of
+ * exo_z for an environment that is terminated or past its limit; the horizon is not cut at the limit; exo_rho = 0 gives the
+ * forecast without correlation bit for bit.  gym_anm_amd/rng.py (exo_forecast_expected) is the specification.  Every pointer
+ * is a DEVICE pointer. */
+typedef struct anm_mpc_expect {
+  int32_t exo_mode;           /* ANM_EXO_UNIFORM or ANM_EXO_SERIES_NOISE */
+  const double* exo_low;      /* [n_load + n_gen] MW */
+  const double* exo_high;
+  const double* exo_noise;    /* [n_load + n_gen][period] MW (series-noise mode), else NULL */
+  const double* exo_rho;      /* [n_load + n_gen], or NULL: no correlation */
+  const double* exo_z;        /* [num_envs][n_load + n_gen], or NULL with exo_rho */
+} anm_mpc_expect;
+#define ANM_MPC_FORECAST_EXPECT 5
+/* anm_mpc_act_chain_f64's arguments with that forecast (anm_mpc_act_f64 refuses 5 as unknown, like 3 and 4).  Refused: a NULL
+ * struct; an exo_mode other than the two above; exo_low or exo_high NULL; the series-noise mode without series, period or
+ * exo_noise; only one of exo_rho / exo_z; either of them in uniform mode.  num_envs <= 0 returns 0. */
+int anm_mpc_act_expect_f64(anm_mpc* m, int64_t num_envs, const double* state, const double* state_alt,
+                           const uint8_t* state_same, int32_t state_dim, const int32_t* aux_index, const double* series,
+                           int32_t period, const double* soc, const double* act_low, const double* act_high, double* action,
+                           double* u0, double* objective, int32_t* iters, double* info, const anm_mpc_opts* opts,
+                           const anm_mpc_expect* exo, void* stream);
+
 /* Offsets of each quantity inside one row of `full` (p.u. / rad), in the order of the reference's
  * STATE_VARIABLES (constants.py:31-48): bus_p, bus_q, bus_v_magn, bus_v_ang, bus_i_magn,
  * bus_i_ang [n_bus each], dev_p, dev_q [n_dev each], des_soc [n_des], gen_p_max [n_gen],
