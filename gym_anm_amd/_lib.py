@@ -54,7 +54,7 @@ class EnvConfig(C.Structure):
     ]  # fmt: skip
 
 
-ENV_TAIL_NONE, ENV_TAIL_EPISODE, ENV_TAIL_NOISE, ENV_TAIL_CORR = 0, 1, 2, 3   # anm_env_config.tail
+ENV_TAIL_NONE, ENV_TAIL_EPISODE, ENV_TAIL_NOISE, ENV_TAIL_CORR, ENV_TAIL_FORECAST = 0, 1, 2, 3, 5   # anm_env_config.tail (4: not used)
 
 
 class EnvConfigEpisode(EnvConfig):
@@ -84,6 +84,17 @@ class EnvConfigCorr(EnvConfigNoise):
     def __init__(self, *a, **kw):
         super().__init__(*a, **kw)
         C.c_int32.from_address(C.addressof(self) + EnvConfig.K.offset + 4).value = ENV_TAIL_CORR
+
+
+class EnvConfigForecast(EnvConfigCorr):
+    """anm_env_config_forecast (tail = ANM_ENV_TAIL_FORECAST): the horizon and the rows of the expected forecast the kernels
+    write (device, ``[E, n_exo, H]``, float64 or -- float32 I/O -- float32).  The correlation trio before them is all set
+    or all null (a task without noise states)."""
+    _fields_ = [("forecast_horizon", C.c_int32), ("exo_forecast", C.c_void_p)]
+
+    def __init__(self, *a, **kw):
+        super().__init__(*a, **kw)
+        C.c_int32.from_address(C.addressof(self) + EnvConfig.K.offset + 4).value = ENV_TAIL_FORECAST
 
 
 class StepWs(C.Structure):

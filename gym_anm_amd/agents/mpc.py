@@ -662,15 +662,21 @@ class MPCAgentExpected(MPCAgent):
         return super().act(env)
 
     def forecast(self, env):
-        """The unfused path: the specification itself (``rng.exo_forecast_expected_v``, exact) on the host."""
+        """The unfused path: the rows the step kernels wrote themselves (``env.exo_forecast``, a float64 environment built
+        with ``forecast_horizon >= planning_steps``: a slice on the device, the prefix property of the forecast), else the
+        specification itself (``rng.exo_forecast_expected_v``, exact) on the host."""
         from .. import rng
 
         self._drawn_env(env)
+        nl = env.simulator.N_load
+        H = getattr(env, "forecast_horizon", None)
+        if H is not None and H >= self.planning_steps and env.exo_forecast.dtype == torch.float64:
+            f = env.exo_forecast[:, :, :self.planning_steps].to(self.device)
+            return f[:, :nl] / self._base_t, f[:, nl:] / self._base_t
         noisy, corr = bool(env._noisy), env.exo_corr is not None
         f = rng.exo_forecast_expected_v(
             env.num_envs, self.planning_steps, env.exo_low, env.exo_high,
             aux=env.state[:, -1].cpu().numpy().astype(np.int64) if noisy else None, z=env.exo_z.cpu().numpy() if corr else None,
             series=env._series if noisy else None, noise=env.exo_noise if noisy else None, rho=env.exo_corr if corr else None)
         f = torch.as_tensor(f, dtype=torch.float64, device=self.device)   # [E, n_load + n_gen, N] MW
-        nl = env.simulator.N_load
         return f[:, :nl] / self._base_t, f[:, nl:] / self._base_t

@@ -140,6 +140,16 @@ __global__ __launch_bounds__(BLOCK) void k_step_general(cptr_t C0, EnvIO io, Sol
   op_step_general<Topo, JT>(C, io, so, n, lds_dyn);
 #endif
 }
+// ... with the expected forecast written beside the state rows (io.forecast bound).  A kernel of its own: a task without
+// the forecast keeps k_step_general's instruction stream
+template <class JT>
+__global__ __launch_bounds__(BLOCK) void k_step_general_fc(cptr_t C0, EnvIO io, SolverOpts so, int64_t n, ClassSel cs) {
+#ifndef ANM_DEV_LANE_GROUPS_ONLY
+  extern __shared__ double lds_dyn[];
+  const cptr_t C = class_constants(C0, cs, int64_t(blockIdx.x) * BLOCK);
+  op_step_general<Topo, JT, true>(C, io, so, n, lds_dyn);
+#endif
+}
 
 template <class JT, bool GROUPS>
 __global__ __launch_bounds__(BLOCK) void k_step_stragglers(cptr_t C, EnvIO io, SolverOpts so, int level) {
@@ -315,6 +325,8 @@ struct anm_model {
   DevBuf<double> d_noise;                     // noisy time series: [n_load + n_gen][period] MW amplitudes
   DevBuf<double> d_corr;                      // ... correlated (anm_env_config_corr): [2][n_load + n_gen] rho, then sqrt(1 - rho^2)
   double* exo_z = nullptr;                    // ... the caller's noise states [E][n_load + n_gen] (device; not owned)
+  DevBuf<ExoForecastIO> d_forecast;           // ... the expected forecast (anm_env_config_forecast; null: off): the block the kernels
+                                              // read -- the tables above, exo_z and the caller's rows [E][n_load + n_gen][H] (not owned)
   EpisodeIO ep{};                             // episode time limit and statistics (anm_env_config.max_episode_steps / .episode)
   int io_mode = ANM_IO_F64;                   // anm_model_set_io: float32 action / obs / reward arrays
   std::vector<cplx> ybus;
@@ -405,7 +417,10 @@ struct Task {
   std::vector<double> ends;         // drawn modes: [2][nexo] low, high
   std::vector<double> ar1;          // correlated noise: [2][nexo] rho, then sqrt(1 - rho^2)
   double* exo_z = nullptr;          // ... the caller's noise states
+  void* exo_forecast = nullptr;     // expected forecast: the caller's rows
+  int forecast_h = 0;               // ... and the horizon (0: off)
   DevBuf<double> series, exo, noise, corr;
+  DevBuf<ExoForecastIO> forecast;
   EpisodeIO ep{};
 };
 
@@ -445,9 +460,13 @@ int check_task(const anm_model* m, const anm_env_config& cfg, Task& t) {
   const bool has_series = cfg.series && cfg.period > 0;
   if (has_series && cfg.K != 1) return fail("series mode needs exactly K = 1 auxiliary variable (the time index)");
   t.period = has_series ? cfg.period : 0;
-  if (cfg.tail < ANM_ENV_TAIL_NONE || cfg.tail > ANM_ENV_TAIL_CORR) return fail("anm_model_set_env: unknown value of tail");
+  // (0 ... 3 and ANM_ENV_TAIL_FORECAST = 5; 4 stays unknown, as it was before the forecast)
+  if (cfg.tail < ANM_ENV_TAIL_NONE || (cfg.tail > ANM_ENV_TAIL_CORR && cfg.tail != ANM_ENV_TAIL_FORECAST))
+    return fail("anm_model_set_env: unknown value of tail");
   if (cfg.tail == ANM_ENV_TAIL_CORR && cfg.exo_mode != ANM_EXO_SERIES_NOISE)
     return fail("anm_model_set_env: correlated noise (tail = ANM_ENV_TAIL_CORR, an anm_env_config_corr) needs exo_mode = ANM_EXO_SERIES_NOISE");
+  if (cfg.tail == ANM_ENV_TAIL_FORECAST && cfg.exo_mode != ANM_EXO_SERIES_NOISE)
+    return fail("anm_model_set_env: the expected forecast (tail = ANM_ENV_TAIL_FORECAST, an anm_env_config_forecast) needs exo_mode = ANM_EXO_SERIES_NOISE");
   const int nexo = m->dims.n_load + m->dims.n_gen;
   const bool classes = m->n_classes() > 1 || m->d_env_class, no_defaults = int(m->exo_default.size()) != 2 * nexo;
   if (cfg.exo_mode == ANM_EXO_SERIES_NOISE) {
@@ -465,11 +484,24 @@ int check_task(const anm_model* m, const anm_env_config& cfg, Task& t) {
         return fail("anm_model_set_env: the amplitudes of the series-noise mode must be finite and >= 0");
     if (!resolve_ends(m, cfg, false, t.ends))
       return fail("anm_model_set_env: the clip ends of the series-noise mode must not be NaN, with exo_low <= exo_high");
-    if (cfg.tail == ANM_ENV_TAIL_CORR) {
+    bool corr = cfg.tail == ANM_ENV_TAIL_CORR;
+    if (cfg.tail == ANM_ENV_TAIL_FORECAST) {
+      // expected forecast: the horizon and the caller's rows; the correlation trio before them is all set or all NULL
+      const anm_env_config_forecast& fc = reinterpret_cast<const anm_env_config_forecast&>(cfg);
+      if (fc.forecast_horizon < 1 || fc.forecast_horizon > 64)
+        return fail("anm_model_set_env: forecast_horizon (anm_env_config_forecast) must be in [1, 64]");
+      if (!fc.exo_forecast) return fail("anm_model_set_env: the expected forecast needs exo_forecast (a device array [num_envs][n_load + n_gen][forecast_horizon])");
+      corr = fc.cfg.exo_rho || fc.cfg.exo_innov || fc.cfg.exo_z;
+      t.forecast_h = fc.forecast_horizon;
+      t.exo_forecast = fc.exo_forecast;
+    }
+    if (corr) {
       // correlated noise: the AR(1) tables, both from the host (the kernels take no square root), and the caller's states
       const anm_env_config_corr& cc = reinterpret_cast<const anm_env_config_corr&>(cfg);
       if (!cc.exo_rho || !cc.exo_innov || !cc.exo_z)
-        return fail("anm_model_set_env: correlated noise needs exo_rho, exo_innov and exo_z (anm_env_config_corr): none may be NULL");
+        return fail(cfg.tail == ANM_ENV_TAIL_FORECAST
+                        ? "anm_model_set_env: exo_rho, exo_innov and exo_z of an anm_env_config_forecast go together: all set (correlated noise) or all NULL"
+                        : "anm_model_set_env: correlated noise needs exo_rho, exo_innov and exo_z (anm_env_config_corr): none may be NULL");
       t.ar1.resize(size_t(2 * nexo));
       for (int k = 0; k < nexo; ++k) {
         const double r = cc.exo_rho[k], c = cc.exo_innov[k];
@@ -500,6 +532,12 @@ int stage_task(const anm_model* m, const anm_env_config& cfg, Task& t) {
   if (!t.ends.empty() && (rc = stage(t.exo, t.ends.data(), t.ends.size(), 8, "hipMalloc(exo ends)", "hipMemcpy(exo ends)"))) return rc;
   if (t.amp && (rc = stage(t.noise, t.amp, cells, 0, "hipMalloc(exo noise)", "hipMemcpy(exo noise)"))) return rc;
   if (!t.ar1.empty() && (rc = stage(t.corr, t.ar1.data(), t.ar1.size(), 8, "hipMalloc(exo corr)", "hipMemcpy(exo corr)"))) return rc;
+  if (t.forecast_h > 0) {   // the block of the expected forecast: the tables just staged (a move keeps their addresses)
+    const int nexo = m->dims.n_load + m->dims.n_gen;
+    const ExoForecastIO f{t.corr.get(), t.corr.get() ? t.exo_z : nullptr, t.noise.get(), t.series.get(), t.exo.get(), t.exo.get() + nexo,
+                          t.exo_forecast, t.period, t.forecast_h};
+    if ((rc = stage(t.forecast, &f, 1, 0, "hipMalloc(exo forecast)", "hipMemcpy(exo forecast)"))) return rc;
+  }
   if (cfg.tail >= ANM_ENV_TAIL_EPISODE && (cfg.max_episode_steps > 0 || cfg.episode)) {
     EpisodeIO& ep = t.ep;
     if (const anm_episode_buffers* b = cfg.episode)
@@ -707,9 +745,11 @@ int anm_model_create(const anm_network_desc* desc, anm_model** out) {
     constexpr size_t worst = (size_t(GL::FULL_OK ? (64 * GL::FSP > GL::B_DOUBLES ? 64 * GL::FSP : GL::B_DOUBLES) : GL::B_DOUBLES) +
                               size_t(64) * size_t(GL::SP)) * sizeof(double);
     if (worst > 64 * 1024) {
-      hipError_t a1 = hipFuncSetAttribute((const void*)k_step_general<float>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-      hipError_t a2 = hipFuncSetAttribute((const void*)k_step_general<double>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-      if (a1 != hipSuccess || a2 != hipSuccess) return give_up(fail_hip(a1 != hipSuccess ? a1 : a2, "k_step_general: LDS size attribute"));
+      for (const void* k : {(const void*)k_step_general<float>, (const void*)k_step_general<double>, (const void*)k_step_general_fc<float>,
+                            (const void*)k_step_general_fc<double>}) {
+        hipError_t a = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+        if (a != hipSuccess) return give_up(fail_hip(a, "k_step_general: LDS size attribute"));
+      }
     }
     hipError_t e = m->t_thread.dev.alloc(m->h_const.size());
     if (e != hipSuccess) return give_up(fail_hip(e, "hipMalloc(constants)"));
@@ -815,6 +855,7 @@ int anm_model_set_env(anm_model* m, const anm_env_config* cfg) {
   m->period = t.period;
   m->exo_mode = cfg->exo_mode;
   m->exo_z = t.exo_z;
+  m->d_forecast = std::move(t.forecast);
   m->ep = t.ep;
   m->env_set = true;
   return upload_const(m);
@@ -1140,6 +1181,7 @@ static int env_io_of_model(const anm_model* m, const char* who, EnvIO& io) {
     io.exo_innov = m->d_corr.get() + (m->dims.n_load + m->dims.n_gen);
     io.exo_z = m->exo_z;
   }
+  io.forecast = m->exo_mode == ANM_EXO_SERIES_NOISE ? m->d_forecast.get() : nullptr;   // expected forecast (null: off)
   io.series = m->d_series.get();
   io.period = m->period;
   io.ep = m->ep;
@@ -1378,6 +1420,7 @@ static int launch_step(anm_model* m, const EnvIO& io_in, int64_t n, const anm_so
   io.state_row_off = int(doubles);               // the state rows follow the buffer the other uses overlay
   const size_t lds_bytes = (doubles + size_t(64) * size_t(S | 1)) * sizeof(double);
   return by_precision(prec, [&](auto jt) {
+    if (io.forecast) return launch("launch k_step_general_fc", k_step_general_fc<decltype(jt)>, grid, BLOCK, lds_bytes, s, C, io, so, n, cs);
     return launch("launch k_step_general", k_step_general<decltype(jt)>, grid, BLOCK, lds_bytes, s, C, io, so, n, cs);
   });
 }

@@ -239,6 +239,23 @@ ANM_HD void episode_step(const EpisodeIO& ep, int64_t e, double r, bool terminat
   }
 }
 
+// The expected forecast of the noisy time series (anm_env_config_forecast): its tables and the caller's rows, as a block in
+// DEVICE memory behind ONE pointer of EnvIO.  The lane-group kernels run at their scalar-register limit: kernel arguments
+// read after the Newton trips stay live across them and spill (through vector lanes: k_radial<double, Topo> went from 168
+// to 169 VGPRs, from three wavefronts per SIMD to two, with the seven pointers as arguments); behind the pointer they are
+// loaded where they are used, after the last of everything else.
+struct ExoForecastIO {
+  const double* rho;        // [NEXO] or null (a task without noise states)
+  const double* z;          // [E, NEXO] the noise states (EnvIO::exo_z) or null
+  const double* noise;      // [NEXO, period]
+  const double* series;     // [NEXO, period]
+  const double* lo;         // [NEXO]
+  const double* hi;         // [NEXO]
+  void* out;                // [E, NEXO, H] MW: doubles, or floats under EnvIO::io32
+  int period;
+  int H;                    // the horizon, 1 ... 64
+};
+
 struct EnvIO {
   int K;                    // number of aux variables
   const double* action;     // [E, ADIM]
@@ -301,6 +318,9 @@ struct EnvIO {
   const double* exo_rho;    // [NEXO] (device)
   const double* exo_innov;  // [NEXO] sqrt(1 - rho^2), formed on the host (device)
   double* exo_z;            // [E, NEXO]
+  // expected forecast of the noisy time series (anm_env_config_forecast; null: off, wave-uniform): wherever a kernel writes
+  // the state row and exo_z of an environment it writes the row of ExoForecastIO::out from what it wrote (ExoNoise::forecast_row)
+  const ExoForecastIO* forecast;   // (device)
 };
 
 // Float32 policy-facing I/O (ANM_IO_F32; gym_anm_amd/io_dtype.py is the specification): the arrays behind EnvIO::action,
@@ -318,6 +338,21 @@ ANM_HD void io_store(double* p, int64_t i, double v, bool f32) {
 }
 // how a piece of code learns the mode: not at all (float64 alone), at compile time, or from EnvIO::io32 at run time
 constexpr int IO_F64 = 0, IO_F32 = 1, IO_RT = 2;
+
+// The forecast row of environment e (the lane's OWN: the caller stores nothing else for another) from the table index its
+// state row just got and its row of the noise states as stored.  One unit after the other, each a serial chain
+// (ExoNoise::forecast_row); the stores go out per lane, H consecutive entries per unit.
+template <int NEXO>
+ANM_HD void store_exo_forecast(const EnvIO& io, int64_t e, int aux) {
+  const ExoForecastIO f = *io.forecast;
+  const bool f32 = io.io32 != 0;
+  static_for<0, NEXO>([&](auto U) {
+    constexpr int u = U;
+    const int64_t zi = e * NEXO + u, o = zi * f.H;
+    ExoNoise::forecast_row(f.z ? f.rho[u] : 0.0, f.z ? f.z[zi] : 0.0, f.noise + u * f.period, f.series + u * f.period, f.lo[u], f.hi[u], aux,
+                           f.period, f.H, [&](int i, double v) { io_store(static_cast<double*>(f.out), o + i, v, f32); });
+  });
+}
 
 // Split an init_state row (anm_env.py / simulator.py:248-268) into transition inputs.
 // (S0: anything indexable -- a row in memory or a register array with constant indices)
@@ -504,6 +539,8 @@ ANM_HD void reset_from(cptr_t C, const EnvIO& io, SolverOpts so, int64_t e, cons
   RowPtrs rows{io.state + e * S, io.obs + e * S};
   if (io.io32) rows.obs32 = reinterpret_cast<float*>(io.obs) + e * S;
   finish_reset<T, Layout<T>::KMAX, S0>(C, w, s0, io.K, io.soc + e * WD, rows);
+  // expected forecast: from the table index the row just got and the noise states this reset stored (or found)
+  if (io.forecast) store_exo_forecast<Dims<T>::NEXO>(io, e, int(s0[T::SDIM]));
   io.converged[e] = w.converged ? 1 : 0;
   io.terminated[e] = 0;
   if (io.timestep) io.timestep[e] = 0;
@@ -1122,7 +1159,9 @@ struct GenLds {
   static constexpr int B_DOUBLES = B_MIN > G_MIN ? B_MIN : G_MIN;  // action / state / obs rows, hand-over slots
 };
 
-template <class T, class JT>
+// FC: the caller serves the expected forecast (io.forecast bound: k_step_general_fc); off, it is not in the code at all -- with
+// a run-time test of the pointer the task without it ran 1.2 us (1.8 %) slower than on the revision before
+template <class T, class JT, bool FC = false>
 __device__ void op_step_general(cptr_t C, const EnvIO& io, SolverOpts so, int64_t n, double* lds) {
   typedef Dims<T> D;
   typedef GenLds<T> G;
@@ -1233,6 +1272,11 @@ __device__ void op_step_general(cptr_t C, const EnvIO& io, SolverOpts so, int64_
   if (store) {
     store_step_scalars<T, KM, true, IO_RT>(io, e, out, true, ts_prev);
     if (io.aux_index && out.write_state) io.aux_index[e] = int32_t(out.row[T::SDIM]);
+    // expected forecast: wherever the state row is written, from its table index (0 in a zero row) and the lane's own
+    // row of exo_z as the draw site stored it
+    if constexpr (FC) {
+      if (out.write_state) store_exo_forecast<D::NEXO>(io, e, int(out.row[T::SDIM]));
+    }
   }
   const bool zero_obs = ctx.absorbing || out.terminated == 1;   // anm_env.py:365-367, 442-446
   const unsigned long long zero_rows = __ballot(zero_obs);

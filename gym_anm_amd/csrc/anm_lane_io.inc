@@ -27,7 +27,10 @@
 //      and sets `dump`.  ANM_LIST_OBS_DUE(zero) is the kernel's: a list observation is due -- zeros (terminal / absorbing:
 //      anm_env.py:365-367, 442-446) or gathered from the electrical state -- on a path all lanes of the environment take
 //      together (every condition around it is uniform over the lane group).  k_radial writes it on the spot, k_mesh notes
-//      it and writes it at its single site (DESIGN 3.6, 3.7).
+//      it and writes it at its single site (DESIGN 3.6, 3.7).  Sets fc_due / fc_at (the kernel's: `bool fc_due = false; int
+//      fc_at = 0;` beside `dump`) wherever it writes the state row.
+//   5  after the dump, outside every do { } while: the expected forecast of the lane's unit (io.e.forecast) where part 4
+//      said it is due.
 #if ANM_LANE_IO_PART == 1   // ---- inputs per device lane
   bool skip = false;        // env in the absorbing terminal state (step mode, no autoreset), or masked out of a reset
   bool resetting = false;
@@ -248,6 +251,10 @@
       }
       ANM_LIST_OBS_DUE(!converged);
     }
+    // (the forecast row is due, part 5, at the table index of the row: the caller's, the drawn one, or 0 where a redraw left
+    // the zero row)
+    fc_due = true;
+    fc_at = mode == 1 ? (sampled ? aux : int(io.e.init_state[e * W_ST + d.SDIM])) : (converged ? aux : 0);
     dump = true;
     break;
   }
@@ -284,8 +291,24 @@
     if (io.e.ep.on) episode_step(io.e.ep, e, rwd, term, io.e.timestep[e] + 1);   // (before the increment below)
     if (io.e.timestep) io.e.timestep[e] += 1;
   }
+  fc_due = true;
+  fc_at = term ? 0 : aux;   // (a terminal step writes the zero row: table index 0, the noise state as stored)
   dump = true;
+#elif ANM_LANE_IO_PART == 5   // ---- modes 1 and 2: the expected forecast, the kernel's last stores
+  // (io.e.forecast bound, wave-uniform; rng.py: exo_forecast_expected)  The load or generator lane forms the H entries of its
+  // own unit from the table index the state row got (fc_at) and the noise state it stored itself at the draw site, re-read
+  // here.  The tables come from the block behind io.e.forecast, loaded HERE: nothing of the feature lives across the Newton
+  // trips but that pointer, and the electrical state is dead by now.  fc_due is set by part 4 alone, which runs for the
+  // lane's OWN environment (env_ok) on the paths that write the state row (not skip).
+  if (fc_due && io.e.forecast && (typ == DEV_LOAD || typ == DEV_CLASSICAL || typ == DEV_RENEWABLE)) {
+    const ExoForecastIO f = *io.e.forecast;
+    const int unit = typ == DEV_LOAD ? slot : d.NLOAD + slot;
+    const int64_t zi = e * (d.NLOAD + d.NGEN) + unit, fo = zi * f.H;
+    const bool f32 = io.e.io32 != 0;
+    ExoNoise::forecast_row(f.z ? f.rho[unit] : 0.0, f.z ? f.z[zi] : 0.0, f.noise + unit * f.period, f.series + unit * f.period, f.lo[unit],
+                           f.hi[unit], fc_at, f.period, f.H, [&](int i, double v) { io_store(static_cast<double*>(f.out), fo + i, v, f32); });
+  }
 #else
-#error "ANM_LANE_IO_PART: 1 ... 4"
+#error "ANM_LANE_IO_PART: 1 ... 5"
 #endif
 #undef ANM_LANE_IO_PART

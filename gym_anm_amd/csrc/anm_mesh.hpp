@@ -1214,6 +1214,8 @@ __global__ __launch_bounds__(WG ? 512 : 256, SW == 2 ? ANM_MESH_MINWAVES2 : SW) 
   // mode and branch -- the branches only decide: lo_mode 0 none, 1 zeros, 2 gather; dump)
   int lo_mode = 0;
   bool dump = false;
+  bool fc_due = false;   // the forecast row is due (anm_lane_io.inc, parts 4 and 5), at table index fc_at
+  int fc_at = 0;
   auto outputs = [&](auto F32c) {
   constexpr bool f32 = decltype(F32c)::value;
 #define ANM_LANE_IO_PART 3
@@ -1275,6 +1277,8 @@ __global__ __launch_bounds__(WG ? 512 : 256, SW == 2 ? ANM_MESH_MINWAVES2 : SW) 
   if (io.e.io32) outputs(std::true_type{});
   else outputs(std::false_type{});
   if (dump) write_full();
+#define ANM_LANE_IO_PART 5
+#include "anm_lane_io.inc"
 }
 #endif  // __HIPCC__
 

@@ -643,6 +643,8 @@ __global__ __launch_bounds__(64, ANM_RADIAL_WAVES) void k_radial(Dims d, const i
 
   // (one call site for the dump: its |z| / arg z code exists once, not once per mode)
   bool dump = false;
+  bool fc_due = false;   // the forecast row is due (anm_lane_io.inc, parts 4 and 5), at table index fc_at
+  int fc_at = 0;
   do {
 #define ANM_LANE_IO_PART 2
 #include "anm_lane_io.inc"
@@ -704,6 +706,8 @@ __global__ __launch_bounds__(64, ANM_RADIAL_WAVES) void k_radial(Dims d, const i
   else outputs(std::false_type{});
   } while (false);
   if (dump) write_full();
+#define ANM_LANE_IO_PART 5
+#include "anm_lane_io.inc"
   ANM_PHASE(5);
 }
 #endif  // __HIPCC__

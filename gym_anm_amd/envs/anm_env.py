@@ -98,7 +98,7 @@ class BatchedANMEnv(GymEnv):
                  num_envs=1, device="cuda", tol=1e-5, max_iter=100, precision="f64", autoreset=False, series=None,
                  env_offset=0, impl=None, straggler_after="auto", straggler_mid="auto", handoff_after="auto", row_continuation=0, track_full=False,
                  fuse_observation=True, variants=None, env_variant=None, exogenous=None, exo_low=None, exo_high=None, exo_noise=None,
-                 exo_corr=None,
+                 exo_corr=None, forecast_horizon=None,
                  max_episode_steps=None, episode_stats=False, io_dtype=None, _backend=None):  # fmt: skip
         GymEnv.reset(self, seed=seed)
         self.K, self.gamma, self.lamb, self.delta_t = K, gamma, lamb, delta_t
@@ -170,7 +170,9 @@ class BatchedANMEnv(GymEnv):
         self._act_high = torch.as_tensor(hi, dtype=self.io_dtype, device=self.device)
         self.check_actions = True
         self._series = None if series is None else np.ascontiguousarray(series, dtype=np.float64)
+        self._check_forecast(forecast_horizon, exogenous)
         self._check_exogenous(exogenous, exo_low, exo_high, exo_noise, exo_corr, variants is not None or env_variant is not None)
+        self._alloc_forecast()
         self._obs_is_state = self.obs_values is not None and self.obs_values == self.state_values
         self._set_task()
         self._set_observation_gather(fuse_observation)
@@ -299,6 +301,39 @@ class BatchedANMEnv(GymEnv):
         if not ordered:
             raise E.ArgsError("exo_low / exo_high must not be NaN, with exo_low <= exo_high")
 
+    def _check_forecast(self, forecast_horizon, exogenous):
+        """forecast_horizon=H (series-noise mode; an int in [1, 64], the planning horizons k_mpc accepts): the step and reset
+        kernels write, wherever they write a state row, the EXPECTED loads and generator potentials of the next H steps into
+        `exo_forecast` ([num_envs, n_exo, H] MW, io_dtype; units: loads by device id, then non-slack generators) -- the
+        second input of a policy, beside the observation.  After every reset() and step(), for every environment,
+        exo_forecast[e] == rng.exo_forecast_expected(H, exo_low, exo_high, aux=state[e, -1], z=exo_z[e], ...) bit for bit
+        (float32 I/O: that double rounded once); undefined before the first reset.  None: no buffer, nothing changes."""
+        self.forecast_horizon = self.exo_forecast = self.forecast_space = None
+        if forecast_horizon is None:
+            return
+        if isinstance(forecast_horizon, bool) or not isinstance(forecast_horizon, (int, np.integer)):
+            raise E.ArgsError("The argument forecast_horizon is %r but should be an int in [1, 64] or None." % (forecast_horizon,))
+        if not 1 <= int(forecast_horizon) <= 64:
+            raise E.ArgsError("The argument forecast_horizon is %d but should be in [1, 64]." % int(forecast_horizon))
+        if exogenous != "series_noise":
+            # (uniform mode: the forecast is a constant; series and host-hook mode: nothing is drawn in the kernels)
+            raise E.ArgsError("forecast_horizon needs exogenous='series_noise'")
+        if self.simulator.backend.device_type != "cuda":
+            raise E.EnvInitializationError("forecast_horizon needs the GPU library: this backend writes no forecast in its kernels")
+        self.forecast_horizon = int(forecast_horizon)
+
+    def _alloc_forecast(self):
+        """The rows the kernels write and their space, once the task's ends are resolved."""
+        if self.forecast_horizon is None:
+            return
+        H, n_exo = self.forecast_horizon, len(self.exo_low)
+        self.exo_forecast = torch.zeros((self.num_envs, n_exo, H), dtype=self.io_dtype, device=self.device)
+        lo = np.ascontiguousarray(np.broadcast_to(self.exo_low[:, None], (n_exo, H)))
+        hi = np.ascontiguousarray(np.broadcast_to(self.exo_high[:, None], (n_exo, H)))
+        if self._io32:   # bounds rounded to nearest, like the observation's: the conversion is monotone
+            lo, hi = _io.observation_bounds32(lo, hi)
+        self.forecast_space = Box(low=lo, high=hi, dtype=np.float32 if self._io32 else np.float64)
+
     def _env_config(self):
         """The anm_env_config of the task: the struct that ends with the last field the task uses.  The arrays behind its
         pointers stay alive on self (`_cfg_keep`: the observation bounds; the exogenous tables; `exo_z`)."""
@@ -325,6 +360,9 @@ class BatchedANMEnv(GymEnv):
             self.exo_z = torch.zeros((self.num_envs, len(self.exo_corr)), dtype=torch.float64, device=self.device)
             kw.update(exo_rho=self.exo_corr.ctypes.data_as(_lib.c_double_p),
                       exo_innov=self._exo_innov.ctypes.data_as(_lib.c_double_p), exo_z=self.exo_z.data_ptr())
+        if self.forecast_horizon is not None:   # (without exo_corr the correlation trio before it stays null)
+            struct = _lib.EnvConfigForecast
+            kw.update(forecast_horizon=self.forecast_horizon, exo_forecast=self.exo_forecast.data_ptr())
         return struct(**kw)
 
     def _set_task(self):

@@ -95,6 +95,9 @@ class _Task(BatchedANMEnv):
             # (the modes that draw inside the step kernels are refused by the library behind a batch view)
             raise E.EnvInitializationError("MixedBatchedANMEnv steps through batch views, which take no exogenous mode drawn in "
                                            "the kernels (exogenous='uniform' / 'series_noise'): use BatchedANMEnv")
+        if spec.get("forecast_horizon") is not None:
+            raise E.EnvInitializationError("MixedBatchedANMEnv writes no expected forecast (forecast_horizon= belongs to "
+                                           "exogenous='series_noise', which batch views do not take): use BatchedANMEnv")
         self.hooked = spec.get("series") is None
         dt, lamb = spec.get("delta_t", 0.25), spec.get("lamb", 100)
         if self.hooked:

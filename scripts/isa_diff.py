@@ -1,10 +1,12 @@
 """Compare the gfx950 code of two builds of a library, kernel by kernel, as text.
 
-    python scripts/isa_diff.py LIB_A LIB_B [name filter]
+    python scripts/isa_diff.py [--mnemonics] LIB_A LIB_B [name filter]
 
 Each library's gfx950 code object is extracted (as scripts/kernel_resources.py does) and disassembled with
 llvm-objdump -d; addresses, encodings and the numbering of labels are dropped.  One line per kernel: `identical`, or the
 instruction counts of both and the first differing instruction.  Exit status 1 when some kernel differs or is missing.
+--mnemonics: compare the mnemonic streams alone (operands dropped) -- a kernel whose arguments moved inside the kernarg
+segment, or whose registers were renumbered, is then still `identical`.
 """
 import os
 import re
@@ -46,11 +48,16 @@ def kernels(lib, td, tag):
 
 
 def main():
+    mnemonics = "--mnemonics" in sys.argv
+    if mnemonics:
+        sys.argv.remove("--mnemonics")
     if len(sys.argv) < 3:
         sys.exit(__doc__)
     flt = sys.argv[3] if len(sys.argv) > 3 else ""
     with tempfile.TemporaryDirectory() as td:
         a, b = kernels(sys.argv[1], td, "a"), kernels(sys.argv[2], td, "b")
+    if mnemonics:
+        a, b = ({k: [ins.split(" ")[0] for ins in v] for k, v in x.items()} for x in (a, b))
     differ = False
     for name in sorted(set(a) | set(b)):
         dem = subprocess.run(["c++filt", name], capture_output=True, text=True).stdout.strip()
