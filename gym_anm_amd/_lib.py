@@ -135,6 +135,13 @@ class MpcExpect(C.Structure):
                 ("exo_rho", C.c_void_p), ("exo_z", C.c_void_p)]
 
 
+class IoMap(C.Structure):
+    """anm_io_map: the affine policy I/O of anm_model_set_io_map (HOST arrays, copied by the call; a pair / quartet left
+    NULL is not mapped; io_affine.py)"""
+    _fields_ = [(k, c_double_p) for k in ["act_mid", "act_half", "act_low", "act_high", "obs_scale", "obs_bias"]] + \
+               [("reward_scale", C.c_double)]  # fmt: skip
+
+
 class SolverOpts(C.Structure):
     """anm_solver_opts.  row_continuation: 0 the library's policy, 1 always rows, -1 always lane groups, 2 the policy with
     the row passes on one lane per bus even where the topology has a pair layout (include/anm_mi355x.h)"""
@@ -185,6 +192,7 @@ ABI = {
     "anm_model_bind_env_classes": (C.c_int, [C.c_void_p, _P, C.c_int64]),
     "anm_model_bind_state_same": (C.c_int, [C.c_void_p, _P]),
     "anm_model_set_io": (C.c_int, [C.c_void_p, C.c_int32]),
+    "anm_model_set_io_map": (C.c_int, [C.c_void_p, C.POINTER(IoMap)]),
     "anm_model_bind_nr_diff": (C.c_int, [C.c_void_p, _P]),
     "anm_model_bind_nr_start": (C.c_int, [C.c_void_p, _P]),
     "anm_model_bind_view": (C.c_int, [C.c_void_p, C.POINTER(BatchView)]),
@@ -215,7 +223,7 @@ ABI = {
 
 # entry points of modes that live in the GPU kernels alone: a backend that is not the GPU library (the host test double)
 # may lack them -- the host layer refuses those modes on such a backend before it would call them
-GPU_ONLY = ("anm_model_set_io", "anm_mpc_act_stream_f64", "anm_mpc_act_chain_f64", "anm_mpc_act_expect_f64", "anm_test_row_dpp")
+GPU_ONLY = ("anm_model_set_io", "anm_model_set_io_map", "anm_mpc_act_stream_f64", "anm_mpc_act_chain_f64", "anm_mpc_act_expect_f64", "anm_test_row_dpp")
 
 
 def bind(cdll, optional=()):

@@ -12,8 +12,10 @@
 
 #include <algorithm>
 #include <array>
+#include <cmath>
 #include <cstdio>
 #include <cstring>
+#include <limits>
 #include <new>
 #include <string>
 #include <utility>
@@ -128,6 +130,18 @@ __global__ __launch_bounds__(BLOCK, ANM_ROWS_WAVES) void k_step_rows_io32(cptr_t
   __shared__ double lds[64 * (Topo::SDIM + 2)];
   const cptr_t C = class_constants(C0, cs, int64_t(blockIdx.x) * BLOCK);
   op_step_rows<Topo, JT, false, EP, true>(C, io, so, n, lds);
+#endif
+}
+
+// the fast path through the affine I/O map (anm_model_set_io_map), float64 or float32 arrays: again kernels of their own,
+// the four above carry none of it.  The episode settings are served at run time (io.ep.on, as in k_step_rows_ep): two
+// instantiations per solve precision, not four
+template <class JT, bool IO32>
+__global__ __launch_bounds__(BLOCK, ANM_ROWS_WAVES) void k_step_rows_map(cptr_t C0, EnvIO io, SolverOpts so, int64_t n, ClassSel cs) {
+#ifndef ANM_DEV_LANE_GROUPS_ONLY   // (tuning builds of the lane-group kernels alone: minutes less to compile)
+  __shared__ double lds[64 * (Topo::SDIM + 2)];
+  const cptr_t C = class_constants(C0, cs, int64_t(blockIdx.x) * BLOCK);
+  op_step_rows<Topo, JT, false, true, IO32, true>(C, io, so, n, lds);
 #endif
 }
 
@@ -329,6 +343,7 @@ struct anm_model {
                                               // read -- the tables above, exo_z and the caller's rows [E][n_load + n_gen][H] (not owned)
   EpisodeIO ep{};                             // episode time limit and statistics (anm_env_config.max_episode_steps / .episode)
   int io_mode = ANM_IO_F64;                   // anm_model_set_io: float32 action / obs / reward arrays
+  DevBuf<double> d_iomap;                     // anm_model_set_io_map (null: off): the block of IoMap the kernels read
   std::vector<cplx> ybus;
 
   std::array<Tables*, 3> tables() { return {&t_thread, &t_radial, &t_mesh}; }
@@ -589,11 +604,14 @@ void mesh_variants(std::vector<const void*>& out) {
   out.push_back((const void*)mesh::k_mesh<double, false, WG, SW, TL>);
   out.push_back((const void*)mesh::k_mesh<float, true, WG, SW, TL>);
   out.push_back((const void*)mesh::k_mesh<double, true, WG, SW, TL>);
+  out.push_back((const void*)mesh::k_mesh<IoMapped<float>, false, WG, SW, TL>);   // (the affine I/O map: no parameter classes)
+  out.push_back((const void*)mesh::k_mesh<IoMapped<double>, false, WG, SW, TL>);
 }
 
 // the variant of k_mesh for a plan (mesh::Launch: WG, SW, TL) and for how the classes are bound
 template <class JT, bool WG, int SW = 2, bool TL = !WG>
-auto mesh_kernel(bool class_per_group) {
+auto mesh_kernel(bool class_per_group, bool mapped) {
+  if (mapped) return mesh::k_mesh<IoMapped<JT>, false, WG, SW, TL>;   // (anm_model_set_io_map refuses parameter classes)
   return class_per_group ? mesh::k_mesh<JT, true, WG, SW, TL> : mesh::k_mesh<JT, false, WG, SW, TL>;
 }
 
@@ -603,13 +621,13 @@ int launch_mesh(anm_model* m, int precision, int64_t n, hipStream_t s, const rad
   const int per_block = mesh::envs_per_block(d, L);
   const unsigned grid = unsigned((n + per_block - 1) / per_block), threads = unsigned(64 * L.waves);
   const ClassSel cs = class_sel(m, m->t_mesh);
-  const bool pg = cs.per_group != 0;
+  const bool pg = cs.per_group != 0, mp = io.mode != 0 && io.e.iomap != nullptr;
   return by_precision(precision, [&](auto jt) {
     using JT = decltype(jt);
-    auto kern = mesh::is_workgroup(d) ? mesh_kernel<JT, true>(pg)
-                : !L.tables_in_lds    ? mesh_kernel<JT, false, 2, false>(pg)
-                : L.simd_waves == 3   ? mesh_kernel<JT, false, 3>(pg)
-                                      : mesh_kernel<JT, false>(pg);
+    auto kern = mesh::is_workgroup(d) ? mesh_kernel<JT, true>(pg, mp)
+                : !L.tables_in_lds    ? mesh_kernel<JT, false, 2, false>(pg, mp)
+                : L.simd_waves == 3   ? mesh_kernel<JT, false, 3>(pg, mp)
+                                      : mesh_kernel<JT, false>(pg, mp);
     return launch("launch k_mesh", kern, grid, threads, L.lds, s, d, m->t_mesh.dev_int.get(), m->t_mesh.dev.get(), io, so, n, cs);
   });
 }
@@ -634,8 +652,10 @@ int launch_radial(anm_model* m, int precision, int64_t n, hipStream_t s, const r
   };
   return by_precision(precision, [&](auto jt) {
     using JT = decltype(jt);
+    const bool mp = io.mode != 0 && io.e.iomap != nullptr;   // the affine I/O map (it refuses parameter classes)
     if constexpr (Topo::TREE != 0)
-      if (spec) return cs.per_group ? go(radial::k_radial<JT, Topo, true>) : go(radial::k_radial<JT, Topo>);
+      if (spec) return mp ? go(radial::k_radial<IoMapped<JT>, Topo>) : cs.per_group ? go(radial::k_radial<JT, Topo, true>) : go(radial::k_radial<JT, Topo>);
+    if (mp) return go(radial::k_radial<IoMapped<JT>, void>);
     return cs.per_group ? go(radial::k_radial<JT, void, true>) : go(radial::k_radial<JT, void>);
   });
 }
@@ -833,6 +853,9 @@ int anm_model_full_layout(const anm_model* m, anm_full_layout* o) {
 
 int anm_model_set_env(anm_model* m, const anm_env_config* cfg) {
   if (!m || !cfg) return fail("anm_model_set_env: null argument");
+  if (m->d_iomap.get())
+    return fail("anm_model_set_env: an affine I/O map is set (anm_model_set_io_map), whose tables have the lengths of the task that was "
+                "set: clear it first (NULL) and set it again afterwards");
   // 1. whatever can refuse the task, 2. its device tables, in buffers of their own: the model is untouched so far
   Task t;
   if (int rc = check_task(m, *cfg, t)) return rc;
@@ -868,6 +891,7 @@ int anm_model_set_classes(anm_model* m, int32_t n_classes, const anm_network_des
   if (n_classes < 1 || n_classes > 65536) return fail("anm_model_set_classes: n_classes must be in [1, 65536]");
   if (n_classes > 1 && m->exo_mode != ANM_EXO_HOST) return fail("anm_model_set_classes: the uniform and series-noise exogenous modes do not take parameter classes");
   if (n_classes > 1 && m->io_mode == ANM_IO_F32) return fail("anm_model_set_classes: the float32 I/O mode (anm_model_set_io) does not take parameter classes");
+  if (n_classes > 1 && m->d_iomap.get()) return fail("anm_model_set_classes: the affine I/O map (anm_model_set_io_map) does not take parameter classes");
   if (n_classes > 1 && !descs) return fail("anm_model_set_classes: null descriptions");
   std::vector<std::vector<double>> xc, xh, xm;
   for (int k = 1; k < n_classes; ++k) {
@@ -934,6 +958,7 @@ int anm_model_bind_env_classes(anm_model* m, const int32_t* env_class, int64_t n
     return fail("anm_model_bind_env_classes: not while a batch view is bound (anm_model_bind_view)");
   if (m->exo_mode == ANM_EXO_SERIES_NOISE) return fail("anm_model_bind_env_classes: the series-noise mode does not take parameter classes");
   if (m->io_mode == ANM_IO_F32) return fail("anm_model_bind_env_classes: the float32 I/O mode (anm_model_set_io) does not take parameter classes");
+  if (m->d_iomap.get()) return fail("anm_model_bind_env_classes: the affine I/O map (anm_model_set_io_map) does not take parameter classes");
   if (num_envs <= 0) return fail("anm_model_bind_env_classes: num_envs must be positive");
   const int n_classes = m->n_classes();
   std::vector<int32_t> h(static_cast<size_t>(num_envs));
@@ -972,6 +997,8 @@ int anm_model_bind_state_same(anm_model* m, uint8_t* state_same) {
   if (state_same && m->has_view) return fail("anm_model_bind_state_same: not while a batch view is bound");
   if (state_same && m->io_mode == ANM_IO_F32)
     return fail("anm_model_bind_state_same: not in the float32 I/O mode (anm_model_set_io): the state row has no float64 twin in obs and is always written");
+  if (state_same && m->d_iomap.get())
+    return fail("anm_model_bind_state_same: not while an affine I/O map is set (anm_model_set_io_map): obs is no copy of the state row, which is always written");
   m->d_state_same = state_same;
   return 0;
 }
@@ -1002,6 +1029,53 @@ int anm_model_set_io(anm_model* m, int32_t io) {
   return 0;
 }
 
+int anm_model_set_io_map(anm_model* m, const anm_io_map* map) {
+  if (!m) return fail("anm_model_set_io_map: null model");
+  if (!map) {   // back to the plain arrays
+    m->d_iomap.reset();
+    return 0;
+  }
+  if (!m->env_set) return fail("anm_model_set_io_map: call anm_model_set_env first (and anm_model_set_obs, where a list is gathered in the kernel)");
+  if (m->has_view) return fail("anm_model_set_io_map: the affine I/O map does not go with a batch view (anm_model_bind_view)");
+  if (m->n_classes() > 1 || m->d_env_class)
+    return fail("anm_model_set_io_map: the affine I/O map does not take parameter classes (anm_model_set_classes / anm_model_bind_env_classes)");
+  if (m->d_state_same)
+    return fail("anm_model_set_io_map: the affine I/O map does not go with anm_model_bind_state_same (obs is no copy of the state row)");
+  const int n_act = (map->act_mid ? 1 : 0) + (map->act_half ? 1 : 0) + (map->act_low ? 1 : 0) + (map->act_high ? 1 : 0);
+  if (n_act != 0 && n_act != 4) return fail("anm_model_set_io_map: act_mid, act_half, act_low and act_high are all NULL (actions not mapped) or all set");
+  if ((map->obs_scale == nullptr) != (map->obs_bias == nullptr))
+    return fail("anm_model_set_io_map: obs_scale and obs_bias are both NULL (observations not mapped) or both set");
+  if (!(std::isfinite(map->reward_scale) && map->reward_scale > 0.0)) return fail("anm_model_set_io_map: reward_scale must be finite and > 0");
+  const int A = m->dims.action_dim, N = m->n_obs > 0 ? m->n_obs : m->dims.state_base_dim + m->K;
+  const double inf = std::numeric_limits<double>::infinity();
+  // a part that is not mapped gets the exact identity (IoMap, anm_env_ops.hpp): the kernels test one pointer, no table
+  std::vector<double> h(size_t(IoMap::obs(A)) + 2 * size_t(N));
+  h[IoMap::REWARD] = map->reward_scale;
+  for (int j = 0; j < A; ++j) {
+    double* a = &h[IoMap::ACT + j];
+    a[0] = -0.0; a[A] = 1.0; a[2 * A] = -inf; a[3 * A] = inf;
+    if (!n_act) continue;
+    const double mid = map->act_mid[j], half = map->act_half[j], lo = map->act_low[j], hi = map->act_high[j];
+    if (!(std::isfinite(half) && half > 0.0)) return fail("anm_model_set_io_map: act_half must be finite and > 0");
+    if (!std::isfinite(mid)) return fail("anm_model_set_io_map: act_mid must be finite");
+    if (!(lo <= hi)) return fail("anm_model_set_io_map: act_low > act_high (or NaN)");
+    a[0] = mid; a[A] = half; a[2 * A] = lo; a[3 * A] = hi;
+  }
+  for (int k = 0; k < N; ++k) {
+    double* o = &h[IoMap::obs(A) + k];
+    o[0] = 1.0; o[N] = -0.0;
+    if (!map->obs_scale) continue;
+    if (!(std::isfinite(map->obs_scale[k]) && map->obs_scale[k] > 0.0)) return fail("anm_model_set_io_map: obs_scale must be finite and > 0");
+    if (!std::isfinite(map->obs_bias[k])) return fail("anm_model_set_io_map: obs_bias must be finite");
+    o[0] = map->obs_scale[k]; o[N] = map->obs_bias[k];
+  }
+  DevBuf<double> d;   // (a refused or failed call leaves the map that is set as it was)
+  const hipError_t e = d.assign(h.data(), h.size());
+  if (e != hipSuccess) return fail_hip(e, "anm_model_set_io_map");
+  m->d_iomap = std::move(d);
+  return 0;
+}
+
 int anm_model_bind_view(anm_model* m, const anm_batch_view* v) {
   if (!m) return fail("anm_model_bind_view: null model");
   if (!v) {
@@ -1012,6 +1086,7 @@ int anm_model_bind_view(anm_model* m, const anm_batch_view* v) {
   if (m->d_env_class) return fail("anm_model_bind_view: not together with parameter classes (anm_model_bind_env_classes)");
   if (m->exo_mode == ANM_EXO_SERIES_NOISE) return fail("anm_model_bind_view: a batch view does not go with the series-noise mode");
   if (m->io_mode == ANM_IO_F32) return fail("anm_model_bind_view: a batch view does not go with the float32 I/O mode (anm_model_set_io)");
+  if (m->d_iomap.get()) return fail("anm_model_bind_view: a batch view does not go with the affine I/O map (anm_model_set_io_map)");
   if (m->n_obs > 0 && m->impl == ANM_IMPL_THREAD)
     return fail("anm_model_bind_view: the thread-per-environment family gathers no list-form observation through a view "
                 "(anm_model_set_obs): clear it, or move the model to a lane-group family first (anm_model_set_impl)");
@@ -1051,6 +1126,9 @@ int anm_model_obs_fusable(const anm_model* m) {
 int anm_model_set_obs(anm_model* m, int32_t n_obs, const int32_t* index, const double* scale, const double* low,
                       const double* high) {
   if (!m) return fail("anm_model_set_obs: null model");
+  if (m->d_iomap.get())
+    return fail("anm_model_set_obs: an affine I/O map is set (anm_model_set_io_map), whose observation tables have the length of the "
+                "observation that was set: clear it first (NULL) and set it again afterwards");
   if (n_obs <= 0) {   // back to the "state" observation
     m->d_obs_index.reset(); m->d_obs_tab.reset(); m->n_obs = 0;
     return 0;
@@ -1186,8 +1264,10 @@ static int env_io_of_model(const anm_model* m, const char* who, EnvIO& io) {
   io.period = m->period;
   io.ep = m->ep;
   io.io32 = m->io_mode == ANM_IO_F32 ? 1 : 0;
+  io.iomap = m->d_iomap.get();
   if (m->has_view) {
     const std::string w(who);
+    if (io.iomap) return fail((w + ": the affine I/O map (anm_model_set_io_map) does not go with a batch view (anm_model_bind_view)").c_str());
     if (io.io32) return fail((w + ": the float32 I/O mode (anm_model_set_io) does not go with a batch view (anm_model_bind_view)").c_str());
     if (io.ep.on) return fail((w + ": an episode time limit or episode buffers do not go with a batch view (anm_model_bind_view)").c_str());
   }
@@ -1213,6 +1293,9 @@ int anm_reset_f64(anm_model* m, int64_t n, const double* init_state, const uint8
     return fail("anm_reset_f64: correlated noise needs reset_count (the epoch keys the noise state every reset stores)");
   EnvIO io;
   if (int rc = env_io_of_model(m, "anm_reset_f64", io)) return rc;
+  // (a list-form observation is set: this launch writes the "state" form, whose rows are not the length of the map's tables --
+  // left raw, and the caller maps the list it gathers afterwards: io_affine.py, reset)
+  if (m->n_obs > 0) io.iomap = nullptr;
   io.init_state = init_state;
   io.rng_seed = rng_seed;
   io.env_offset = env_offset;
@@ -1308,6 +1391,9 @@ static int make_step_io(anm_model* m, const double* action, const double* exo, c
   if (io.io32 && full && m->n_obs == 0)
     return fail("anm_step_f64: the float32 I/O mode (anm_model_set_io) has no unfused observation gather: `full` + anm_gather_obs_f64 "
                 "writes float64 observations; set the list in the kernel (anm_model_set_obs) or leave `full` NULL");
+  if (io.iomap && full && m->n_obs == 0)
+    return fail("anm_step_f64: the affine I/O map (anm_model_set_io_map) has no unfused observation gather: `full` + anm_gather_obs_f64 "
+                "writes unmapped observations; set the list in the kernel (anm_model_set_obs) or leave `full` NULL");
   io.n_obs = 0;
   io.state_magic = magic_div(m->dims.state_base_dim + m->K);
   if (m->t_thread.ok && m->impl == ANM_IMPL_THREAD && (m->n_obs > 0 || full)) {
@@ -1382,6 +1468,10 @@ static int launch_step(anm_model* m, const EnvIO& io_in, int64_t n, const anm_so
   if (io.aux_index && io.exo == nullptr && io.exo_mode == ANM_EXO_HOST && io.K == 1 && !io.full && io.n_obs == 0) {
     // fast path: series mode, "state" observation, nothing but the batch tensors
     int rc = by_precision(prec, [&](auto jt) {
+      if (io.iomap) {
+        if (io.io32) return launch("launch k_step_rows_map", k_step_rows_map<decltype(jt), true>, grid, BLOCK, 0, s, C, io, so, n, cs);
+        return launch("launch k_step_rows_map", k_step_rows_map<decltype(jt), false>, grid, BLOCK, 0, s, C, io, so, n, cs);
+      }
       if (io.io32) {
         if (io.ep.on) return launch("launch k_step_rows_io32", k_step_rows_io32<decltype(jt), true>, grid, BLOCK, 0, s, C, io, so, n, cs);
         return launch("launch k_step_rows_io32", k_step_rows_io32<decltype(jt), false>, grid, BLOCK, 0, s, C, io, so, n, cs);

@@ -110,8 +110,11 @@ struct RowPtrs {
   double* state;
   double* obs;
   float* obs32 = nullptr;   // float32 I/O (EnvIO::io32): the obs row is this one, of floats
+  const double* map_scale = nullptr;   // affine I/O map (EnvIO::iomap): the stored entry is fma(v, scale[k], bias[k])
+  const double* map_bias = nullptr;
   ANM_HD void put_st(int k, double v) { state[k] = v; }
   ANM_HD void put_ob(int k, double v) {
+    if (map_scale) v = fma(v, map_scale[k], map_bias[k]);
     if (obs32) obs32[k] = float(v);
     else obs[k] = v;
   }
@@ -321,7 +324,41 @@ struct EnvIO {
   // expected forecast of the noisy time series (anm_env_config_forecast; null: off, wave-uniform): wherever a kernel writes
   // the state row and exo_z of an environment it writes the row of ExoForecastIO::out from what it wrote (ExoNoise::forecast_row)
   const ExoForecastIO* forecast;   // (device)
+  // affine policy I/O (anm_model_set_io_map; null: off, wave-uniform): ONE pointer to the block of IoMap below, in DEVICE memory
+  const double* iomap;
 };
+
+// Affine policy I/O (anm_model_set_io_map; gym_anm_amd/io_affine.py is the specification).  The kernel reads u where the plain
+// mode reads the action, steps with a = clamp(fma(half[j], u, mid[j]), lo[j], hi[j]) (select form: NaN passes), stores
+// fma(o, scale[k], bias[k]) where the plain mode stores the observation entry o and r * reward_scale where it stores the
+// reward r -- before the one float32 rounding of EnvIO::io32 -- and everything else as the plain mode fed `a` does.  The
+// block behind EnvIO::iomap: [reward_scale | mid, half, lo, hi: A each | scale, bias: N each], A = action_dim, N the entries
+// of an observation row.  The host fills the tables of a part that is not mapped with the exact identity (half 1, mid -0.0,
+// ends -inf / +inf; scale 1, bias -0.0; reward_scale 1): fma(1, u, -0.0) == u and u * 1 == u for every u, so ONE flag, the
+// pointer, switches the three maps and no kernel tests a table for null.
+struct IoMap {
+  static constexpr int REWARD = 0, ACT = 1;
+  static constexpr ANM_HD int obs(int A) { return 1 + 4 * A; }
+  // a of entry j from u; M: the block, A: action_dim
+  static ANM_HD double action(const double* M, int A, int j, double u) {
+    const double x = fma(M[ACT + A + j], u, M[ACT + j]);
+    const double lo = M[ACT + 2 * A + j], hi = M[ACT + 3 * A + j];
+    return x < lo ? lo : (x > hi ? hi : x);
+  }
+  // stored observation entry k of a row of N from o
+  static ANM_HD double observation(const double* M, int A, int N, int k, double o) { return fma(o, M[obs(A) + k], M[obs(A) + N + k]); }
+  static ANM_HD double reward(const double* M, double r) { return r * M[REWARD]; }
+};
+// The lane-group kernels take the map as a TAG on their solve-precision parameter -- k_radial<IoMapped<double>, ...> -- so
+// that the plain instantiations keep their names (tests/test_abi.py finds their register budgets by name) and their code
+template <class JT>
+struct IoMapped {};
+template <class JTM>
+struct IoMapTag { typedef JTM type; static constexpr bool map = false; };
+template <class JT>
+struct IoMapTag<IoMapped<JT>> { typedef JT type; static constexpr bool map = true; };
+// how a piece of code learns of the map: not at all, at compile time (the launch has it), or from EnvIO::iomap at run time
+constexpr int MAP_OFF = 0, MAP_ON = 1, MAP_RT = 2;
 
 // Float32 policy-facing I/O (ANM_IO_F32; gym_anm_amd/io_dtype.py is the specification): the arrays behind EnvIO::action,
 // obs and reward hold floats of the same shapes.  An action entry widens to double exactly; an observation entry or a
@@ -538,6 +575,10 @@ ANM_HD void reset_from(cptr_t C, const EnvIO& io, SolverOpts so, int64_t e, cons
                       io.exo_z + e * Dims<T>::NEXO);
   RowPtrs rows{io.state + e * S, io.obs + e * S};
   if (io.io32) rows.obs32 = reinterpret_cast<float*>(io.obs) + e * S;
+  if (io.iomap) {   // (no batch view in that mode: a row has T::SDIM + K entries)
+    rows.map_scale = io.iomap + IoMap::obs(Dims<T>::ADIM);
+    rows.map_bias = rows.map_scale + S;
+  }
   finish_reset<T, Layout<T>::KMAX, S0>(C, w, s0, io.K, io.soc + e * WD, rows);
   // expected forecast: from the table index the row just got and the noise states this reset stored (or found)
   if (io.forecast) store_exo_forecast<Dims<T>::NEXO>(io, e, int(s0[T::SDIM]));
@@ -789,8 +830,10 @@ ANM_HD void step_compute(cptr_t C, const EnvIO& io, SolverOpts so, int64_t e, co
 // EP: the caller serves the episode time limit and statistics (io.ep, a wave-uniform runtime switch); off, they are not in
 // the code at all (the fast path of the step keeps its instruction stream: k_step_rows / k_step_rows_ep)
 // IOM: the float32 I/O of the reward (IO_F64 | IO_F32 | IO_RT); the statistics above accumulate the double either way
+// MAPM: the affine map of the stored reward (MAP_OFF | MAP_ON | MAP_RT; EnvIO::iomap): r * reward_scale, one rounding,
+// then IOM's; the statistics accumulate the raw double
 // have_ts: the caller already read timestep[e]; w_des: row stride of soc (a batch view pads the rows)
-template <class T, int KCAP, bool EP = false, int IOM = IO_F64>
+template <class T, int KCAP, bool EP = false, int IOM = IO_F64, int MAPM = MAP_OFF>
 ANM_HD void store_step_scalars(const EnvIO& io, int64_t e, const StepFlags<T>& o, bool have_ts = false, int32_t ts_prev = 0,
                                int w_des = T::NDES) {
   if constexpr (EP) {
@@ -801,8 +844,15 @@ ANM_HD void store_step_scalars(const EnvIO& io, int64_t e, const StepFlags<T>& o
   }
   if (o.write_soc) static_for<0, T::NDES>([&](auto I) { io.soc[e * w_des + I] = o.soc[I]; });
   if (o.terminated >= 0) io.terminated[e] = uint8_t(o.terminated);
-  if constexpr (IOM == IO_F64) io.reward[e] = o.reward;
-  else io_store(io.reward, e, o.reward, IOM == IO_F32 || io.io32 != 0);
+  if constexpr (MAPM == MAP_OFF) {
+    if constexpr (IOM == IO_F64) io.reward[e] = o.reward;
+    else io_store(io.reward, e, o.reward, IOM == IO_F32 || io.io32 != 0);
+  } else {
+    double r = o.reward;
+    if (MAPM == MAP_ON || io.iomap) r = IoMap::reward(io.iomap, r);
+    if constexpr (IOM == IO_F64) io.reward[e] = r;
+    else io_store(io.reward, e, r, IOM == IO_F32 || io.io32 != 0);
+  }
   if (o.write_costs) {
     io.e_loss[e] = o.e_loss;
     io.penalty[e] = o.penalty;
@@ -910,7 +960,9 @@ __device__ int64_t load_record(const double* r, StepCtx<T>& ctx, EnvWork<T>& w, 
 
 // IO32: float32 I/O of the obs rows and the reward (k_step_rows_io32 / _ep): the obs block leaves as 64 x S floats, whole-wave
 // 256-byte transactions with the same tail handling; the state rows are always written (no state_same in that mode)
-template <class T, bool FULL, bool EP = false, bool IO32 = false>
+// MAP: the affine I/O map (k_step_rows_map; EnvIO::iomap): the obs rows are mapped in registers before they go through LDS
+// (constant table offsets: wave-uniform scalar loads), the reward where it is stored; the state rows are always written
+template <class T, bool FULL, bool EP = false, bool IO32 = false, bool MAP = false>
 __device__ __forceinline__ void epilogue_stores(const EnvIO& io, int64_t e0, int64_t e, int lane, bool store, int32_t ts_prev,
                                                 StepOut<T, 1>& out, const EnvWork<T>& w, double* lds) {
   constexpr int S = T::SDIM + 1;
@@ -923,7 +975,7 @@ __device__ __forceinline__ void epilogue_stores(const EnvIO& io, int64_t e0, int
     state_dup = same;
   }
   if (store) {
-    store_step_scalars<T, 1, EP, IO32 ? IO_F32 : IO_F64>(io, e, out, true, ts_prev);
+    store_step_scalars<T, 1, EP, IO32 ? IO_F32 : IO_F64, MAP ? MAP_ON : MAP_OFF>(io, e, out, true, ts_prev);
     if (io.state_same && out.write_state) io.state_same[e] = state_dup ? 1 : 0;
     if (out.write_state) io.aux_index[e] = int32_t(out.state[T::SDIM]);
     if constexpr (FULL) {
@@ -961,6 +1013,8 @@ __device__ __forceinline__ void epilogue_stores(const EnvIO& io, int64_t e0, int
     ANM_WAVE_SYNC();
   };
   store_rows(io.state + e0 * S, out.state, out.write_state && !state_dup);
+  if constexpr (MAP)
+    static_for<0, S>([&](auto Kc) { out.obs[Kc] = IoMap::observation(io.iomap, Dims<T>::ADIM, S, Kc, out.obs[Kc]); });
   if constexpr (IO32) store_rows(reinterpret_cast<float*>(io.obs) + e0 * S, out.obs, out.write_obs);
   else store_rows(io.obs + e0 * S, out.obs, out.write_obs);
   ANM_PHASE(6);
@@ -1027,7 +1081,9 @@ __device__ void op_step_view(cptr_t C, const EnvIO& io, SolverOpts so, int64_t n
 // IO32: float32 I/O (k_step_rows_io32 / _ep, anm_model_set_io): the 64 x ADIM actions arrive as floats, 256 bytes per wave
 // transaction, and widen on their way into LDS; obs and reward leave as floats (epilogue_stores).  Compile-time, like EP:
 // the float64 kernels carry none of it
-template <class T, class JT, bool FULL, bool EP = false, bool IO32 = false>
+// MAP: the affine I/O map (k_step_rows_map, anm_model_set_io_map): the action entries are mapped as they come out of the LDS
+// transpose, obs and reward as they leave (epilogue_stores).  Compile-time as well: the plain kernels carry none of it
+template <class T, class JT, bool FULL, bool EP = false, bool IO32 = false, bool MAP = false>
 __device__ void op_step_rows(cptr_t C, const EnvIO& io, SolverOpts so, int64_t n, double* lds) {
   typedef Dims<T> D;
   constexpr int S = T::SDIM + 1;
@@ -1076,6 +1132,7 @@ __device__ void op_step_rows(cptr_t C, const EnvIO& io, SolverOpts so, int64_t n
     ANM_WAVE_SYNC();
     const int lr = valid ? lane : rows - 1;
     static_for<0, D::ADIM>([&](auto I) { in.action[I] = lds[lr * AP + I]; });
+    if constexpr (MAP) static_for<0, D::ADIM>([&](auto I) { in.action[I] = IoMap::action(io.iomap, D::ADIM, I, in.action[I]); });
     ANM_WAVE_SYNC();
   }
   {
@@ -1133,7 +1190,7 @@ __device__ void op_step_rows(cptr_t C, const EnvIO& io, SolverOpts so, int64_t n
   }
   step_end<T, 1>(C, io, so, ec, ctx, w, st, out);
   const bool store = valid && !pending;
-  epilogue_stores<T, FULL, EP, IO32>(io, e0, e, lane, store, ts_prev, out, w, lds);
+  epilogue_stores<T, FULL, EP, IO32, MAP>(io, e0, e, lane, store, ts_prev, out, w, lds);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1212,6 +1269,8 @@ __device__ void op_step_general(cptr_t C, const EnvIO& io, SolverOpts so, int64_
     ANM_WAVE_SYNC();
     const int lr = valid ? lane : rows - 1;
     static_for<0, D::ADIM>([&](auto I) { in.action[I] = ldsB[lr * AP + I]; });
+    // (affine I/O map, io.iomap: wave-uniform, like f32)
+    if (io.iomap) static_for<0, D::ADIM>([&](auto I) { in.action[I] = IoMap::action(io.iomap, D::ADIM, I, in.action[I]); });
     ANM_WAVE_SYNC();
   }
   in.was_term = io.terminated[ec] != 0;
@@ -1270,7 +1329,7 @@ __device__ void op_step_general(cptr_t C, const EnvIO& io, SolverOpts so, int64_
   step_end<T, KM, false, RowOut>(C, io, so, ec, ctx, w, st, out);
   const bool store = valid;
   if (store) {
-    store_step_scalars<T, KM, true, IO_RT>(io, e, out, true, ts_prev);
+    store_step_scalars<T, KM, true, IO_RT, MAP_RT>(io, e, out, true, ts_prev);
     if (io.aux_index && out.write_state) io.aux_index[e] = int32_t(out.row[T::SDIM]);
     // expected forecast: wherever the state row is written, from its table index (0 in a zero row) and the lane's own
     // row of exo_z as the draw site stored it
@@ -1296,7 +1355,9 @@ __device__ void op_step_general(cptr_t C, const EnvIO& io, SolverOpts so, int64_
           const int k = idx - r * io.n_obs;
           const double v = ldsA[r * RS + io.obs_index[k]] * io.obs_scale[k];
           const double c = fmin(fmax(v, io.obs_lo[k]), io.obs_hi[k]);
-          if ((obs_rows >> r) & 1ull) io_store(io.obs, gobs0 + idx, ((zero_rows >> r) & 1ull) ? 0.0 : c, f32);
+          double o = ((zero_rows >> r) & 1ull) ? 0.0 : c;
+          if (io.iomap) o = IoMap::observation(io.iomap, D::ADIM, io.n_obs, k, o);
+          if ((obs_rows >> r) & 1ull) io_store(io.obs, gobs0 + idx, o, f32);
         }
       }
       if (io.full) {
@@ -1326,7 +1387,9 @@ __device__ void op_step_general(cptr_t C, const EnvIO& io, SolverOpts so, int64_
       if ((state_rows >> r) & 1ull) gstate[idx] = v;
       if (!list && ((obs_rows >> r) & 1ull)) {
         const double c = fmin(fmax(v, C[L::OBS_LO + k]), C[L::OBS_HI + k]);
-        io_store(io.obs, gobs0 + idx, ((zero_rows >> r) & 1ull) ? 0.0 : c, f32);
+        double o = ((zero_rows >> r) & 1ull) ? 0.0 : c;
+        if (io.iomap) o = IoMap::observation(io.iomap, D::ADIM, S, k, o);
+        io_store(io.obs, gobs0 + idx, o, f32);
       }
     }
   }
@@ -1446,7 +1509,7 @@ __device__ void op_step_scatter(const EnvIO& io) {
     out.reward = r[Q::REWARD]; out.e_loss = r[Q::ELOSS]; out.penalty = r[Q::PENALTY];
     out.n_iter = int(r[Q::NITER]); out.terminated = int(r[Q::TERM]); out.timestep_op = int(r[Q::TSOP]);
     static_for<0, T::NDES>([&](auto I) { out.soc[I] = r[Q::SOC + I]; });
-    store_step_scalars<T, 1, true, IO_RT>(io, e, out);   // (reads timestep[e] itself: the first launch stored nothing for e)
+    store_step_scalars<T, 1, true, IO_RT, MAP_RT>(io, e, out);   // (reads timestep[e] itself: the first launch stored nothing for e)
     if (flags & 1) {
       if (io.state_same) io.state_same[e] = 0;
       io.aux_index[e] = int32_t(r[Q::STATE + T::SDIM]);
@@ -1455,7 +1518,10 @@ __device__ void op_step_scatter(const EnvIO& io) {
   if (flags & 1)
     for (int k = l; k < S; k += SCATTER_LANES) io.state[e * S + k] = r[Q::STATE + k];
   if (flags & 2)
-    for (int k = l; k < S; k += SCATTER_LANES) io_store(io.obs, e * S + k, r[Q::OBS + k], io.io32 != 0);
+    for (int k = l; k < S; k += SCATTER_LANES) {   // (the record holds the raw row: the affine I/O map is applied here)
+      const double o = io.iomap ? IoMap::observation(io.iomap, Dims<T>::ADIM, S, k, r[Q::OBS + k]) : r[Q::OBS + k];
+      io_store(io.obs, e * S + k, o, io.io32 != 0);
+    }
 }
 #endif
 

@@ -21,7 +21,11 @@
 //   3  declares state, list, ON, OW and the sinks put_obs / put_reward / put; inside a generic lambda whose
 //      `constexpr bool f32` chooses float32 or float64 obs rows and reward (EnvIO::io32, a wave-uniform flag; the float64
 //      values rounded once as they are stored: ONE branch chooses between the two instantiations, nothing of it is inside
-//      the Newton trips, and the float64 path is the code it was without the mode).
+//      the Newton trips, and the float64 path is the code it was without the mode).  MAP, the kernel's template flag: the
+//      affine I/O map (EnvIO::iomap, never null there; io_affine.py) -- ONE instance of the output section, which maps what
+//      it stores and takes the number format at run time.  A kernel instantiation of its own, not a third arm: with the arm
+//      in it, k_radial<double, Topo> took 169 VGPRs instead of 168 -- two wavefronts per SIMD instead of three -- for every
+//      task (profiles/io_map_kernels.txt); the plain instantiations are the code they were.
 //   4  the skeleton of modes 1 and 2, after part 3 and inside a do { } while (false).  Needs dev_p, dev_q, p_pot and what
 //      part 2 needs; writes `soc` on a reset (the requested one, which the kernel's dump and list observation then show)
 //      and sets `dump`.  ANM_LIST_OBS_DUE(zero) is the kernel's: a list observation is due -- zeros (terminal / absorbing:
@@ -170,6 +174,18 @@
         in_q = a[2 * d.NGEN + d.NDES + slot];
         soc = io.e.soc[ee * W_DES + slot];
       }
+      // (affine I/O map, the kernel's MAP instantiation: what was read is u, the set-points are a = clamp(fma(half, u, mid))
+      // -- IoMap::action; behind the reads, which are the code they were)
+      if constexpr (MAP) {
+        const int A = 2 * (d.NGEN + d.NDES);
+        if (typ == DEV_CLASSICAL || typ == DEV_RENEWABLE) {
+          in_p = IoMap::action(io.e.iomap, A, slot, in_p);
+          in_q = IoMap::action(io.e.iomap, A, d.NGEN + slot, in_q);
+        } else if (typ == DEV_STORAGE) {
+          in_p = IoMap::action(io.e.iomap, A, 2 * d.NGEN + slot, in_p);
+          in_q = IoMap::action(io.e.iomap, A, 2 * d.NGEN + d.NDES + slot, in_q);
+        }
+      }
     }
   }
 #elif ANM_LANE_IO_PART == 2   // ---- mode 0: what Simulator.transition returns beside the dump
@@ -194,11 +210,13 @@
   double* obs = io.e.obs + e * OW;
   float* obs32 = reinterpret_cast<float*>(io.e.obs) + e * OW;
   auto put_obs = [&](int k, double v) {
-    if constexpr (f32) obs32[k] = float(v);
+    if constexpr (MAP) io_store(io.e.obs, e * OW + k, IoMap::observation(io.e.iomap, 2 * (d.NGEN + d.NDES), ON, k, v), io.e.io32 != 0);
+    else if constexpr (f32) obs32[k] = float(v);
     else obs[k] = v;
   };
   auto put_reward = [&](double v) {
-    if constexpr (f32) reinterpret_cast<float*>(io.e.reward)[e] = float(v);
+    if constexpr (MAP) io_store(io.e.reward, e, IoMap::reward(io.e.iomap, v), io.e.io32 != 0);
+    else if constexpr (f32) reinterpret_cast<float*>(io.e.reward)[e] = float(v);
     else io.e.reward[e] = v;
   };
   cptr_t lo = C + d.off_obs_lo, hi = C + d.off_obs_hi;

@@ -677,7 +677,9 @@ inline bool build_plan(const anm_network_desc& n, Plan& P, std::string& err) {
 
 // PG: see k_radial; WG: the environment is the workgroup; SW: wavefronts per SIMD the registers are budgeted for; TL: the tables
 // are staged in LDS (Launch)
-template <class JT, bool PG = false, bool WG = false, int SW = 2, bool TL = !WG>
+// JTM: the solve precision JT (float | double) or IoMapped<JT> -- MAP: the launch goes through the affine I/O map (io.e.iomap
+// set; anm_lane_io.inc parts 1 and 3): instantiations of their own, so that the others carry none of it
+template <class JTM, bool PG = false, bool WG = false, int SW = 2, bool TL = !WG>
 #ifndef ANM_MESH_MINWAVES2
 // The waves-per-SIMD hint of the SW = 2 variants: none (1).  Round 6 traced most of the 522 -> 546 us of the meshed 30-bus batch
 // between rounds 4 and 5 to `__launch_bounds__(256, 2)` (round 4 compiled without a hint): the same 192 registers either way,
@@ -692,6 +694,8 @@ template <class JT, bool PG = false, bool WG = false, int SW = 2, bool TL = !WG>
 #endif
 __global__ __launch_bounds__(WG ? 512 : 256, SW == 2 ? ANM_MESH_MINWAVES2 : SW) void k_mesh(Dims d, const int* __restrict__ ri, const double* __restrict__ rd0,
                                                               radial::IO io, SolverOpts so, int64_t n_env, ClassSel cls) {
+  typedef typename IoMapTag<JTM>::type JT;
+  constexpr bool MAP = IoMapTag<JTM>::map;
   // a workgroup = 1, 2 or 4 wavefronts that share one LDS copy of the tables and otherwise never meet: a lane
   // group lies within one wavefront, whose LDS operations complete in program order (fences only).
   // WG: the workgroup (2 ... 8 wavefronts) is ONE environment; every place where lanes of an environment hand
@@ -1274,7 +1278,8 @@ __global__ __launch_bounds__(WG ? 512 : 256, SW == 2 ? ANM_MESH_MINWAVES2 : SW) 
   // (lo_mode and dump are uniform over the lanes of an environment: list_obs synchronises them)
   if (list && lo_mode != 0) list_obs(lo_mode == 1);
   };
-  if (io.e.io32) outputs(std::true_type{});
+  if constexpr (MAP) outputs(std::false_type{});   // (the affine I/O map: one instance, the number format at run time)
+  else if (io.e.io32) outputs(std::true_type{});
   else outputs(std::false_type{});
   if (dump) write_full();
 #define ANM_LANE_IO_PART 5

@@ -246,9 +246,13 @@ enum { A_VR = 0, A_VI, A_UPR, A_UPI, A_S0, A_S1, A_N = 10 };  // LDS of a wavefr
 // of the table-driven one below; void: any radial network (generic mode).
 // PG: the parameter class is that of the lane group's own environment (any assignment of classes to environments;
 // the constants are then read by vector loads) instead of one class per wavefront (scalar loads).
-template <class JT, class TT, bool PG = false>
+// JTM: the solve precision JT (float | double) or IoMapped<JT> -- MAP: the launch goes through the affine I/O map (io.e.iomap
+// set; anm_lane_io.inc parts 1 and 3): instantiations of their own, so that the others carry none of it
+template <class JTM, class TT, bool PG = false>
 __global__ __launch_bounds__(64, ANM_RADIAL_WAVES) void k_radial(Dims d, const int* __restrict__ ri, const double* __restrict__ rd0, IO io,
                                               SolverOpts so, int64_t n_env, ClassSel cls) {
+  typedef typename IoMapTag<JTM>::type JT;
+  constexpr bool MAP = IoMapTag<JTM>::map;
   constexpr bool USE_T = !std::is_void<TT>::value;
   // parameter class of this wavefront's environments (uniform over aligned blocks of 64 environments), or, PG, of
   // this lane group's environment
@@ -702,7 +706,8 @@ __global__ __launch_bounds__(64, ANM_RADIAL_WAVES) void k_radial(Dims d, const i
 #undef ANM_LIST_OBS_DUE
   } while (false);
   };
-  if (io.e.io32) outputs(std::true_type{});
+  if constexpr (MAP) outputs(std::false_type{});   // (the affine I/O map: one instance, the number format at run time)
+  else if (io.e.io32) outputs(std::true_type{});
   else outputs(std::false_type{});
   } while (false);
   if (dump) write_full();

@@ -21,7 +21,8 @@ zero state with reward 0 (anm_env.py:365-367) until it is reset -- explicitly th
 
 Every tensor is float64 unless ``io_dtype=torch.float32``: then the kernels read float32 actions and write float32
 observations and rewards (the float64 values rounded once), the spaces are float32 ``Box``es and everything else stays
-float64 (gym_anm_amd/io_dtype.py).
+float64 (gym_anm_amd/io_dtype.py).  ``action_map=`` / ``obs_map=`` / ``reward_scale=`` put fixed affine maps on the same three
+arrays, inside the kernels: unit actions in, scaled observations and rewards out (gym_anm_amd/io_affine.py).
 """
 
 from __future__ import annotations
@@ -35,6 +36,7 @@ import torch
 from .. import _lib
 from .. import episode as _episode
 from .. import errors as E
+from .. import io_affine as _aff
 from .. import io_dtype as _io
 from .. import rng as _rng
 from ..model import STATE_VARIABLES
@@ -99,8 +101,12 @@ class BatchedANMEnv(GymEnv):
                  env_offset=0, impl=None, straggler_after="auto", straggler_mid="auto", handoff_after="auto", row_continuation=0, track_full=False,
                  fuse_observation=True, variants=None, env_variant=None, exogenous=None, exo_low=None, exo_high=None, exo_noise=None,
                  exo_corr=None, forecast_horizon=None,
-                 max_episode_steps=None, episode_stats=False, io_dtype=None, _backend=None):  # fmt: skip
+                 max_episode_steps=None, episode_stats=False, io_dtype=None, action_map=None, obs_map=None, reward_scale=None,
+                 _backend=None):  # fmt: skip
         GymEnv.reset(self, seed=seed)
+        # affine policy I/O inside the kernels (gym_anm_amd/io_affine.py has the semantics): checked before anything is built
+        self._check_io_map_args(action_map, obs_map, reward_scale, observation, fuse_observation, track_full,
+                                variants is not None or env_variant is not None)
         self.K, self.gamma, self.lamb, self.delta_t = K, gamma, lamb, delta_t
         self.aux_bounds = aux_bounds
         if costs_clipping is None:
@@ -139,6 +145,11 @@ class BatchedANMEnv(GymEnv):
             raise E.EnvInitializationError("io_dtype=torch.float32 needs the GPU library: this backend reads and writes "
                                            "float64 arrays alone")
 
+        if self._mapped and sim.backend.device_type != "cuda":
+            # (a backend that ignores the maps would step with the unit actions as MW without saying so)
+            raise E.EnvInitializationError("action_map / obs_map / reward_scale need the GPU library: this backend maps nothing "
+                                           "in its kernels")
+
         self.state_values = self._expand_all_ids(
             [("dev_p", "all", "MW"), ("dev_q", "all", "MVAr"), ("des_soc", "all", "MWh"), ("gen_p_max", "all", "MW"),
              ("aux", "all", None)]
@@ -148,6 +159,14 @@ class BatchedANMEnv(GymEnv):
         if self._io32:  # bounds rounded inward: every float32 point of the Box lies in the reference's float64 Box
             lo, hi = _io.action_bounds32(lo, hi)
         self.action_space = Box(low=lo, high=hi, dtype=np.float32 if self._io32 else np.float64)
+        self.raw_action_space = self.action_space   # MW / MVAr: what the kernels step with, whatever the policy sends
+        if self._action_map_arg is not None:
+            # the policy sends u in [-1, 1]; the kernels step with clamp(fma(half, u, mid)) inside the float64 Box
+            lo64, hi64 = (np.asarray(x, dtype=np.float64) for x in sim.model.action_bounds())
+            mid, half = _aff.unit_action_map(lo64, hi64) if isinstance(self._action_map_arg, str) else self._action_map_arg
+            self._map_act = _aff.check_action_map(mid, half, lo64, hi64)
+            lo, hi = -np.ones(len(lo64)), np.ones(len(lo64))
+            self.action_space = Box(low=lo, high=hi, dtype=np.float32 if self._io32 else np.float64)
         self.single_action_space = self.action_space
 
         self.obs_values = self._build_observation_space(observation)
@@ -156,6 +175,11 @@ class BatchedANMEnv(GymEnv):
         self._obs_space64 = self.observation_space
         if self.observation_space is not None:
             self.observation_N = self.observation_space.shape[0]
+            if self._obs_map_arg is not None:   # the Box of images: the map is monotone (io_affine.py rule 5)
+                lo64, hi64 = np.asarray(self._obs_space64.low, float), np.asarray(self._obs_space64.high, float)
+                sc, bi = _aff.box_obs_map(lo64, hi64) if isinstance(self._obs_map_arg, str) else self._obs_map_arg
+                self._map_obs = _aff.check_obs_map(sc, bi, self.observation_N)
+                self.observation_space = Box(*_aff.observation_image(lo64, hi64, *self._map_obs), dtype=np.float64)
             if self._io32:
                 lo32, hi32 = _io.observation_bounds32(self.observation_space.low, self.observation_space.high)
                 self.observation_space = Box(low=lo32, high=hi32, dtype=np.float32)
@@ -176,7 +200,74 @@ class BatchedANMEnv(GymEnv):
         self._obs_is_state = self.obs_values is not None and self.obs_values == self.state_values
         self._set_task()
         self._set_observation_gather(fuse_observation)
+        self._set_io_map()
         self._plan_step_path(track_full, straggler_after, straggler_mid, max_iter)
+
+    def _check_io_map_args(self, action_map, obs_map, reward_scale, observation, fuse_observation, track_full, has_classes):
+        """action_map=None | "unit" | (mid, half); obs_map=None | "box" | (scale, bias); reward_scale=None | a finite number
+        > 0: fixed affine maps applied INSIDE the step and reset kernels (gym_anm_amd/io_affine.py).  The policy sends u, the
+        kernels step with a = clamp(fma(half, u, mid)) inside the action Box ("unit": [-1, 1] onto the Box); they store
+        fma(o, scale, bias) for every observation entry o ("box": every column with finite ends onto about [-1, 1]) and
+        reward * reward_scale.  Everything else -- state, costs, episode statistics, exo_forecast (MW) -- stays raw.  With all
+        three None nothing changes.  What the mode does not serve is refused here, by the name of the argument."""
+        for name, val, word in (("action_map", action_map, "unit"), ("obs_map", obs_map, "box")):
+            if val is None or (isinstance(val, str) and val == word):
+                continue
+            if isinstance(val, str) or not isinstance(val, (tuple, list)) or len(val) != 2:
+                raise E.ArgsError("The argument %s is %r but should be None, %r or a pair of vectors." % (name, val, word))
+        self._action_map_arg = None if action_map is None else action_map if isinstance(action_map, str) else tuple(action_map)
+        self._obs_map_arg = None if obs_map is None else obs_map if isinstance(obs_map, str) else tuple(obs_map)
+        self.reward_scale = None if reward_scale is None else _aff.check_reward_scale(reward_scale)
+        self._map_act = self._map_obs = None   # the resolved host tables: (mid, half, low, high), (scale, bias)
+        self._mapped = action_map is not None or obs_map is not None or reward_scale is not None
+        if not self._mapped:
+            return
+        which = "/".join(n for n, v in (("action_map", action_map), ("obs_map", obs_map), ("reward_scale", reward_scale)) if v is not None)
+        if has_classes:
+            raise E.EnvInitializationError("%s does not take parameter classes (variants=)" % which)
+        if callable(observation):
+            raise E.EnvInitializationError("%s does not go with a callable observation: the kernels map what they write, and a "
+                                           "callable observation is computed outside them" % which)
+        if isinstance(observation, list) and not fuse_observation:
+            raise E.EnvInitializationError("%s needs the list-form observation gathered inside the step kernel: "
+                                           "fuse_observation=False leaves it to anm_gather_obs_f64, which maps nothing" % which)
+        if track_full and not isinstance(observation, list):
+            raise E.EnvInitializationError("%s takes track_full=True only next to a list-form observation gathered inside the "
+                                           "step kernel" % which)
+
+    @property
+    def io_map(self):
+        """The host tables of the affine I/O maps in use (float64 arrays; io_affine.py), or None without the mode: a dict with
+        ``action`` = (mid, half, low, high) or None, ``obs`` = (scale, bias) or None, ``reward_scale`` (1.0 when not given)."""
+        if not self._mapped:
+            return None
+        return dict(action=self._map_act, obs=self._map_obs, reward_scale=1.0 if self.reward_scale is None else self.reward_scale)
+
+    def encode_action(self, a_mw):
+        """The u to send for an action in MW / MVAr (an ``MPCAgent``'s): ``(a_mw - mid) / half``; the action itself without
+        ``action_map``.  Not bit-exact under the kernels' decode (io_affine.encode_action)."""
+        if self._map_act is None:
+            return a_mw
+        return _aff.encode_action(a_mw, self._map_act[0], self._map_act[1])
+
+    def _set_io_map(self):
+        """Hand the maps to the library (anm_model_set_io_map): after the task and the observation list, whose lengths its
+        tables have."""
+        if not self._mapped:
+            return
+        sim = self.simulator
+        if self._gather is not None and not self._obs_fused:
+            raise E.EnvInitializationError("action_map / obs_map / reward_scale need the list-form observation gathered inside "
+                                           "the step kernel: this model cannot gather in its kernel")
+        m = _lib.IoMap(reward_scale=1.0 if self.reward_scale is None else self.reward_scale)
+        keep = []
+        for names, tabs in ((("act_mid", "act_half", "act_low", "act_high"), self._map_act), (("obs_scale", "obs_bias"), self._map_obs)):
+            for name, tab in zip(names, tabs or ()):
+                arr, ptr = _lib.as_c(tab, np.float64)
+                keep.append(arr)
+                setattr(m, name, ptr)
+        with sim._device_ctx():
+            sim.backend.check(sim.backend.lib.anm_model_set_io_map(sim._handle, C.byref(m)), "anm_model_set_io_map")
 
     def _alloc_buffers(self):
         """Device-resident per-environment state, and the episode buffers the step kernels keep."""
@@ -424,6 +515,9 @@ class BatchedANMEnv(GymEnv):
         # track_full: also dump the electrical state of every step, so that simulator.state /
         # simulator.pfe_converged follow the environment like the reference's (simulator.py:529-537)
         self.track_full = bool(track_full)
+        if self._mapped and self.track_full and not self._obs_fused:
+            raise E.EnvInitializationError("action_map / obs_map / reward_scale take track_full=True only next to a list-form "
+                                           "observation gathered inside the step kernel")
         if self._io32 and self.track_full and not self._obs_fused:
             raise E.EnvInitializationError("io_dtype=torch.float32 takes track_full=True only next to a list-form observation "
                                            "gathered inside the step kernel")
@@ -441,8 +535,9 @@ class BatchedANMEnv(GymEnv):
         self._aux_index_ptr = None if self._aux_index is None else self._aux_index.data_ptr()
         # "state" observation on the fast path: obs = clip(state) is the state itself unless a bound bites, so
         # the kernel writes the state row only then and flags the rest (anm_model_bind_state_same)
-        # (float32 mode: the state row has no float64 twin in obs and is always written)
-        if self._aux_index is not None and self._obs_is_state and sim.backend.device_type == "cuda" and not self._io32:
+        # (float32 mode: the state row has no float64 twin in obs and is always written; the affine I/O map: likewise)
+        if self._aux_index is not None and self._obs_is_state and sim.backend.device_type == "cuda" and not self._io32 \
+                and not self._mapped:
             self._state_same = torch.zeros(self.num_envs, dtype=torch.uint8, device=self.device)
             with sim._device_ctx():
                 sim.backend.check(sim.backend.lib.anm_model_bind_state_same(sim._handle, self._state_same.data_ptr()),
@@ -592,7 +687,12 @@ class BatchedANMEnv(GymEnv):
 
     # ---- observation ---------------------------------------------------------------------------------------
     def observation(self, s_t):
-        """``o_t = observation(s_t)``: clip(state variables, Box) (anm_env.py:313-331), batched."""
+        """``o_t = observation(s_t)``: clip(state variables, Box) (anm_env.py:313-331), batched.
+
+        With ``obs_map`` and a list-form observation (``reset()`` only; ``step()`` gets the mapped list from its kernel) the
+        gathered rows of ALL environments go to the host, through ``io_affine.map_obs`` and back: the call synchronises and
+        copies ``num_envs x n_obs`` doubles each way, masked resets included.  A training loop that resets often should use
+        ``autoreset=True``, whose rows the step kernel maps itself."""
         if self._obs_is_state:
             return self._state_obs
         sim = self.simulator
@@ -601,7 +701,8 @@ class BatchedANMEnv(GymEnv):
         if self._obs_buf is None:
             self._obs_buf = torch.zeros((self.num_envs, n_obs), dtype=torch.float64, device=self.device)
         out = self._obs_buf
-        if self._io32:   # (reset() only: gathered in float64, cast once -- io_dtype.py rule 5)
+        remap = self._map_obs is not None   # (reset() only: gathered raw, mapped on the host -- io_affine.py rule 6)
+        if self._io32 or remap:   # (reset() only: gathered in float64, cast once -- io_dtype.py rule 5)
             if self._obs_gather64 is None:
                 self._obs_gather64 = torch.zeros((self.num_envs, n_obs), dtype=torch.float64, device=self.device)
             out = self._obs_gather64
@@ -612,6 +713,8 @@ class BatchedANMEnv(GymEnv):
                 low.data_ptr(), high.data_ptr(), out.data_ptr(), _stream_ptr(self.device),
             )  # fmt: skip
         sim.backend.check(rc, "anm_gather_obs_f64")
+        if remap:   # exactly the kernels' fma, evaluated on the host (rng.fma_v): reset() is not the hot path
+            out = torch.as_tensor(_aff.map_obs(out.cpu().numpy(), *self._map_obs), dtype=torch.float64, device=self.device)
         if out is not self._obs_buf:
             self._obs_buf.copy_(out)
         return self._obs_buf

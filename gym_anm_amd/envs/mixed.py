@@ -98,6 +98,9 @@ class _Task(BatchedANMEnv):
         if spec.get("forecast_horizon") is not None:
             raise E.EnvInitializationError("MixedBatchedANMEnv writes no expected forecast (forecast_horizon= belongs to "
                                            "exogenous='series_noise', which batch views do not take): use BatchedANMEnv")
+        if any(spec.get(k) is not None for k in ("action_map", "obs_map", "reward_scale")):
+            raise E.EnvInitializationError("MixedBatchedANMEnv steps through batch views, which take no affine I/O map "
+                                           "(action_map / obs_map / reward_scale): use BatchedANMEnv")
         self.hooked = spec.get("series") is None
         dt, lamb = spec.get("delta_t", 0.25), spec.get("lamb", 100)
         if self.hooked:
@@ -147,8 +150,14 @@ class MixedBatchedANMEnv:
     ``[0, 0]``); ``single_observation_spaces[k]`` / ``single_action_spaces[k]`` are those of task k."""
 
     def __init__(self, tasks, env_task, device="cuda", seed=None, tol=1e-5, max_iter=100, precision="f64", autoreset=False,
-                 env_offset=0, streams=True, max_episode_steps=None, episode_stats=False, io_dtype=None):
+                 env_offset=0, streams=True, max_episode_steps=None, episode_stats=False, io_dtype=None, action_map=None, obs_map=None,
+                 reward_scale=None):
         from ..io_dtype import check_io_dtype
+
+        if action_map is not None or obs_map is not None or reward_scale is not None:
+            # (the affine maps live in the kernels of ONE model's own batch; a batch view is refused by the library)
+            raise E.EnvInitializationError("MixedBatchedANMEnv steps through batch views, which take no affine I/O map "
+                                           "(action_map / obs_map / reward_scale): use BatchedANMEnv")
 
         if check_io_dtype(io_dtype) != torch.float64:
             # (float32 action / obs / reward I/O lives in the kernels of ONE model's own batch; a batch view is refused by the library)

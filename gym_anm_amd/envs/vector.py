@@ -30,6 +30,8 @@ class NumpyVectorEnv:
         self.single_observation_space = env.observation_space
         self.action_space = env.action_space          # per-environment Box; actions are [num_envs, A]
         self.observation_space = env.observation_space
+        # (action_map= / obs_map=: the two spaces above are the mapped ones, [-1, 1] and the Box of images; MW / MVAr here)
+        self.raw_action_space = getattr(env, "raw_action_space", env.action_space)
         self.render_mode = None
         env.check_actions = False                     # checked here on the host, where the data already is
         self._pinned = None

@@ -315,6 +315,34 @@ int anm_model_bind_state_same(anm_model* m, uint8_t* state_same);
 #define ANM_IO_F32 1
 int anm_model_set_io(anm_model* m, int32_t io);
 
+/* Affine policy I/O: fixed maps, given once, on the three arrays a policy touches (gym_anm_amd/io_affine.py has the
+ * semantics).  While a map is set the step kernels
+ *   read u from `action` (widened first under ANM_IO_F32) and step with a[j] = x < low[j] ? low[j] : (x > high[j] ?
+ *     high[j] : x), x = fma(half[j], u, mid[j]) (this select form: a NaN passes, as it would unmapped), j < action_dim;
+ *   store fma(o, scale[k], bias[k]) where they would have stored the observation entry o (after the clip; both forms of
+ *     the observation, the zero rows of terminated environments -- which therefore hold `bias` -- and the rows an
+ *     in-kernel autoreset writes), k < obs_dim, and so does anm_reset_f64 for the "state" form;
+ *   store reward * reward_scale where they would have stored the reward;
+ * each ONE rounding, followed by the float32 rounding under ANM_IO_F32.  state, soc, e_loss, penalty, the flags, timestep,
+ * reset_count, nr_iters, exo_z and exo_forecast (still MW) stay raw, the episode statistics accumulate the raw reward, and
+ * all of them are bit-identical to the unmapped step fed `a`.  Still one launch, nothing allocated, graph-capturable.
+ * All arrays are HOST arrays of doubles, copied by the call.  The action quartet is all NULL (actions are not mapped) or
+ * all set, [action_dim] each; the observation pair likewise, [obs_dim] each: obs_dim is the n_obs of the list that is set
+ * in the kernel (anm_model_set_obs), state_base_dim + K otherwise.  reward_scale == 1.0: the reward is not mapped.  A NULL
+ * struct turns the mode off.  Call it after anm_model_set_env and anm_model_set_obs; while a map is set both are refused
+ * (its tables have their lengths): clear the map, change the task, set the map again.  With a list set in the kernel,
+ * anm_reset_f64 (which writes the "state" form) leaves obs unmapped: the caller maps the list it gathers.
+ * Refused: act_half, obs_scale or reward_scale not finite or not > 0, act_mid or obs_bias not finite, act_low > act_high;
+ * and together with a batch view (anm_model_bind_view), parameter classes (anm_model_set_classes with more than one class,
+ * anm_model_bind_env_classes) or anm_model_bind_state_same (obs is no copy of the state row) -- from either side -- and,
+ * at anm_step_f64, with `full` when no list-form observation is set in the kernel. */
+typedef struct anm_io_map {
+  const double *act_mid, *act_half, *act_low, *act_high;
+  const double *obs_scale, *obs_bias;
+  double reward_scale;
+} anm_io_map;
+int anm_model_set_io_map(anm_model* m, const anm_io_map* map);
+
 /* The reference's solver returns the final mismatch next to the iteration count (`diff` of
  * _newton_raphson_sparse, solve_load_flow.py:176-226: ||F(x)||inf of the iterate it stopped at).  With an array bound here
  * (DEVICE double [num_envs], caller-owned, alive while bound; NULL unbinds) anm_transition_f64 and anm_reset_f64 write it per
