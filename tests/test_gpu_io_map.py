@@ -5,7 +5,10 @@ plain and steps with ``io_affine.map_action(u)`` evaluated exactly on the host; 
 of A equals B's, and A's obs / reward are ``map_obs`` / ``map_reward`` of B's (then the one float32 rounding).
   1. pairs over the five (network, family) pairs, both modes, both dtypes, partial maps;  2. terminal-on-entry rows;  3. tails;
   4. the fused list observation;  5. the two-launch step;  6. masked reset();  7. nothing allocated, capturable;  8. refusals
-  and NULL;  9. the NumPy adapter."""
+  and NULL;  9. the NumPy adapter.
+Modes: "series", "uniform", and the series-noise task of tests/test_gpu_exo_noise.py with the expected forecast (H = 3) --
+"noise" (white noise) and "noise_corr" (AR(1), ``exo_corr=rho_of(net)``): the map beside the ``exo_z`` read-modify-write and
+the forecast rows, which stay raw MW (``exo_forecast`` of A is B's, rounded once to A's io_dtype)."""
 import ctypes as C
 
 import numpy as np
@@ -17,6 +20,8 @@ from gym_anm_amd.envs import ANM6EasyVec, MixedBatchedANMEnv, NumpyVectorEnv
 from gym_anm_amd.envs.anm6 import anm6easy_series
 from gym_anm_amd.envs.anm_env import BatchedANMEnv
 
+from test_gpu_exo_corr import rho_of
+from test_gpu_exo_noise import task_of
 from test_gpu_io_f32 import F64_OUT, FAMILIES, LIST_OBS, NETS, STATS, device_reset, f64_outputs, series_of
 
 pytestmark = pytest.mark.gpu
@@ -25,6 +30,7 @@ GAMMA = 0.995
 F32, F64 = torch.float32, torch.float64
 FULL_MAP = dict(action_map="unit", obs_map="box", reward_scale=1 / 64)
 E_THREAD, E_GROUP = 165, 229   # two full wavefronts and a partial one; a partial last lane group
+NOISE_MODES, H_NOISE = ("noise", "noise_corr"), 3
 
 
 def n_envs(impl):
@@ -35,7 +41,12 @@ def make_env(net, impl, mode, E_, seed, observation="state", **kw):
     if mode == "series":
         ser = series_of(net)
         kw.update(series=ser, aux_bounds=np.array(((0, ser.shape[1] - 1),)))
+    elif mode in NOISE_MODES:
+        ser, amp, low, high = task_of(net)
+        kw.update(exogenous="series_noise", series=ser, exo_noise=amp, exo_low=low, exo_high=high, forecast_horizon=H_NOISE,
+                  exo_corr=rho_of(net) if mode == "noise_corr" else None, aux_bounds=np.array(((0, ser.shape[1] - 1),)))
     else:
+        assert mode == "uniform"
         kw.update(exogenous="uniform", aux_bounds=np.array(((0, 1000),)))
     env = BatchedANMEnv(NETS[net](), observation, 1, 0.25, GAMMA, 100, costs_clipping=(1, 100), seed=seed, num_envs=E_,
                         device=DEV, tol=1e-6, impl=impl, **kw)
@@ -93,6 +104,12 @@ def compare(a, b, oa, ob, where, stats=False, ra=None, rb=None):
     ra = a.reward if ra is None else ra
     rb = b.reward if rb is None else rb
     assert ra.dtype == a.io_dtype and same_bits(ra, expect_reward(a, rb)), "%s: reward is not map_reward of the plain mode's" % where
+    if a.forecast_horizon is not None:     # the series-noise modes: the noise states are B's, the forecast stays raw MW under the map
+        assert (a.exo_z is None) == (b.exo_z is None) == (a.exo_corr is None)
+        if a.exo_z is not None:
+            assert a.exo_z.dtype == F64 and same_bits(a.exo_z, b.exo_z), "%s: exo_z differs" % where
+        assert a.exo_forecast.dtype == a.io_dtype and b.exo_forecast.dtype == F64 and a.exo_forecast.shape == b.exo_forecast.shape
+        assert same_bits(a.exo_forecast, b.exo_forecast.to(a.io_dtype)), "%s: exo_forecast is not the plain mode's, rounded once" % where
     lo = torch.as_tensor(a.observation_space.low, device=DEV)
     hi = torch.as_tensor(a.observation_space.high, device=DEV)
     assert lo.dtype == a.io_dtype
@@ -122,6 +139,7 @@ def rollout(a, b, n_steps, seed, where, stats=False, before_step=None):
 # ---- 1. the mapped mode is the plain mode plus the three maps ---------------------------------------------------------------------
 ROLL = dict(autoreset=True, max_episode_steps=3, episode_stats=True)
 CASES = [(n, i, m, d) for n, i in FAMILIES for m in ("series", "uniform") for d in (F64, F32)]
+CASES += [(n, i, m, d) for n, i in FAMILIES for m in NOISE_MODES for d in (F64, F32)]
 
 
 @pytest.mark.parametrize("net,impl,mode,dtype", CASES)
@@ -134,7 +152,10 @@ def test_mapped_mode_is_the_plain_mode_plus_the_maps(net, impl, mode, dtype):
     assert a.raw_action_space.dtype == a.action_space.dtype
     assert np.array_equal(a.raw_action_space.low, want[0]) and np.array_equal(a.raw_action_space.high, want[1])
     assert a._state_same is None
+    if mode in NOISE_MODES:
+        assert a.exo_forecast.shape == (E_, task_of(net)[0].shape[0], H_NOISE) and (a.exo_z is not None) == (mode == "noise_corr")
     n_reset = rollout(a, b, 8, 17, "%s %s %s %s" % (net, impl, mode, dtype), stats=True)
+    print("%s %s %s %s: %d in-kernel resets" % (net, impl, mode, dtype, n_reset))
     assert n_reset >= E_          # the limit of 3 sends every environment through the in-kernel autoreset
     assert int(a.episodes_done.min()) >= 1
 
@@ -169,14 +190,23 @@ def test_one_map_alone(net, impl, maps):
 @pytest.mark.parametrize("dtype", [F64, F32])
 @pytest.mark.parametrize("net,impl", FAMILIES)
 def test_terminal_on_entry_rows_hold_the_bias(net, impl, dtype):
-    a, b = make_pair(net, impl, "series", n_envs(impl), 5, io_dtype=dtype)
+    terminal_on_entry_rows_hold_the_bias(net, impl, dtype, "series")
+
+
+@pytest.mark.parametrize("net,impl", [("anm6", "thread"), ("case30", "radial"), ("anm6", "mesh")])
+def test_terminal_on_entry_rows_hold_the_bias_beside_noise_and_forecast(net, impl):
+    terminal_on_entry_rows_hold_the_bias(net, impl, F32, "noise_corr")
+
+
+def terminal_on_entry_rows_hold_the_bias(net, impl, dtype, mode):
+    a, b = make_pair(net, impl, mode, n_envs(impl), 5, io_dtype=dtype)
 
     def mark(t, a, b):
         if t == 0:
             for env in (a, b):
                 env._term_u8[::7] = 1
 
-    rollout(a, b, 3, 3, "terminal %s %s" % (net, impl), before_step=mark)
+    rollout(a, b, 3, 3, "terminal %s %s %s" % (net, impl, mode), before_step=mark)
     assert bool(a.terminated[::7].all())
     bias = torch.as_tensor(a.io_map["obs"][1], dtype=F64, device=DEV).to(dtype)
     rows = a._state_obs[::7]
@@ -248,9 +278,18 @@ def test_two_launch_step(dtype):
 @pytest.mark.parametrize("net,impl,observation", [("anm6", "thread", "state"), ("anm6", "radial", "state"), ("case30", "mesh", "state"),
                                                   ("anm6", "thread", LIST_OBS), ("case30", "radial", LIST_OBS)])
 def test_masked_reset(net, impl, observation):
+    masked_reset(net, impl, observation, "series")
+
+
+@pytest.mark.parametrize("net,impl", [("anm6", "thread"), ("anm6", "radial"), ("case30", "mesh")])
+def test_masked_reset_beside_noise_and_forecast(net, impl):
+    masked_reset(net, impl, "state", "noise_corr")
+
+
+def masked_reset(net, impl, observation, mode):
     E_ = 131
-    a, b = make_pair(net, impl, "series", E_, 9, io_dtype=F32, observation=observation)
-    where = "masked reset %s %s" % (net, impl)
+    a, b = make_pair(net, impl, mode, E_, 9, io_dtype=F32, observation=observation)
+    where = "masked reset %s %s %s" % (net, impl, mode)
     rollout(a, b, 2, 4, where)
     m = torch.arange(E_, device=DEV) % 3 == 0
     oa, _ = device_reset(a, m)                                  # the device sampler
@@ -271,8 +310,16 @@ def test_masked_reset(net, impl, observation):
 
 # ---- 7. one launch, nothing allocated, capturable ---------------------------------------------------------------------------------------
 def test_nothing_allocated_and_capturable():
+    nothing_allocated_and_capturable()
+
+
+def test_nothing_allocated_and_capturable_beside_noise_and_forecast():
+    nothing_allocated_and_capturable(exogenous="series_noise", exo_noise=0.5, exo_corr=0.8, forecast_horizon=H_NOISE)
+
+
+def nothing_allocated_and_capturable(**task):
     E_, SEED = 256, 21
-    kw = dict(num_envs=E_, seed=SEED, tol=1e-6, device=DEV, io_dtype=F32, **FULL_MAP, **ROLL)
+    kw = dict(num_envs=E_, seed=SEED, tol=1e-6, device=DEV, io_dtype=F32, **FULL_MAP, **ROLL, **task)
     env, twin = ANM6EasyVec(**kw), ANM6EasyVec(**kw)
     for e in (env, twin):
         e.check_actions = False
@@ -296,6 +343,8 @@ def test_nothing_allocated_and_capturable():
         for k in STATS:
             assert torch.equal(getattr(env, k), getattr(twin, k)), "replay %d: %s" % (t, k)
         assert same_bits(env._state_obs, o2) and same_bits(env.reward, r2), "replay %d" % t
+        if task:
+            assert same_bits(env.exo_z, twin.exo_z) and same_bits(env.exo_forecast, twin.exo_forecast), "replay %d" % t
     assert int(env.episodes_done.min()) >= 1
     torch.cuda.synchronize()
     m0 = torch.cuda.memory_allocated()
@@ -304,6 +353,8 @@ def test_nothing_allocated_and_capturable():
         o, r, _, _, _ = twin.step(buf)
         assert torch.cuda.memory_allocated() == m0
     assert o is twin._state_obs and r is twin.reward and o.dtype == F32 and r.dtype == F32
+    if task:
+        assert env.exo_forecast.dtype == F32 and env.exo_forecast.shape == (E_, 5, H_NOISE)
 
 
 def test_the_mapped_anm6easy_step_is_the_coalesced_row_kernel():
