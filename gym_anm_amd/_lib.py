@@ -142,6 +142,13 @@ class IoMap(C.Structure):
                [("reward_scale", C.c_double)]  # fmt: skip
 
 
+class IoNorm(C.Structure):
+    """anm_io_norm: the device buffers and constants of the running normalisation (anm_model_io_norm_update; io_norm.py)"""
+    _fields_ = [("stats", C.c_void_p), ("counters", C.c_void_p), ("slabs", C.c_void_p), ("n_slab_doubles", C.c_int64),
+                ("ret_acc", C.c_void_p), ("t_seen", C.c_void_p), ("gamma", C.c_double), ("eps", C.c_double),
+                ("obs_on", C.c_int32), ("reward_on", C.c_int32)]
+
+
 class SolverOpts(C.Structure):
     """anm_solver_opts.  row_continuation: 0 the library's policy, 1 always rows, -1 always lane groups, 2 the policy with
     the row passes on one lane per bus even where the topology has a pair layout (include/anm_mi355x.h)"""
@@ -193,6 +200,8 @@ ABI = {
     "anm_model_bind_state_same": (C.c_int, [C.c_void_p, _P]),
     "anm_model_set_io": (C.c_int, [C.c_void_p, C.c_int32]),
     "anm_model_set_io_map": (C.c_int, [C.c_void_p, C.POINTER(IoMap)]),
+    "anm_model_io_norm_update": (C.c_int, [C.c_void_p, C.c_int64, _P, _P, _P, _P, _P, C.POINTER(IoNorm), _P]),
+    "anm_model_io_norm_tables": (C.c_int, [C.c_void_p, C.POINTER(IoNorm), _P]),
     "anm_model_bind_nr_diff": (C.c_int, [C.c_void_p, _P]),
     "anm_model_bind_nr_start": (C.c_int, [C.c_void_p, _P]),
     "anm_model_bind_view": (C.c_int, [C.c_void_p, C.POINTER(BatchView)]),
@@ -223,7 +232,7 @@ ABI = {
 
 # entry points of modes that live in the GPU kernels alone: a backend that is not the GPU library (the host test double)
 # may lack them -- the host layer refuses those modes on such a backend before it would call them
-GPU_ONLY = ("anm_model_set_io", "anm_model_set_io_map", "anm_mpc_act_stream_f64", "anm_mpc_act_chain_f64", "anm_mpc_act_expect_f64", "anm_test_row_dpp")
+GPU_ONLY = ("anm_model_set_io", "anm_model_set_io_map", "anm_model_io_norm_update", "anm_model_io_norm_tables", "anm_mpc_act_stream_f64", "anm_mpc_act_chain_f64", "anm_mpc_act_expect_f64", "anm_test_row_dpp")
 
 
 def bind(cdll, optional=()):

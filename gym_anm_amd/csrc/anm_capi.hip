@@ -24,6 +24,7 @@
 #include ANM_TOPO_HEADER
 #include "anm_devbuf.hpp"
 #include "anm_env_ops.hpp"
+#include "anm_io_norm.hpp"
 #include "anm_pack.hpp"
 #include "anm_radial.hpp"
 #include "anm_mesh.hpp"
@@ -1074,6 +1075,77 @@ int anm_model_set_io_map(anm_model* m, const anm_io_map* map) {
   if (e != hipSuccess) return fail_hip(e, "anm_model_set_io_map");
   m->d_iomap = std::move(d);
   return 0;
+}
+
+namespace {
+
+// what both entry points of the running normalisation check, and the arguments of its kernels
+int io_norm_args(const char* who, anm_model* m, const anm_io_norm* nm, ionorm::Args& a) {
+  const std::string w = who;
+  if (!m) return fail((w + ": null model").c_str());
+  if (!nm) return fail((w + ": null anm_io_norm").c_str());
+  if (!m->d_iomap.get())
+    return fail((w + ": no affine I/O map is set (anm_model_set_io_map): the running normalisation rewrites the tables of that map").c_str());
+  if (m->has_view) return fail((w + ": the running normalisation does not go with a batch view (anm_model_bind_view)").c_str());
+  if (m->n_classes() > 1 || m->d_env_class)
+    return fail((w + ": the running normalisation does not take parameter classes (anm_model_set_classes / anm_model_bind_env_classes)").c_str());
+  if (!nm->stats || !nm->counters) return fail((w + ": stats and counters must be set").c_str());
+  if (!(std::isfinite(nm->eps) && nm->eps > 0.0)) return fail((w + ": eps must be finite and > 0").c_str());
+  if (!(nm->gamma >= 0.0 && nm->gamma <= 1.0)) return fail((w + ": gamma must be in [0, 1]").c_str());
+  a = ionorm::Args{};
+  a.iomap = m->d_iomap.get();
+  a.off_scale = IoMap::obs(m->dims.action_dim);
+  a.D = m->n_obs > 0 ? m->n_obs : m->dims.state_base_dim + m->K;
+  a.stats = nm->stats;
+  a.counters = reinterpret_cast<long long*>(nm->counters);
+  a.slabs = nm->slabs;
+  a.G = nm->ret_acc;
+  a.t_seen = nm->t_seen;
+  a.gamma = nm->gamma;
+  a.eps = nm->eps;
+  a.obs_on = nm->obs_on ? 1 : 0;
+  a.reward_on = nm->reward_on ? 1 : 0;
+  return 0;
+}
+
+}  // namespace
+
+int anm_model_io_norm_update(anm_model* m, int64_t num_envs, const double* obs, const double* reward, const uint8_t* terminated,
+                             const uint8_t* truncated, const int32_t* timestep, const anm_io_norm* nm, void* stream) {
+  const char* who = "anm_model_io_norm_update";
+  ionorm::Args a;
+  if (int rc = io_norm_args(who, m, nm, a)) return rc;
+  if (num_envs < 1) return fail("anm_model_io_norm_update: num_envs < 1");
+  if (!a.obs_on && !a.reward_on) return 0;
+  if (!obs || !reward || !terminated || !timestep) return fail("anm_model_io_norm_update: obs, reward, terminated and timestep must be set");
+  if (a.reward_on && (!a.G || !a.t_seen)) return fail("anm_model_io_norm_update: ret_acc and t_seen must be set while reward_on is");
+  const int rows = ionorm::rows_per_group(num_envs);
+  const int64_t groups = (num_envs + rows - 1) / rows;
+  if (groups > ionorm::MAX_SLABS) return fail("anm_model_io_norm_update: more than 4 194 304 environments (4096 slabs of 1024 rows)");
+  if (!nm->slabs || nm->n_slab_doubles < groups * ionorm::slab_doubles(a.D))
+    return fail("anm_model_io_norm_update: the slab buffer is too short: ceil(num_envs / rows) slabs of 4 + 2 obs_dim doubles each, "
+                "rows = 256 up to 262 144 environments and 1024 above");
+  a.obs = obs;
+  a.reward = reward;
+  a.terminated = terminated;
+  a.truncated = truncated;
+  a.timestep = timestep;
+  a.E = num_envs;
+  a.n_slabs = int(groups);
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const bool f32 = m->io_mode == ANM_IO_F32;
+  auto partial = [&](auto kernel) { return launch("launch k_norm_partial", kernel, unsigned(groups), ionorm::LANES, 0, s, a); };
+  if (int rc = rows == ionorm::WAVES * ionorm::SUB
+                   ? (f32 ? partial(ionorm::k_norm_partial<true, 1>) : partial(ionorm::k_norm_partial<false, 1>))
+                   : (f32 ? partial(ionorm::k_norm_partial<true, 4>) : partial(ionorm::k_norm_partial<false, 4>)))
+    return rc;
+  return launch("launch k_norm_finish", ionorm::k_norm_finish, 1, ionorm::FINISH_LANES, (size_t(ionorm::slab_doubles(a.D)) + 1) * sizeof(double), s, a);
+}
+
+int anm_model_io_norm_tables(anm_model* m, const anm_io_norm* nm, void* stream) {
+  ionorm::Args a;
+  if (int rc = io_norm_args("anm_model_io_norm_tables", m, nm, a)) return rc;
+  return launch("launch k_norm_tables", ionorm::k_norm_tables, 1, ionorm::LANES, 0, static_cast<hipStream_t>(stream), a);
 }
 
 int anm_model_bind_view(anm_model* m, const anm_batch_view* v) {

@@ -28,6 +28,7 @@ arrays, inside the kernels: unit actions in, scaled observations and rewards out
 from __future__ import annotations
 
 import ctypes as C
+import gc
 from copy import deepcopy
 
 import numpy as np
@@ -38,6 +39,7 @@ from .. import episode as _episode
 from .. import errors as E
 from .. import io_affine as _aff
 from .. import io_dtype as _io
+from .. import io_norm as _nrm
 from .. import rng as _rng
 from ..model import STATE_VARIABLES
 from ..simulator import BatchedSimulator, StateView, _stream_ptr
@@ -102,11 +104,14 @@ class BatchedANMEnv(GymEnv):
                  fuse_observation=True, variants=None, env_variant=None, exogenous=None, exo_low=None, exo_high=None, exo_noise=None,
                  exo_corr=None, forecast_horizon=None,
                  max_episode_steps=None, episode_stats=False, io_dtype=None, action_map=None, obs_map=None, reward_scale=None,
-                 _backend=None):  # fmt: skip
+                 obs_norm=None, reward_norm=None, norm_eps=_nrm.EPS_DEFAULT, _backend=None):  # fmt: skip
         GymEnv.reset(self, seed=seed)
+        # a simulator sits in a reference cycle, so the device buffers of an environment that was dropped wait for the cycle
+        # collector: collect here, where the next environment is about to allocate its own, not at some later step()
+        gc.collect()
         # affine policy I/O inside the kernels (gym_anm_amd/io_affine.py has the semantics): checked before anything is built
         self._check_io_map_args(action_map, obs_map, reward_scale, observation, fuse_observation, track_full,
-                                variants is not None or env_variant is not None)
+                                variants is not None or env_variant is not None, obs_norm, reward_norm, norm_eps)
         self.K, self.gamma, self.lamb, self.delta_t = K, gamma, lamb, delta_t
         self.aux_bounds = aux_bounds
         if costs_clipping is None:
@@ -147,8 +152,8 @@ class BatchedANMEnv(GymEnv):
 
         if self._mapped and sim.backend.device_type != "cuda":
             # (a backend that ignores the maps would step with the unit actions as MW without saying so)
-            raise E.EnvInitializationError("action_map / obs_map / reward_scale need the GPU library: this backend maps nothing "
-                                           "in its kernels")
+            raise E.EnvInitializationError("action_map / obs_map / reward_scale / obs_norm / reward_norm need the GPU library: "
+                                           "this backend maps nothing in its kernels")
 
         self.state_values = self._expand_all_ids(
             [("dev_p", "all", "MW"), ("dev_q", "all", "MVAr"), ("des_soc", "all", "MWh"), ("gen_p_max", "all", "MW"),
@@ -180,6 +185,10 @@ class BatchedANMEnv(GymEnv):
                 sc, bi = _aff.box_obs_map(lo64, hi64) if isinstance(self._obs_map_arg, str) else self._obs_map_arg
                 self._map_obs = _aff.check_obs_map(sc, bi, self.observation_N)
                 self.observation_space = Box(*_aff.observation_image(lo64, hi64, *self._map_obs), dtype=np.float64)
+            if self._obs_norm:   # the tables move: no finite Box holds (io_norm.py); they start at those of the initial statistics
+                self._map_obs = _nrm.tables(np.zeros(self.observation_N), np.ones(self.observation_N), self.norm_eps)
+                inf = np.full(self.observation_N, np.inf)
+                self.observation_space = Box(low=-inf, high=inf, dtype=np.float64)
             if self._io32:
                 lo32, hi32 = _io.observation_bounds32(self.observation_space.low, self.observation_space.high)
                 self.observation_space = Box(low=lo32, high=hi32, dtype=np.float32)
@@ -203,13 +212,22 @@ class BatchedANMEnv(GymEnv):
         self._set_io_map()
         self._plan_step_path(track_full, straggler_after, straggler_mid, max_iter)
 
-    def _check_io_map_args(self, action_map, obs_map, reward_scale, observation, fuse_observation, track_full, has_classes):
+    def _check_io_map_args(self, action_map, obs_map, reward_scale, observation, fuse_observation, track_full, has_classes,
+                           obs_norm=None, reward_norm=None, norm_eps=_nrm.EPS_DEFAULT):
         """action_map=None | "unit" | (mid, half); obs_map=None | "box" | (scale, bias); reward_scale=None | a finite number
         > 0: fixed affine maps applied INSIDE the step and reset kernels (gym_anm_amd/io_affine.py).  The policy sends u, the
         kernels step with a = clamp(fma(half, u, mid)) inside the action Box ("unit": [-1, 1] onto the Box); they store
         fma(o, scale, bias) for every observation entry o ("box": every column with finite ends onto about [-1, 1]) and
         reward * reward_scale.  Everything else -- state, costs, episode statistics, exo_forecast (MW) -- stays raw.  With all
-        three None nothing changes.  What the mode does not serve is refused here, by the name of the argument."""
+        three None nothing changes.  What the mode does not serve is refused here, by the name of the argument.
+
+        obs_norm=None | "running", reward_norm=None | "running", norm_eps: the observation tables / the reward scale of the
+        same map follow running statistics kept on the device -- mean and variance of the observations, variance of the
+        discounted return -- rewritten after every step() by two small launches behind the step kernel
+        (gym_anm_amd/io_norm.py).  obs_norm excludes obs_map, reward_norm excludes reward_scale, action_map is free."""
+        self._obs_norm, self._reward_norm, self.norm_eps = _nrm.check_norm_args(obs_norm, reward_norm, norm_eps, obs_map, reward_scale)
+        self._norm_on = self._obs_norm or self._reward_norm
+        self.norm_training = True   # False: step() skips the update -- tables and statistics frozen (evaluation)
         for name, val, word in (("action_map", action_map, "unit"), ("obs_map", obs_map, "box")):
             if val is None or (isinstance(val, str) and val == word):
                 continue
@@ -219,10 +237,11 @@ class BatchedANMEnv(GymEnv):
         self._obs_map_arg = None if obs_map is None else obs_map if isinstance(obs_map, str) else tuple(obs_map)
         self.reward_scale = None if reward_scale is None else _aff.check_reward_scale(reward_scale)
         self._map_act = self._map_obs = None   # the resolved host tables: (mid, half, low, high), (scale, bias)
-        self._mapped = action_map is not None or obs_map is not None or reward_scale is not None
+        self._mapped = action_map is not None or obs_map is not None or reward_scale is not None or self._norm_on
         if not self._mapped:
             return
-        which = "/".join(n for n, v in (("action_map", action_map), ("obs_map", obs_map), ("reward_scale", reward_scale)) if v is not None)
+        which = "/".join(n for n, v in (("action_map", action_map), ("obs_map", obs_map), ("reward_scale", reward_scale),
+                                        ("obs_norm", obs_norm), ("reward_norm", reward_norm)) if v is not None)
         if has_classes:
             raise E.EnvInitializationError("%s does not take parameter classes (variants=)" % which)
         if callable(observation):
@@ -241,7 +260,18 @@ class BatchedANMEnv(GymEnv):
         ``action`` = (mid, half, low, high) or None, ``obs`` = (scale, bias) or None, ``reward_scale`` (1.0 when not given)."""
         if not self._mapped:
             return None
-        return dict(action=self._map_act, obs=self._map_obs, reward_scale=1.0 if self.reward_scale is None else self.reward_scale)
+        rs = 1.0 if self.reward_scale is None else self.reward_scale
+        if self._reward_norm:   # (running: what the device holds now -- the read synchronises)
+            rs = float(self._norm_stats[_nrm.STATS_HEAD - 4])
+        return dict(action=self._map_act, obs=self._obs_tables_now(), reward_scale=rs)
+
+    def _obs_tables_now(self):
+        """(scale, bias) on the host, or None: the fixed tables, or -- obs_norm -- a copy of what the device holds now"""
+        if not self._obs_norm:
+            return self._map_obs
+        D, H = self.observation_N, _nrm.STATS_HEAD
+        t = self._norm_stats[H + 2 * D:H + 4 * D].cpu().numpy()
+        return t[:D].copy(), t[D:].copy()
 
     def encode_action(self, a_mw):
         """The u to send for an action in MW / MVAr (an ``MPCAgent``'s): ``(a_mw - mid) / half``; the action itself without
@@ -259,7 +289,8 @@ class BatchedANMEnv(GymEnv):
         if self._gather is not None and not self._obs_fused:
             raise E.EnvInitializationError("action_map / obs_map / reward_scale need the list-form observation gathered inside "
                                            "the step kernel: this model cannot gather in its kernel")
-        m = _lib.IoMap(reward_scale=1.0 if self.reward_scale is None else self.reward_scale)
+        rs0 = _nrm.reward_scale(1.0, self.norm_eps) if self._reward_norm else self.reward_scale
+        m = _lib.IoMap(reward_scale=1.0 if rs0 is None else rs0)
         keep = []
         for names, tabs in ((("act_mid", "act_half", "act_low", "act_high"), self._map_act), (("obs_scale", "obs_bias"), self._map_obs)):
             for name, tab in zip(names, tabs or ()):
@@ -268,6 +299,8 @@ class BatchedANMEnv(GymEnv):
                 setattr(m, name, ptr)
         with sim._device_ctx():
             sim.backend.check(sim.backend.lib.anm_model_set_io_map(sim._handle, C.byref(m)), "anm_model_set_io_map")
+        if self._norm_on:
+            self._norm_write_tables()
 
     def _alloc_buffers(self):
         """Device-resident per-environment state, and the episode buffers the step kernels keep."""
@@ -310,6 +343,106 @@ class BatchedANMEnv(GymEnv):
                 b.last_disc_return = self.last_episode_discounted_return.data_ptr()
                 b.last_length, b.episodes_done = self.last_episode_length.data_ptr(), self.episodes_done.data_ptr()
             self._episode_bufs = b
+        # running normalisation (gym_anm_amd/io_norm.py): statistics, counters, the slabs between the two launches of an
+        # update, and per environment the discounted-return accumulator and the timestep last seen
+        self._norm_ref = self._norm_args = None
+        if self._norm_on:
+            D, H = self.observation_N, _nrm.STATS_HEAD
+            self._norm_stats = torch.zeros(H + 4 * D, **f64)
+            self._norm_counters = torch.zeros(2, dtype=torch.int64, device=self.device)
+            self._norm_slabs = torch.zeros(_nrm.slab_doubles(E_, D), **f64)
+            self._norm_G = torch.zeros(E_, **f64)
+            self._norm_t_seen = torch.zeros(E_, dtype=torch.int32, device=self.device)
+            self._norm_struct = _lib.IoNorm(
+                stats=self._norm_stats.data_ptr(), counters=self._norm_counters.data_ptr(), slabs=self._norm_slabs.data_ptr(),
+                n_slab_doubles=self._norm_slabs.numel(), ret_acc=self._norm_G.data_ptr(), t_seen=self._norm_t_seen.data_ptr(),
+                gamma=float(self.gamma), eps=self.norm_eps, obs_on=int(self._obs_norm), reward_on=int(self._reward_norm))
+            self._norm_ref = C.byref(self._norm_struct)
+            self._norm_fill(_nrm.initial_state(E_, D))
+
+    # ---- running normalisation (gym_anm_amd/io_norm.py) -----------------------------------------------------------------------
+    def _norm_fill(self, d):
+        """The device buffers from a state dict of io_norm.py (host values); the mirrors of the tables by rule 1 -- a part
+        that is off: the identity of io_affine.py rule 8 -- until anm_model_io_norm_tables rewrites them."""
+        D, H = self.observation_N, _nrm.STATS_HEAD
+        mean, var = np.asarray(d["mean"], dtype=np.float64), np.asarray(d["var"], dtype=np.float64)
+        G, seen = np.asarray(d["G"], dtype=np.float64), np.asarray(d["t_seen"], dtype=np.int32)
+        if mean.shape != (D,) or var.shape != (D,) or G.shape != (self.num_envs,) or seen.shape != (self.num_envs,):
+            raise E.ArgsError("norm state: mean and var must have %d entries, G and t_seen %d" % (D, self.num_envs))
+        scale, bias = _nrm.tables(mean, var, self.norm_eps) if self._obs_norm else (np.ones(D), np.full(D, -0.0))
+        rs = _nrm.reward_scale(d["rvar"], self.norm_eps) if self._reward_norm else 1.0
+        head = [float(d["cnt"]), float(d["rcnt"]), float(d["rmean"]), float(d["rvar"]), rs, 0.0, 0.0, 0.0]
+        self._norm_stats.copy_(torch.as_tensor(np.concatenate([head, mean, var, scale, bias]), dtype=torch.float64))
+        self._norm_counters.copy_(torch.as_tensor([int(d["n_updates"]), int(d["n_skipped"])], dtype=torch.int64))
+        self._norm_G.copy_(torch.as_tensor(G))
+        self._norm_t_seen.copy_(torch.as_tensor(seen))
+
+    def _norm_write_tables(self):
+        """Rule 1 on the device: the tables of the map from the statistics block (anm_model_io_norm_tables)."""
+        sim = self.simulator
+        with sim._device_ctx():
+            sim.backend.check(sim.backend.lib.anm_model_io_norm_tables(sim._handle, self._norm_ref, _stream_ptr(self.device)),
+                              "anm_model_io_norm_tables")
+
+    def _norm_views(self, lo):
+        from types import SimpleNamespace
+
+        D, H, s = self.observation_N, _nrm.STATS_HEAD, self._norm_stats
+        if lo == 0:
+            return SimpleNamespace(count=s[0:1], mean=s[H:H + D], var=s[H + D:H + 2 * D], scale=s[H + 2 * D:H + 3 * D],
+                                   bias=s[H + 3 * D:H + 4 * D])
+        return SimpleNamespace(count=s[1:2], mean=s[2:3], var=s[3:4], scale=s[4:5])
+
+    @property
+    def obs_rms(self):
+        """The running observation statistics ON THE DEVICE, to read (views: count [1], mean, var and the tables they give,
+        scale and bias, [obs_dim] each; float64), or None without obs_norm.  To change them: load_norm_state()."""
+        return self._norm_views(0) if self._obs_norm else None
+
+    @property
+    def ret_rms(self):
+        """The running statistics of the discounted return on the device, to read (views: count, mean, var, and scale = the
+        reward_scale of the map; [1] each), or None without reward_norm."""
+        return self._norm_views(1) if self._reward_norm else None
+
+    def norm_state(self):
+        """Host copies of everything the running normalisation keeps (the dict of io_norm.py: cnt, mean, var, rcnt, rmean,
+        rvar, G, t_seen, n_updates, n_skipped): a checkpoint.  Synchronises."""
+        if not self._norm_on:
+            raise E.ArgsError("norm_state() needs obs_norm or reward_norm")
+        D, H = self.observation_N, _nrm.STATS_HEAD
+        s, c = self._norm_stats.cpu().numpy(), self._norm_counters.cpu().numpy()
+        return dict(cnt=float(s[0]), rcnt=float(s[1]), rmean=float(s[2]), rvar=float(s[3]), mean=s[H:H + D].copy(),
+                    var=s[H + D:H + 2 * D].copy(), G=self._norm_G.cpu().numpy(), t_seen=self._norm_t_seen.cpu().numpy(),
+                    n_updates=int(c[0]), n_skipped=int(c[1]))
+
+    def load_norm_state(self, d):
+        """Restore a norm_state() and rewrite the tables of the map on the device from it (rule 1)."""
+        if not self._norm_on:
+            raise E.ArgsError("load_norm_state() needs obs_norm or reward_norm")
+        self._norm_fill(d)
+        self._norm_write_tables()
+
+    def _norm_update(self, stream=None, switch=None):
+        """The update pair behind a step, on the same stream (`stream`, `switch`: what _step_call found for its own launch):
+        reads what the step stored, rewrites the tables in place."""
+        sim, dev = self.simulator, self.device
+        args = self._norm_args
+        if args is None:
+            args = self._norm_args = (
+                (self._obs_buf if self._obs_fused else self._state_obs).data_ptr(), self.reward.data_ptr(),
+                self._term_u8.data_ptr(), self._trunc_u8.data_ptr(), self.timestep.data_ptr(), self._norm_ref)
+        if stream is None:
+            stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+            switch = torch.cuda.current_device() != dev.index
+        fn = sim.backend.lib.anm_model_io_norm_update
+        if switch:
+            with torch.cuda.device(dev):
+                rc = fn(sim._handle, self.num_envs, *args, stream)
+        else:
+            rc = fn(sim._handle, self.num_envs, *args, stream)
+        if rc != 0:
+            sim.backend.check(rc, "anm_model_io_norm_update")
 
     def _check_exogenous(self, exogenous, exo_low, exo_high, exo_noise, exo_corr, has_classes):
         """The exogenous mode and its tables, checked and resolved; nothing is handed to the library here.
@@ -702,6 +835,7 @@ class BatchedANMEnv(GymEnv):
             self._obs_buf = torch.zeros((self.num_envs, n_obs), dtype=torch.float64, device=self.device)
         out = self._obs_buf
         remap = self._map_obs is not None   # (reset() only: gathered raw, mapped on the host -- io_affine.py rule 6)
+        tables = self._obs_tables_now() if remap else None   # (obs_norm: the tables the device holds now)
         if self._io32 or remap:   # (reset() only: gathered in float64, cast once -- io_dtype.py rule 5)
             if self._obs_gather64 is None:
                 self._obs_gather64 = torch.zeros((self.num_envs, n_obs), dtype=torch.float64, device=self.device)
@@ -714,7 +848,7 @@ class BatchedANMEnv(GymEnv):
             )  # fmt: skip
         sim.backend.check(rc, "anm_gather_obs_f64")
         if remap:   # exactly the kernels' fma, evaluated on the host (rng.fma_v): reset() is not the hot path
-            out = torch.as_tensor(_aff.map_obs(out.cpu().numpy(), *self._map_obs), dtype=torch.float64, device=self.device)
+            out = torch.as_tensor(_aff.map_obs(out.cpu().numpy(), *tables), dtype=torch.float64, device=self.device)
         if out is not self._obs_buf:
             self._obs_buf.copy_(out)
         return self._obs_buf
@@ -764,6 +898,13 @@ class BatchedANMEnv(GymEnv):
                 C.byref(sim.opts), _stream_ptr(self.device),
             )  # fmt: skip
         sim.backend.check(rc, "anm_reset_f64")
+        if self._reward_norm:   # io_norm.py rule 2: the return accumulator of a re-initialised row starts over
+            if mask_u8 is None:
+                self._norm_G.zero_()
+                self._norm_t_seen.zero_()
+            else:
+                self._norm_G.masked_fill_(mask_u8.ne(0), 0.0)
+                self._norm_t_seen.masked_fill_(mask_u8.ne(0), 0)
         if self._state_same is not None:  # the reset kernel writes both rows
             if mask_u8 is None:
                 self._state_same.zero_()
@@ -921,6 +1062,8 @@ class BatchedANMEnv(GymEnv):
                         stream)  # fmt: skip
         if rc != 0:
             sim.backend.check(rc, "anm_step_f64")
+        if self._norm_on and self.norm_training:   # two small launches behind the step: the tables the NEXT step maps with
+            self._norm_update(stream, switch)
 
     def step(self, action):
         sim = self.simulator

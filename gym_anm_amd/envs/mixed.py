@@ -101,6 +101,9 @@ class _Task(BatchedANMEnv):
         if any(spec.get(k) is not None for k in ("action_map", "obs_map", "reward_scale")):
             raise E.EnvInitializationError("MixedBatchedANMEnv steps through batch views, which take no affine I/O map "
                                            "(action_map / obs_map / reward_scale): use BatchedANMEnv")
+        if any(spec.get(k) is not None for k in ("obs_norm", "reward_norm")):
+            raise E.EnvInitializationError("MixedBatchedANMEnv steps through batch views, which take no running normalisation "
+                                           "(obs_norm / reward_norm rewrite the tables of the affine I/O map): use BatchedANMEnv")
         self.hooked = spec.get("series") is None
         dt, lamb = spec.get("delta_t", 0.25), spec.get("lamb", 100)
         if self.hooked:
@@ -151,9 +154,13 @@ class MixedBatchedANMEnv:
 
     def __init__(self, tasks, env_task, device="cuda", seed=None, tol=1e-5, max_iter=100, precision="f64", autoreset=False,
                  env_offset=0, streams=True, max_episode_steps=None, episode_stats=False, io_dtype=None, action_map=None, obs_map=None,
-                 reward_scale=None):
+                 reward_scale=None, obs_norm=None, reward_norm=None):
         from ..io_dtype import check_io_dtype
 
+        if obs_norm is not None or reward_norm is not None:
+            # (the running normalisation rewrites the tables of the affine map, which a batch view does not take)
+            raise E.EnvInitializationError("MixedBatchedANMEnv steps through batch views, which take no running normalisation "
+                                           "(obs_norm / reward_norm rewrite the tables of the affine I/O map): use BatchedANMEnv")
         if action_map is not None or obs_map is not None or reward_scale is not None:
             # (the affine maps live in the kernels of ONE model's own batch; a batch view is refused by the library)
             raise E.EnvInitializationError("MixedBatchedANMEnv steps through batch views, which take no affine I/O map "

@@ -7,7 +7,7 @@ A learned policy emits values in ``[-1, 1]``, wants observations of one magnitud
 speaks MW, MVAr, p.u. and a time index.  The mode moves the three fixed affine maps between them into the step kernels.  It
 changes what is stored in ``action``, ``obs`` and ``reward`` and nothing else: *the mapped mode is the plain mode plus the
 maps below on three arrays, bit for bit*.  All constants are given at construction; there are no running statistics, no
-reduction over environments and no new state.
+reduction over environments and no new state (io_norm.py adds those, outside the step kernels).
 
 1. Action.  Tables ``mid[j]``, ``half[j]``, ``lo[j]``, ``hi[j]`` (float64, ``j < action_dim``; ``half`` finite and > 0,
    ``lo <= hi``).  The kernel reads ``u`` (under ``io_dtype=float32`` it widens ``u`` first, which is exact), forms
@@ -40,8 +40,9 @@ reduction over environments and no new state.
 
 Not served (refused, not ignored): a backend other than the GPU library, parameter classes (``variants=``), batch views and
 ``MixedBatchedANMEnv``, a list-form observation that is not gathered inside the step kernel, ``track_full`` without such a
-list, a callable observation, and ``action_map="unit"`` on a ``Box`` with an infinite end.  Running mean and variance can be
-built on top of the fixed maps; they are not part of this mode.
+list, a callable observation, and ``action_map="unit"`` on a ``Box`` with an infinite end.  Running mean and variance are
+not part of this mode: ``obs_norm="running"`` / ``reward_norm="running"`` (io_norm.py) rewrite ``scale``, ``bias`` and
+``reward_scale`` of this map on the device between steps, and the kernels below map through whatever the tables hold.
 """
 
 from __future__ import annotations

@@ -343,6 +343,42 @@ typedef struct anm_io_map {
 } anm_io_map;
 int anm_model_set_io_map(anm_model* m, const anm_io_map* map);
 
+/* Running observation and return normalisation, kept on the device (gym_anm_amd/io_norm.py has the semantics: Gymnasium's
+ * NormalizeObservation / NormalizeReward, one step late).  No step or reset kernel knows of it: they map through the tables
+ * of the affine I/O map above, and anm_model_io_norm_update rewrites obs_scale, obs_bias and reward_scale INSIDE the model's
+ * device copy of that map (whose address never changes: captured graphs stay valid) from float64 statistics of what the
+ * last anm_step_f64 stored.  Two launches in stream order -- one workgroup per 256 environments writes a slab of partial
+ * sums, one workgroup reduces the slabs and merges -- summed by ONE fixed pairwise tree over the environment index, so the
+ * result does not depend on the grid and has the same bits on every run; no atomics on floats, nothing allocated, no host
+ * synchronisation, graph-capturable behind the step.
+ * Every pointer is a DEVICE pointer, caller-owned:
+ *   stats     double [8 + 4 obs_dim]: cnt, rcnt, rmean, rvar, reward_scale (a mirror), three unused | mean | var | scale |
+ *             bias (mirrors of the tables in the map); start: cnt = rcnt = 1e-4, means 0, variances 1
+ *   counters  int64 [2]: updates made, columns skipped because their batch moments were not finite
+ *   slabs     double [n_slab_doubles], at least ceil(num_envs / rows) * (4 + 2 obs_dim), rows = 256 up to 262 144
+ *             environments and 1024 above; scratch between the two launches
+ *   ret_acc   double [num_envs]: the discounted-return accumulator G;  t_seen  int32 [num_envs]: the timestep last seen
+ *             (both zero at the start and for every row a reset re-initialises: the caller zeroes them)
+ * gamma: the discount of G; eps > 0: scale = 1 / sqrt(var + eps).  obs_on / reward_on: a part that is off keeps its tables
+ * (the identity, when the map was set without them) and its statistics untouched.  obs_dim is that of anm_model_set_io_map.
+ * `obs` and `reward` are the arrays of the step (floats under ANM_IO_F32), `truncated` may be NULL.
+ * anm_model_io_norm_tables rewrites the tables from `stats` alone (construction, a loaded checkpoint).
+ * Refused: no map set; a batch view or parameter classes (which the map itself refuses); num_envs < 1 or more than
+ * 4 194 304; a slab buffer that is too short; eps not finite or not > 0; gamma outside [0, 1]; a null array that is read. */
+typedef struct anm_io_norm {
+  double* stats;
+  int64_t* counters;
+  double* slabs;
+  int64_t n_slab_doubles;
+  double* ret_acc;
+  int32_t* t_seen;
+  double gamma, eps;
+  int32_t obs_on, reward_on;
+} anm_io_norm;
+int anm_model_io_norm_update(anm_model* m, int64_t num_envs, const double* obs, const double* reward, const uint8_t* terminated,
+                             const uint8_t* truncated, const int32_t* timestep, const anm_io_norm* norm, void* stream);
+int anm_model_io_norm_tables(anm_model* m, const anm_io_norm* norm, void* stream);
+
 /* The reference's solver returns the final mismatch next to the iteration count (`diff` of
  * _newton_raphson_sparse, solve_load_flow.py:176-226: ||F(x)||inf of the iterate it stopped at).  With an array bound here
  * (DEVICE double [num_envs], caller-owned, alive while bound; NULL unbinds) anm_transition_f64 and anm_reset_f64 write it per
