@@ -149,6 +149,15 @@ class IoNorm(C.Structure):
                 ("obs_on", C.c_int32), ("reward_on", C.c_int32)]
 
 
+class Rollout(C.Structure):
+    """anm_rollout: the device buffers and constants of the rollout buffer (anm_rollout_begin / _add / _gae / _adv_norm;
+    rollout.py)"""
+    _fields_ = [(k, C.c_void_p) for k in ["obs", "rewards", "values", "flags", "advantages", "returns", "adv_norm", "t_seen",
+                                          "stats", "slabs"]] + \
+               [("n_slab_doubles", C.c_int64), ("T", C.c_int64), ("E", C.c_int64), ("D", C.c_int32), ("io_dtype", C.c_int32),
+                ("value_dtype", C.c_int32), ("gamma", C.c_double), ("gae_lambda", C.c_double), ("eps", C.c_double)]  # fmt: skip
+
+
 class SolverOpts(C.Structure):
     """anm_solver_opts.  row_continuation: 0 the library's policy, 1 always rows, -1 always lane groups, 2 the policy with
     the row passes on one lane per bus even where the topology has a pair layout (include/anm_mi355x.h)"""
@@ -202,6 +211,10 @@ ABI = {
     "anm_model_set_io_map": (C.c_int, [C.c_void_p, C.POINTER(IoMap)]),
     "anm_model_io_norm_update": (C.c_int, [C.c_void_p, C.c_int64, _P, _P, _P, _P, _P, C.POINTER(IoNorm), _P]),
     "anm_model_io_norm_tables": (C.c_int, [C.c_void_p, C.POINTER(IoNorm), _P]),
+    "anm_rollout_begin": (C.c_int, [C.POINTER(Rollout), _P, _P, _P]),
+    "anm_rollout_add": (C.c_int, [C.POINTER(Rollout), C.c_int64, _P, _P, _P, _P, _P, _P]),
+    "anm_rollout_gae": (C.c_int, [C.POINTER(Rollout), _P]),
+    "anm_rollout_adv_norm": (C.c_int, [C.POINTER(Rollout), _P]),
     "anm_model_bind_nr_diff": (C.c_int, [C.c_void_p, _P]),
     "anm_model_bind_nr_start": (C.c_int, [C.c_void_p, _P]),
     "anm_model_bind_view": (C.c_int, [C.c_void_p, C.POINTER(BatchView)]),
@@ -232,7 +245,7 @@ ABI = {
 
 # entry points of modes that live in the GPU kernels alone: a backend that is not the GPU library (the host test double)
 # may lack them -- the host layer refuses those modes on such a backend before it would call them
-GPU_ONLY = ("anm_model_set_io", "anm_model_set_io_map", "anm_model_io_norm_update", "anm_model_io_norm_tables", "anm_mpc_act_stream_f64", "anm_mpc_act_chain_f64", "anm_mpc_act_expect_f64", "anm_test_row_dpp")
+GPU_ONLY = ("anm_model_set_io", "anm_model_set_io_map", "anm_model_io_norm_update", "anm_model_io_norm_tables", "anm_rollout_begin", "anm_rollout_add", "anm_rollout_gae", "anm_rollout_adv_norm", "anm_mpc_act_stream_f64", "anm_mpc_act_chain_f64", "anm_mpc_act_expect_f64", "anm_test_row_dpp")
 
 
 def bind(cdll, optional=()):

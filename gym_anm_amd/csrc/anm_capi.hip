@@ -25,6 +25,7 @@
 #include "anm_devbuf.hpp"
 #include "anm_env_ops.hpp"
 #include "anm_io_norm.hpp"
+#include "anm_rollout.hpp"
 #include "anm_pack.hpp"
 #include "anm_radial.hpp"
 #include "anm_mesh.hpp"
@@ -1146,6 +1147,122 @@ int anm_model_io_norm_tables(anm_model* m, const anm_io_norm* nm, void* stream) 
   ionorm::Args a;
   if (int rc = io_norm_args("anm_model_io_norm_tables", m, nm, a)) return rc;
   return launch("launch k_norm_tables", ionorm::k_norm_tables, 1, ionorm::LANES, 0, static_cast<hipStream_t>(stream), a);
+}
+
+namespace {
+
+// what every entry point of the rollout buffer checks
+int rollout_args(const char* who, const anm_rollout* rb) {
+  const std::string w = who;
+  if (!rb) return fail((w + ": null anm_rollout").c_str());
+  if (rb->T < 1 || rb->E < 1 || rb->D < 1) return fail((w + ": T, E and D must be at least 1").c_str());
+  if (rb->T > (int64_t(1) << 30) || rb->E > (int64_t(1) << 30) || rb->E * int64_t(rb->D) > (int64_t(1) << 38))
+    return fail((w + ": T or E above 2^30, or E D above 2^38").c_str());
+  for (int32_t code : {rb->io_dtype, rb->value_dtype})
+    if (code != ANM_IO_F64 && code != ANM_IO_F32) return fail((w + ": io_dtype and value_dtype must be ANM_IO_F64 or ANM_IO_F32").c_str());
+  if (!(rb->gamma >= 0.0 && rb->gamma <= 1.0)) return fail((w + ": gamma must be in [0, 1]").c_str());
+  if (!(rb->gae_lambda >= 0.0 && rb->gae_lambda <= 1.0)) return fail((w + ": gae_lambda must be in [0, 1]").c_str());
+  if (!(std::isfinite(rb->eps) && rb->eps > 0.0)) return fail((w + ": eps must be finite and > 0").c_str());
+  return 0;
+}
+
+int rollout_store(const char* what, const anm_rollout* rb, const rollout::StoreArgs& a, void* stream) {
+  const unsigned grid = unsigned((a.n_obs + rollout::STORE_LANES - 1) / rollout::STORE_LANES);   // (E D >= E)
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  return rb->io_dtype == ANM_IO_F32 ? launch(what, rollout::k_rollout_store<true>, grid, rollout::STORE_LANES, 0, s, a)
+                                    : launch(what, rollout::k_rollout_store<false>, grid, rollout::STORE_LANES, 0, s, a);
+}
+
+}  // namespace
+
+int anm_rollout_begin(const anm_rollout* rb, const void* obs, const int32_t* timestep, void* stream) {
+  if (int rc = rollout_args("anm_rollout_begin", rb)) return rc;
+  if (!rb->obs || !rb->t_seen || !obs || !timestep) return fail("anm_rollout_begin: the buffers obs and t_seen and the arrays obs and timestep must be set");
+  rollout::StoreArgs a{};
+  a.src_obs = obs;
+  a.dst_obs = rb->obs;
+  a.n_obs = rb->E * int64_t(rb->D);
+  a.timestep = timestep;
+  a.t_seen = rb->t_seen;
+  a.E = rb->E;
+  a.begin = 1;
+  return rollout_store("launch k_rollout_store (begin)", rb, a, stream);
+}
+
+int anm_rollout_add(const anm_rollout* rb, int64_t k, const void* obs, const void* reward, const uint8_t* terminated,
+                    const uint8_t* truncated, const int32_t* timestep, void* stream) {
+  if (int rc = rollout_args("anm_rollout_add", rb)) return rc;
+  if (k < 0 || k >= rb->T) return fail("anm_rollout_add: k is outside [0, T)");
+  if (!rb->obs || !rb->rewards || !rb->flags || !rb->t_seen) return fail("anm_rollout_add: the buffers obs, rewards, flags and t_seen must be set");
+  if (!obs || !reward || !terminated || !timestep) return fail("anm_rollout_add: obs, reward, terminated and timestep must be set");
+  const size_t io = rb->io_dtype == ANM_IO_F32 ? 4 : 8;
+  rollout::StoreArgs a{};
+  a.src_obs = obs;
+  a.n_obs = rb->E * int64_t(rb->D);
+  a.dst_obs = static_cast<char*>(rb->obs) + size_t(k + 1) * size_t(a.n_obs) * io;
+  a.reward = reward;
+  a.dst_reward = static_cast<char*>(rb->rewards) + size_t(k) * size_t(rb->E) * io;
+  a.terminated = terminated;
+  a.truncated = truncated;
+  a.timestep = timestep;
+  a.flags = rb->flags + k * rb->E;
+  a.t_seen = rb->t_seen;
+  a.E = rb->E;
+  a.begin = 0;
+  return rollout_store("launch k_rollout_store", rb, a, stream);
+}
+
+int anm_rollout_gae(const anm_rollout* rb, void* stream) {
+  if (int rc = rollout_args("anm_rollout_gae", rb)) return rc;
+  if (!rb->rewards || !rb->values || !rb->flags || !rb->advantages || !rb->returns)
+    return fail("anm_rollout_gae: the buffers rewards, values, flags, advantages and returns must be set");
+  rollout::GaeArgs a{};
+  a.rewards = rb->rewards;
+  a.values = rb->values;
+  a.flags = rb->flags;
+  a.advantages = rb->advantages;
+  a.returns = rb->returns;
+  a.T = rb->T;
+  a.E = rb->E;
+  a.g = rb->gamma;
+  const double gl = rb->gamma * rb->gae_lambda;   // (one double product, formed once: rule 3)
+  a.gl = gl;
+  const unsigned grid = unsigned((rb->E + rollout::GAE_LANES - 1) / rollout::GAE_LANES);
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const bool r32 = rb->io_dtype == ANM_IO_F32, v32 = rb->value_dtype == ANM_IO_F32;
+  auto go = [&](auto kernel) { return launch("launch k_rollout_gae", kernel, grid, rollout::GAE_LANES, 0, s, a); };
+  return r32 ? (v32 ? go(rollout::k_rollout_gae<true, true>) : go(rollout::k_rollout_gae<true, false>))
+             : (v32 ? go(rollout::k_rollout_gae<false, true>) : go(rollout::k_rollout_gae<false, false>));
+}
+
+int anm_rollout_adv_norm(const anm_rollout* rb, void* stream) {
+  if (int rc = rollout_args("anm_rollout_adv_norm", rb)) return rc;
+  if (!rb->advantages || !rb->flags || !rb->adv_norm || !rb->stats)
+    return fail("anm_rollout_adv_norm: the buffers advantages, flags, adv_norm and stats must be set");
+  if (rb->T > rollout::MAX_LEAVES / rb->E) return fail("anm_rollout_adv_norm: T E is above 67 108 864 (4096 slabs of 16 384 slots)");
+  rollout::AdvArgs a{};
+  a.advantages = rb->advantages;
+  a.flags = rb->flags;
+  a.adv_norm = rb->adv_norm;
+  a.N = rb->T * rb->E;
+  a.range = rollout::slab_range(a.N);
+  const int64_t n_slabs = (a.N + a.range - 1) / a.range;
+  if (!rb->slabs || rb->n_slab_doubles < n_slabs * rollout::SLAB)
+    return fail("anm_rollout_adv_norm: the slab buffer is too short: 3 ceil(T E / range) doubles, range = 1024 doubled while that "
+                "leaves more than 4096 slabs");
+  a.slabs = rb->slabs;
+  a.n_slabs = int(n_slabs);
+  a.stats = rb->stats;
+  a.eps = rb->eps;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const bool v32 = rb->value_dtype == ANM_IO_F32;
+  if (int rc = v32 ? launch("launch k_adv_partial", rollout::k_adv_partial<true>, unsigned(n_slabs), rollout::ADV_LANES, 0, s, a)
+                   : launch("launch k_adv_partial", rollout::k_adv_partial<false>, unsigned(n_slabs), rollout::ADV_LANES, 0, s, a))
+    return rc;
+  if (int rc = launch("launch k_adv_finish", rollout::k_adv_finish, 1, rollout::ADV_LANES, 0, s, a)) return rc;
+  const unsigned grid = unsigned((a.N + rollout::ADV_LANES - 1) / rollout::ADV_LANES);
+  return v32 ? launch("launch k_adv_apply", rollout::k_adv_apply<true>, grid, rollout::ADV_LANES, 0, s, a)
+             : launch("launch k_adv_apply", rollout::k_adv_apply<false>, grid, rollout::ADV_LANES, 0, s, a);
 }
 
 int anm_model_bind_view(anm_model* m, const anm_batch_view* v) {

@@ -379,6 +379,43 @@ int anm_model_io_norm_update(anm_model* m, int64_t num_envs, const double* obs, 
                              const uint8_t* truncated, const int32_t* timestep, const anm_io_norm* norm, void* stream);
 int anm_model_io_norm_tables(anm_model* m, const anm_io_norm* norm, void* stream);
 
+/* The device rollout buffer of an on-policy loop (gym_anm_amd/rollout.py has the semantics): T slots over E environments,
+ * filled in stream order behind the step calls, then GAE(lambda) and the advantage normalisation, every result with the same
+ * bits on every run.  Model-free: no anm_model is involved, every pointer is a caller-owned DEVICE pointer.
+ *   obs         [T + 1, E, D]  io dtype      rewards  [T, E]      io dtype      flags  uint8 [T, E]
+ *   values      [T + 1, E]     value dtype   advantages, returns, adv_norm  [T, E]  value dtype
+ *   t_seen      int32 [E]: the timestep last seen (rule 2)
+ *   stats       8 x 8 bytes: float64 n, mean, var (Bessel), std, std + eps, 1.0 when normalised | int64 n_valid, n_norm_skipped
+ *   slabs       double [n_slab_doubles], at least 3 ceil(T E / range), range = 1024 doubled while that leaves more than 4096
+ *               slabs (at most 16 384); scratch between the launches of anm_rollout_adv_norm
+ * io_dtype / value_dtype: ANM_IO_F64 | ANM_IO_F32.  flags = valid | terminated << 1 | truncated << 2.  The caller writes
+ * values (all T + 1 slots) before anm_rollout_gae; actions and log-probabilities are the caller's own arrays.
+ * anm_rollout_begin: obs[0] <- obs, t_seen <- timestep (one launch).  anm_rollout_add, after step call k: obs[k + 1], rewards[k],
+ * flags[k], t_seen from what the call stored (one launch; `truncated` may be NULL).  anm_rollout_gae: advantages and returns
+ * (one launch).  anm_rollout_adv_norm: the moments over valid slots by one fixed tree, stats and adv_norm (three launches).
+ * Nothing allocates or synchronises with the host; all of it can be captured into a graph.
+ * Refused: a null struct or a null array that the call reads or writes; T, E or D < 1; a dtype code other than the two; k
+ * outside [0, T); gamma or gae_lambda outside [0, 1]; eps not finite or not > 0; a slab buffer that is too short; T E above
+ * 67 108 864 (4096 slabs of 16 384 slots; anm_rollout_adv_norm only). */
+typedef struct anm_rollout {
+  void *obs, *rewards, *values;
+  uint8_t* flags;
+  void *advantages, *returns, *adv_norm;
+  int32_t* t_seen;
+  double* stats;
+  double* slabs;
+  int64_t n_slab_doubles;
+  int64_t T, E;
+  int32_t D;
+  int32_t io_dtype, value_dtype;
+  double gamma, gae_lambda, eps;
+} anm_rollout;
+int anm_rollout_begin(const anm_rollout* rb, const void* obs, const int32_t* timestep, void* stream);
+int anm_rollout_add(const anm_rollout* rb, int64_t k, const void* obs, const void* reward, const uint8_t* terminated,
+                    const uint8_t* truncated, const int32_t* timestep, void* stream);
+int anm_rollout_gae(const anm_rollout* rb, void* stream);
+int anm_rollout_adv_norm(const anm_rollout* rb, void* stream);
+
 /* The reference's solver returns the final mismatch next to the iteration count (`diff` of
  * _newton_raphson_sparse, solve_load_flow.py:176-226: ||F(x)||inf of the iterate it stopped at).  With an array bound here
  * (DEVICE double [num_envs], caller-owned, alive while bound; NULL unbinds) anm_transition_f64 and anm_reset_f64 write it per
