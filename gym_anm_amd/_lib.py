@@ -158,6 +158,18 @@ class Rollout(C.Structure):
                 ("value_dtype", C.c_int32), ("gamma", C.c_double), ("gae_lambda", C.c_double), ("eps", C.c_double)]  # fmt: skip
 
 
+class Minibatch(C.Structure):
+    """anm_minibatch: the sources, scratch, state and destinations of the minibatch sampler (anm_minibatch_prepare / _gather;
+    minibatch.py)"""
+    _fields_ = [(k, C.c_void_p) for k in ["obs", "actions", "logp", "values", "returns", "adv", "flags", "index", "counts",
+                                          "offsets"]] + \
+               [("n_counts", C.c_int64), ("state", C.c_void_p)] + \
+               [(k, C.c_void_p) for k in ["mb_obs", "mb_actions", "mb_logp", "mb_values", "mb_returns", "mb_adv", "mb_weight",
+                                          "mb_slot"]] + \
+               [("T", C.c_int64), ("E", C.c_int64), ("D", C.c_int32), ("A", C.c_int32), ("B", C.c_int64), ("io_dtype", C.c_int32),
+                ("value_dtype", C.c_int32), ("seed", C.c_uint64)]  # fmt: skip
+
+
 class SolverOpts(C.Structure):
     """anm_solver_opts.  row_continuation: 0 the library's policy, 1 always rows, -1 always lane groups, 2 the policy with
     the row passes on one lane per bus even where the topology has a pair layout (include/anm_mi355x.h)"""
@@ -215,6 +227,8 @@ ABI = {
     "anm_rollout_add": (C.c_int, [C.POINTER(Rollout), C.c_int64, _P, _P, _P, _P, _P, _P]),
     "anm_rollout_gae": (C.c_int, [C.POINTER(Rollout), _P]),
     "anm_rollout_adv_norm": (C.c_int, [C.POINTER(Rollout), _P]),
+    "anm_minibatch_prepare": (C.c_int, [C.POINTER(Minibatch), _P]),
+    "anm_minibatch_gather": (C.c_int, [C.POINTER(Minibatch), C.c_int64, C.c_int64, _P]),
     "anm_model_bind_nr_diff": (C.c_int, [C.c_void_p, _P]),
     "anm_model_bind_nr_start": (C.c_int, [C.c_void_p, _P]),
     "anm_model_bind_view": (C.c_int, [C.c_void_p, C.POINTER(BatchView)]),
@@ -245,7 +259,7 @@ ABI = {
 
 # entry points of modes that live in the GPU kernels alone: a backend that is not the GPU library (the host test double)
 # may lack them -- the host layer refuses those modes on such a backend before it would call them
-GPU_ONLY = ("anm_model_set_io", "anm_model_set_io_map", "anm_model_io_norm_update", "anm_model_io_norm_tables", "anm_rollout_begin", "anm_rollout_add", "anm_rollout_gae", "anm_rollout_adv_norm", "anm_mpc_act_stream_f64", "anm_mpc_act_chain_f64", "anm_mpc_act_expect_f64", "anm_test_row_dpp")
+GPU_ONLY = ("anm_model_set_io", "anm_model_set_io_map", "anm_model_io_norm_update", "anm_model_io_norm_tables", "anm_rollout_begin", "anm_rollout_add", "anm_rollout_gae", "anm_rollout_adv_norm", "anm_minibatch_prepare", "anm_minibatch_gather", "anm_mpc_act_stream_f64", "anm_mpc_act_chain_f64", "anm_mpc_act_expect_f64", "anm_test_row_dpp")
 
 
 def bind(cdll, optional=()):

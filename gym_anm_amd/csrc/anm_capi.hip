@@ -26,6 +26,7 @@
 #include "anm_env_ops.hpp"
 #include "anm_io_norm.hpp"
 #include "anm_rollout.hpp"
+#include "anm_minibatch.hpp"
 #include "anm_pack.hpp"
 #include "anm_radial.hpp"
 #include "anm_mesh.hpp"
@@ -1263,6 +1264,96 @@ int anm_rollout_adv_norm(const anm_rollout* rb, void* stream) {
   const unsigned grid = unsigned((a.N + rollout::ADV_LANES - 1) / rollout::ADV_LANES);
   return v32 ? launch("launch k_adv_apply", rollout::k_adv_apply<true>, grid, rollout::ADV_LANES, 0, s, a)
              : launch("launch k_adv_apply", rollout::k_adv_apply<false>, grid, rollout::ADV_LANES, 0, s, a);
+}
+
+namespace {
+
+// what both entry points of the minibatch sampler check; n_ranges: the ranges of the plan
+int minibatch_args(const char* who, const anm_minibatch* mb, int64_t& n_ranges) {
+  const std::string w = who;
+  if (!mb) return fail((w + ": null anm_minibatch").c_str());
+  if (mb->T < 1 || mb->E < 1 || mb->D < 1 || mb->A < 1 || mb->B < 1) return fail((w + ": T, E, D, A and B must be at least 1").c_str());
+  if (mb->T > rollout::MAX_LEAVES || mb->E > rollout::MAX_LEAVES || mb->T > rollout::MAX_LEAVES / mb->E)
+    return fail((w + ": T E is above 67 108 864 (4096 ranges of 16 384 slots)").c_str());
+  if (mb->D > (1 << 20) || mb->A > (1 << 20) || mb->B > (int64_t(1) << 30)) return fail((w + ": D or A above 2^20, or B above 2^30").c_str());
+  for (int32_t code : {mb->io_dtype, mb->value_dtype})
+    if (code != ANM_IO_F64 && code != ANM_IO_F32) return fail((w + ": io_dtype and value_dtype must be ANM_IO_F64 or ANM_IO_F32").c_str());
+  if (!mb->index || !mb->state) return fail((w + ": index and state must be set").c_str());
+  const int64_t N = mb->T * mb->E, range = rollout::slab_range(N);
+  n_ranges = (N + range - 1) / range;
+  if (!mb->counts || !mb->offsets || mb->n_counts < n_ranges)
+    return fail((w + ": the counts buffer is too short: counts and offsets take ceil(T E / range) int32 each, range = 1024 doubled "
+                     "while that leaves more than 4096 ranges").c_str());
+  return 0;
+}
+
+}  // namespace
+
+int anm_minibatch_prepare(const anm_minibatch* mb, void* stream) {
+  int64_t n_ranges = 0;
+  if (int rc = minibatch_args("anm_minibatch_prepare", mb, n_ranges)) return rc;
+  if (!mb->flags) return fail("anm_minibatch_prepare: flags must be set");
+  minibatch::PrepArgs a{};
+  a.flags = mb->flags;
+  a.index = mb->index;
+  a.counts = mb->counts;
+  a.offsets = mb->offsets;
+  a.state = reinterpret_cast<long long*>(mb->state);
+  a.N = mb->T * mb->E;
+  a.range = rollout::slab_range(a.N);
+  a.n_ranges = int(n_ranges);
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  if (int rc = launch("launch k_mb_count", minibatch::k_mb_count, unsigned(n_ranges), minibatch::LANES, 0, s, a)) return rc;
+  if (int rc = launch("launch k_mb_scan", minibatch::k_mb_scan, 1, minibatch::LANES, 0, s, a)) return rc;
+  return launch("launch k_mb_scatter", minibatch::k_mb_scatter, unsigned(n_ranges), minibatch::LANES, 0, s, a);
+}
+
+int anm_minibatch_gather(const anm_minibatch* mb, int64_t m, int64_t ep, void* stream) {
+  int64_t n_ranges = 0;
+  if (int rc = minibatch_args("anm_minibatch_gather", mb, n_ranges)) return rc;
+  if (!mb->obs || !mb->actions || !mb->logp || !mb->values || !mb->returns || !mb->adv)
+    return fail("anm_minibatch_gather: the sources obs, actions, logp, values, returns and adv must be set");
+  if (!mb->mb_obs || !mb->mb_actions || !mb->mb_logp || !mb->mb_values || !mb->mb_returns || !mb->mb_adv || !mb->mb_weight || !mb->mb_slot)
+    return fail("anm_minibatch_gather: the eight destinations must be set");
+  const int64_t N = mb->T * mb->E;
+  if (m < 0 || m > (N - 1) / mb->B) return fail("anm_minibatch_gather: m is outside [0, ceil(T E / B))");   // (m B >= T E)
+  if (ep < 0 || ep > int64_t(0xFFFFFFFFll)) return fail("anm_minibatch_gather: ep is outside [0, 2^32)");
+  minibatch::GatherArgs a{};
+  a.obs = mb->obs;
+  a.actions = mb->actions;
+  a.logp = mb->logp;
+  a.values = mb->values;
+  a.returns = mb->returns;
+  a.adv = mb->adv;
+  a.index = mb->index;
+  a.state = reinterpret_cast<const long long*>(mb->state);
+  a.mb_obs = mb->mb_obs;
+  a.mb_actions = mb->mb_actions;
+  a.mb_logp = mb->mb_logp;
+  a.mb_values = mb->mb_values;
+  a.mb_returns = mb->mb_returns;
+  a.mb_adv = mb->mb_adv;
+  a.mb_weight = mb->mb_weight;
+  a.mb_slot = mb->mb_slot;
+  a.N = N;
+  a.first = m * mb->B;
+  a.B = int32_t(mb->B);
+  a.D = mb->D;
+  a.A = mb->A;
+  a.dq = minibatch::LANES / mb->D;
+  a.dr = minibatch::LANES % mb->D;
+  a.dm = (65536 + mb->D - 1) / mb->D;
+  a.aq = minibatch::LANES / mb->A;
+  a.ar = minibatch::LANES % mb->A;
+  a.am = (65536 + mb->A - 1) / mb->A;
+  a.ep = uint32_t(ep);
+  a.seed = mb->seed;
+  const unsigned grid = unsigned((mb->B + minibatch::TILE - 1) / minibatch::TILE);
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const bool i32 = mb->io_dtype == ANM_IO_F32, v32 = mb->value_dtype == ANM_IO_F32;
+  auto go = [&](auto kernel) { return launch("launch k_mb_gather", kernel, grid, minibatch::LANES, 0, s, a); };
+  return i32 ? (v32 ? go(minibatch::k_mb_gather<true, true>) : go(minibatch::k_mb_gather<true, false>))
+             : (v32 ? go(minibatch::k_mb_gather<false, true>) : go(minibatch::k_mb_gather<false, false>));
 }
 
 int anm_model_bind_view(anm_model* m, const anm_batch_view* v) {

@@ -57,7 +57,8 @@ IEEE leaves to the machine.
    The kernels partition the flat index into aligned power-of-two ranges (``slab_range``); IEEE addition commutes, so the
    result does not depend on that grid.  ``T * E`` is at most 67 108 864 (4096 ranges of 16 384 slots).
 5. Not served: ``MixedBatchedANMEnv``, batch views, a backend other than the GPU library, and a cross-rank merge of the
-   moments (a sharded run normalises per rank).
+   moments (a sharded run normalises per rank).  Shuffled minibatches of the valid slots are ``RolloutBuffer.sampler``
+   (``minibatch.py``); the loss stays with the caller.
 """
 
 from __future__ import annotations
@@ -324,6 +325,14 @@ class RolloutBuffer:
             rc = lib.anm_rollout_adv_norm(self._ref, stream)
             if rc != 0:
                 self._backend.check(rc, "anm_rollout_adv_norm")
+
+    def sampler(self, batch_size, seed=0, advantage="norm"):
+        """A :class:`~gym_anm_amd.minibatch.MinibatchSampler` over this buffer: shuffled minibatches of ``batch_size`` rows
+        drawn from the valid slots (``minibatch.py``); ``advantage``: ``"norm"`` reads ``adv_norm``, ``"raw"`` ``advantages``.
+        It allocates everything it needs once, here."""
+        from .minibatch import MinibatchSampler
+
+        return MinibatchSampler(self, batch_size, seed=seed, advantage=advantage)
 
     @property
     def valid(self):

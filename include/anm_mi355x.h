@@ -416,6 +416,42 @@ int anm_rollout_add(const anm_rollout* rb, int64_t k, const void* obs, const voi
 int anm_rollout_gae(const anm_rollout* rb, void* stream);
 int anm_rollout_adv_norm(const anm_rollout* rb, void* stream);
 
+/* The minibatch sampler of the rollout buffer (gym_anm_amd/minibatch.py has the semantics): the valid slots of a finished
+ * rollout compacted into an index, and shuffled minibatches of fixed shape gathered through a keyed permutation of that
+ * index.  Model-free like anm_rollout; every pointer is a caller-owned DEVICE pointer.
+ *   sources       obs [T (+ 1), E, D] and actions [T, E, A] in the io dtype; logp, values, returns, adv [T, E] in the value
+ *                 dtype (adv: the advantage source the caller chose, adv_norm or advantages); flags uint8 [T, E]
+ *   index         int32 [T E]: the flat indices k E + e of the valid slots, ascending, then -1
+ *   counts, offsets  int32 [n_counts] each, n_counts at least ceil(T E / range), range = 1024 doubled while that leaves more
+ *                 than 4096 ranges; scratch between the launches of anm_minibatch_prepare
+ *   state         int64 [2]: n_valid, rollout_count (zeroed by the caller once; every prepare adds 1 to the count)
+ *   destinations  mb_obs [B, D], mb_actions [B, A] io dtype; mb_logp, mb_values, mb_returns, mb_adv, mb_weight [B] value dtype;
+ *                 mb_slot int32 [B]
+ * anm_minibatch_prepare: index, n_valid and rollout_count from flags (three launches).  anm_minibatch_gather: minibatch m of
+ * epoch ep -- row i is the slot index[perm(m B + i)] copied bit for bit with weight 1, or, from position n_valid on, all-zero
+ * words with weight 0 and slot -1 (one launch; n_valid and rollout_count are read on the device).  Nothing allocates or
+ * synchronises with the host; all of it can be captured into a graph.
+ * Refused: a null struct or a null array; T, E, D, A or B < 1; T E above 67 108 864 (4096 ranges of 16 384 slots); D or A
+ * above 2^20; B above 2^30; a counts buffer that is too short; a dtype code other than the two; m < 0 or m B >= T E; ep < 0
+ * or ep >= 2^32. */
+typedef struct anm_minibatch {
+  const void *obs, *actions, *logp, *values, *returns, *adv;
+  const uint8_t* flags;
+  int32_t* index;
+  int32_t *counts, *offsets;
+  int64_t n_counts;
+  int64_t* state;
+  void *mb_obs, *mb_actions, *mb_logp, *mb_values, *mb_returns, *mb_adv, *mb_weight;
+  int32_t* mb_slot;
+  int64_t T, E;
+  int32_t D, A;
+  int64_t B;
+  int32_t io_dtype, value_dtype;
+  uint64_t seed;
+} anm_minibatch;
+int anm_minibatch_prepare(const anm_minibatch* mb, void* stream);
+int anm_minibatch_gather(const anm_minibatch* mb, int64_t m, int64_t ep, void* stream);
+
 /* The reference's solver returns the final mismatch next to the iteration count (`diff` of
  * _newton_raphson_sparse, solve_load_flow.py:176-226: ||F(x)||inf of the iterate it stopped at).  With an array bound here
  * (DEVICE double [num_envs], caller-owned, alive while bound; NULL unbinds) anm_transition_f64 and anm_reset_f64 write it per
