@@ -170,6 +170,15 @@ class Minibatch(C.Structure):
                 ("value_dtype", C.c_int32), ("seed", C.c_uint64)]  # fmt: skip
 
 
+class Policy(C.Structure):
+    """anm_policy: the flat parameter vector, the shape, the noise key and the side outputs of the Gaussian MLP policy
+    (anm_policy_act; policy.py)"""
+    _fields_ = [("params", C.c_void_p), ("n_params", C.c_int64), ("D", C.c_int32), ("A", C.c_int32), ("n_hidden", C.c_int32),
+                ("hidden", C.c_int32 * 3), ("activation", C.c_int32), ("deterministic", C.c_int32), ("seed", C.c_uint64),
+                ("env_offset", C.c_uint64), ("reset_count", C.c_void_p), ("timestep", C.c_void_p), ("noise", C.c_void_p),
+                ("std", C.c_void_p), ("E", C.c_int64), ("io_dtype", C.c_int32), ("value_dtype", C.c_int32)]
+
+
 class SolverOpts(C.Structure):
     """anm_solver_opts.  row_continuation: 0 the library's policy, 1 always rows, -1 always lane groups, 2 the policy with
     the row passes on one lane per bus even where the topology has a pair layout (include/anm_mi355x.h)"""
@@ -229,6 +238,7 @@ ABI = {
     "anm_rollout_adv_norm": (C.c_int, [C.POINTER(Rollout), _P]),
     "anm_minibatch_prepare": (C.c_int, [C.POINTER(Minibatch), _P]),
     "anm_minibatch_gather": (C.c_int, [C.POINTER(Minibatch), C.c_int64, C.c_int64, _P]),
+    "anm_policy_act": (C.c_int, [C.POINTER(Policy), _P, _P, _P, _P, _P]),
     "anm_model_bind_nr_diff": (C.c_int, [C.c_void_p, _P]),
     "anm_model_bind_nr_start": (C.c_int, [C.c_void_p, _P]),
     "anm_model_bind_view": (C.c_int, [C.c_void_p, C.POINTER(BatchView)]),
@@ -259,7 +269,7 @@ ABI = {
 
 # entry points of modes that live in the GPU kernels alone: a backend that is not the GPU library (the host test double)
 # may lack them -- the host layer refuses those modes on such a backend before it would call them
-GPU_ONLY = ("anm_model_set_io", "anm_model_set_io_map", "anm_model_io_norm_update", "anm_model_io_norm_tables", "anm_rollout_begin", "anm_rollout_add", "anm_rollout_gae", "anm_rollout_adv_norm", "anm_minibatch_prepare", "anm_minibatch_gather", "anm_mpc_act_stream_f64", "anm_mpc_act_chain_f64", "anm_mpc_act_expect_f64", "anm_test_row_dpp")
+GPU_ONLY = ("anm_model_set_io", "anm_model_set_io_map", "anm_model_io_norm_update", "anm_model_io_norm_tables", "anm_rollout_begin", "anm_rollout_add", "anm_rollout_gae", "anm_rollout_adv_norm", "anm_minibatch_prepare", "anm_minibatch_gather", "anm_policy_act", "anm_mpc_act_stream_f64", "anm_mpc_act_chain_f64", "anm_mpc_act_expect_f64", "anm_test_row_dpp")
 
 
 def bind(cdll, optional=()):

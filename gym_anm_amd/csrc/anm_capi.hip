@@ -27,6 +27,7 @@
 #include "anm_io_norm.hpp"
 #include "anm_rollout.hpp"
 #include "anm_minibatch.hpp"
+#include "anm_policy.hpp"
 #include "anm_pack.hpp"
 #include "anm_radial.hpp"
 #include "anm_mesh.hpp"
@@ -1354,6 +1355,108 @@ int anm_minibatch_gather(const anm_minibatch* mb, int64_t m, int64_t ep, void* s
   auto go = [&](auto kernel) { return launch("launch k_mb_gather", kernel, grid, minibatch::LANES, 0, s, a); };
   return i32 ? (v32 ? go(minibatch::k_mb_gather<true, true>) : go(minibatch::k_mb_gather<true, false>))
              : (v32 ? go(minibatch::k_mb_gather<false, true>) : go(minibatch::k_mb_gather<false, false>));
+}
+
+namespace {
+
+// the layers of one net of the flat parameter vector from offset `at` on (policy.layout): W [K, N] then b [N] per layer
+void policy_net(policy::Net& net, const anm_policy* pi, int n_out, int32_t& at) {
+  net.n_layers = pi->n_hidden + 1;
+  int K = pi->D;
+  for (int i = 0; i < net.n_layers; ++i) {
+    const int N = i < pi->n_hidden ? pi->hidden[i] : n_out;
+    net.K[i] = K;
+    net.N[i] = N;
+    net.w[i] = at;
+    at += K * N;
+    net.b[i] = at;
+    at += N;
+    K = N;
+  }
+}
+
+}  // namespace
+
+int anm_policy_act(const anm_policy* pi, const void* obs, void* actions, void* values, void* logp, void* stream) {
+  if (!pi) return fail("anm_policy_act: null anm_policy");
+  if (pi->D < 1 || pi->D > policy::MAX_D) return fail("anm_policy_act: D is outside [1, 256]");
+  if (pi->A < 1 || pi->A > policy::MAX_A) return fail("anm_policy_act: A is outside [1, 64]");
+  if (pi->n_hidden < 1 || pi->n_hidden > policy::MAX_HIDDEN) return fail("anm_policy_act: n_hidden is outside [1, 3]");
+  int H = 0;
+  for (int i = 0; i < pi->n_hidden; ++i) {
+    const int32_t h = pi->hidden[i];
+    if (h < policy::MIN_WIDTH || h > policy::MAX_WIDTH || h % 32 != 0)
+      return fail("anm_policy_act: a hidden width is not a multiple of 32 in [32, 256]");
+    H = h > H ? h : H;
+  }
+  if (pi->activation != policy::ACT_TANH && pi->activation != policy::ACT_RELU) return fail("anm_policy_act: activation must be ANM_POLICY_TANH or ANM_POLICY_RELU");
+  for (int32_t code : {pi->io_dtype, pi->value_dtype})
+    if (code != ANM_IO_F64 && code != ANM_IO_F32) return fail("anm_policy_act: io_dtype and value_dtype must be ANM_IO_F64 or ANM_IO_F32");
+  if (pi->E < 1 || pi->E > (int64_t(1) << 30)) return fail("anm_policy_act: E is outside [1, 2^30]");
+  policy::Args a{};
+  int32_t at = 0;
+  policy_net(a.actor, pi, pi->A, at);
+  policy_net(a.critic, pi, 1, at);
+  a.log_std = at;
+  at += pi->A;
+  if (pi->n_params != at) return fail("anm_policy_act: n_params is not the size of the layout (actor, critic, log_std)");
+  const bool critic_only = !actions && !logp;
+  if (!pi->params || !obs || !values) return fail("anm_policy_act: params, obs and values must be set");
+  if (!critic_only) {
+    if (!actions || !logp) return fail("anm_policy_act: actions and logp must both be set (or both NULL: the critic alone)");
+    if (!pi->noise || !pi->std) return fail("anm_policy_act: noise and std must be set");
+    if (!pi->deterministic && (!pi->reset_count || !pi->timestep)) return fail("anm_policy_act: reset_count and timestep must be set");
+  }
+  const int wide = H > pi->A ? H : pi->A;
+  a.S = (pi->D > wide ? pi->D : wide) | 1;
+  a.SA = pi->A | 1;
+  int waves = policy::MAX_WAVES;
+  while (waves >= 1 && policy::lds_floats(at, a.S, a.SA, waves) * 4 > policy::LDS_BYTES) waves >>= 1;
+  if (waves < 1) return fail("anm_policy_act: the network does not fit the LDS plan (P + 96 + 32 (2 (max(D, H, A)|1) + (A|1)) floats above 40 960)");
+  a.params = pi->params;
+  a.n_params = at;
+  a.D = pi->D;
+  a.A = pi->A;
+  a.activation = pi->activation;
+  a.deterministic = pi->deterministic ? 1 : 0;
+  a.critic_only = critic_only ? 1 : 0;
+  a.logp0 = float(-0.5 * double(pi->A) * std::log(2.0 * 3.141592653589793));   // (formed in double, rounded once: rule 6)
+  a.seed = pi->seed;
+  a.env_offset = pi->env_offset;
+  a.reset_count = pi->reset_count;
+  a.timestep = pi->timestep;
+  a.obs = obs;
+  a.actions = actions;
+  a.values = values;
+  a.logp = logp;
+  a.noise = pi->noise;
+  a.std = pi->std;
+  a.E = pi->E;
+  const int tile = waves * policy::ROWS;
+  const size_t lds = size_t(policy::lds_floats(at, a.S, a.SA, waves)) * 4;
+  a.vec4 = reinterpret_cast<uintptr_t>(pi->params) % 16 == 0 ? 1 : 0;
+  // a workgroup stages the parameters once and then takes tiles in a loop: no more workgroups than the device holds at once
+  static int n_cu = 0;
+  if (n_cu == 0) {
+    int dev = 0, n = 0;
+    n_cu = hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && n > 0 ? n : -1;
+  }
+  const int64_t n_tiles = (pi->E + tile - 1) / tile;
+  const int64_t resident = n_cu > 0 ? int64_t(n_cu) * int64_t(policy::LDS_BYTES / lds) : n_tiles;
+  const unsigned grid = unsigned(n_tiles < resident ? n_tiles : resident);
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const bool i32 = pi->io_dtype == ANM_IO_F32, v32 = pi->value_dtype == ANM_IO_F32;
+  static bool raised[4] = {false, false, false, false};   // (the default limit of dynamic LDS is 64 KiB; raised once per kernel)
+  auto go = [&](auto kernel, int which) {
+    if (!raised[which]) {
+      hipError_t e = hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, policy::LDS_BYTES);
+      if (e != hipSuccess) return fail_hip(e, "anm_policy_act: hipFuncSetAttribute");
+      raised[which] = true;
+    }
+    return launch("launch k_policy", kernel, grid, unsigned(waves * 64), lds, s, a);
+  };
+  return i32 ? (v32 ? go(policy::k_policy<true, true>, 0) : go(policy::k_policy<true, false>, 1))
+             : (v32 ? go(policy::k_policy<false, true>, 2) : go(policy::k_policy<false, false>, 3));
 }
 
 int anm_model_bind_view(anm_model* m, const anm_batch_view* v) {

@@ -228,10 +228,10 @@ class RolloutBuffer:
 
         buf.begin(obs)                                  # one launch
         for k in range(T):
-            # the policy writes buf.actions[k], buf.values[k], buf.logp[k] in place (contiguous slot views)
-            out = env.step(buf.actions[k])
+            pi.act(buf.obs[k], buf.actions[k], buf.values[k], buf.logp[k])     # one launch (policy.py); or any policy that
+            out = env.step(buf.actions[k])                                     # writes these contiguous slot views in place
             buf.add(*out[:4])                           # one launch; reads env.timestep
-        # the policy writes buf.values[T]
+        pi.value(buf.obs[T], buf.values[T])             # one launch: the critic alone
         buf.finish(normalize=True)                      # the GAE launch (+ three for rule 4)
 
     ``begin()`` without an argument continues from ``obs[T]``.  ``begin``, ``add`` and ``finish`` allocate nothing, do not

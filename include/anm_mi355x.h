@@ -452,6 +452,42 @@ typedef struct anm_minibatch {
 int anm_minibatch_prepare(const anm_minibatch* mb, void* stream);
 int anm_minibatch_gather(const anm_minibatch* mb, int64_t m, int64_t ep, void* stream);
 
+/* The diagonal-Gaussian MLP actor-critic of an on-policy loop (gym_anm_amd/policy.py has the semantics): the observation rows
+ * through an actor MLP D -> hidden -> A and a critic MLP D -> hidden -> 1, a Gaussian sample with a state-independent log_std,
+ * its log-probability and the value, in ONE launch on the f32 matrix cores.  Model-free like anm_rollout; every pointer is a
+ * caller-owned DEVICE pointer.
+ *   params        float32 [n_params], one flat vector: the actor's layers in order, each W [K, N] row-major then b [N]; the
+ *                 critic's layers the same way; then log_std [A].  Read at every call: an optimiser steps it in place
+ *   reset_count, timestep  int32 [E]: the environment's own counters, which key the noise together with seed and
+ *                 env_offset + e (not read when deterministic != 0)
+ *   noise         float32 [E, A]: the standard-normal draws of the call (zeros when deterministic);  std  float32 [A]: exp(log_std)
+ *   obs [E, D] and actions [E, A] in io_dtype; values [E] and logp [E] in value_dtype (ANM_IO_F64 | ANM_IO_F32)
+ * anm_policy_act: actions = mean + std * noise, logp, values, noise and std (one launch).  With actions == NULL and
+ * logp == NULL: the critic alone, values only (one launch; noise and std are not touched).  Nothing allocates or synchronises
+ * with the host; it can be captured into a graph, and a replay draws fresh noise because the counters have moved.
+ * Refused: a null struct, params, obs or values; one of actions / logp set and the other not; noise, std (and, unless
+ * deterministic, reset_count, timestep) null when actions are asked for; D outside [1, 256]; A outside [1, 64]; n_hidden
+ * outside [1, 3]; a hidden width that is not a multiple of 32 in [32, 256]; an activation or dtype code other than the two;
+ * E outside [1, 2^30]; n_params that is not the size of the layout; a network that does not fit the LDS plan, n_params + 96 +
+ * 32 (2 (max(D, H, A) | 1) + (A | 1)) floats above 40 960 (H: the widest hidden layer). */
+#define ANM_POLICY_TANH 0
+#define ANM_POLICY_RELU 1
+typedef struct anm_policy {
+  const float* params;
+  int64_t n_params;
+  int32_t D, A;
+  int32_t n_hidden;
+  int32_t hidden[3];
+  int32_t activation;
+  int32_t deterministic;
+  uint64_t seed, env_offset;
+  const int32_t *reset_count, *timestep;
+  float *noise, *std;
+  int64_t E;
+  int32_t io_dtype, value_dtype;
+} anm_policy;
+int anm_policy_act(const anm_policy* pi, const void* obs, void* actions, void* values, void* logp, void* stream);
+
 /* The reference's solver returns the final mismatch next to the iteration count (`diff` of
  * _newton_raphson_sparse, solve_load_flow.py:176-226: ||F(x)||inf of the iterate it stopped at).  With an array bound here
  * (DEVICE double [num_envs], caller-owned, alive while bound; NULL unbinds) anm_transition_f64 and anm_reset_f64 write it per
