@@ -179,6 +179,14 @@ class Policy(C.Structure):
                 ("std", C.c_void_p), ("E", C.c_int64), ("io_dtype", C.c_int32), ("value_dtype", C.c_int32)]
 
 
+class Ppo(C.Structure):
+    """anm_ppo: one gathered minibatch, the outputs and the constants of the PPO gradient (anm_policy_ppo_grad; policy_grad.py)"""
+    _fields_ = [(k, C.c_void_p) for k in ["obs", "actions", "logp_old", "values_old", "returns", "adv", "weight", "grad", "partials",
+                                          "ratio", "logp", "values", "inv_std", "stats"]] + \
+               [("B", C.c_int64), ("rows_per_partial", C.c_int32), ("io_dtype", C.c_int32), ("value_dtype", C.c_int32),
+                ("clip", C.c_float), ("vf_coef", C.c_float), ("ent_coef", C.c_float), ("vf_clip", C.c_float)]  # fmt: skip
+
+
 class SolverOpts(C.Structure):
     """anm_solver_opts.  row_continuation: 0 the library's policy, 1 always rows, -1 always lane groups, 2 the policy with
     the row passes on one lane per bus even where the topology has a pair layout (include/anm_mi355x.h)"""
@@ -239,6 +247,7 @@ ABI = {
     "anm_minibatch_prepare": (C.c_int, [C.POINTER(Minibatch), _P]),
     "anm_minibatch_gather": (C.c_int, [C.POINTER(Minibatch), C.c_int64, C.c_int64, _P]),
     "anm_policy_act": (C.c_int, [C.POINTER(Policy), _P, _P, _P, _P, _P]),
+    "anm_policy_ppo_grad": (C.c_int, [C.POINTER(Policy), C.POINTER(Ppo), _P]),
     "anm_model_bind_nr_diff": (C.c_int, [C.c_void_p, _P]),
     "anm_model_bind_nr_start": (C.c_int, [C.c_void_p, _P]),
     "anm_model_bind_view": (C.c_int, [C.c_void_p, C.POINTER(BatchView)]),
@@ -269,7 +278,7 @@ ABI = {
 
 # entry points of modes that live in the GPU kernels alone: a backend that is not the GPU library (the host test double)
 # may lack them -- the host layer refuses those modes on such a backend before it would call them
-GPU_ONLY = ("anm_model_set_io", "anm_model_set_io_map", "anm_model_io_norm_update", "anm_model_io_norm_tables", "anm_rollout_begin", "anm_rollout_add", "anm_rollout_gae", "anm_rollout_adv_norm", "anm_minibatch_prepare", "anm_minibatch_gather", "anm_policy_act", "anm_mpc_act_stream_f64", "anm_mpc_act_chain_f64", "anm_mpc_act_expect_f64", "anm_test_row_dpp")
+GPU_ONLY = ("anm_model_set_io", "anm_model_set_io_map", "anm_model_io_norm_update", "anm_model_io_norm_tables", "anm_rollout_begin", "anm_rollout_add", "anm_rollout_gae", "anm_rollout_adv_norm", "anm_minibatch_prepare", "anm_minibatch_gather", "anm_policy_act", "anm_policy_ppo_grad", "anm_mpc_act_stream_f64", "anm_mpc_act_chain_f64", "anm_mpc_act_expect_f64", "anm_test_row_dpp")
 
 
 def bind(cdll, optional=()):

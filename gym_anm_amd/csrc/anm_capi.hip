@@ -28,6 +28,7 @@
 #include "anm_rollout.hpp"
 #include "anm_minibatch.hpp"
 #include "anm_policy.hpp"
+#include "anm_policy_grad.hpp"
 #include "anm_pack.hpp"
 #include "anm_radial.hpp"
 #include "anm_mesh.hpp"
@@ -1457,6 +1458,122 @@ int anm_policy_act(const anm_policy* pi, const void* obs, void* actions, void* v
   };
   return i32 ? (v32 ? go(policy::k_policy<true, true>, 0) : go(policy::k_policy<true, false>, 1))
              : (v32 ? go(policy::k_policy<false, true>, 2) : go(policy::k_policy<false, false>, 3));
+}
+
+int anm_policy_ppo_grad(const anm_policy* pi, const anm_ppo* job, void* stream) {
+  if (!pi) return fail("anm_policy_ppo_grad: null anm_policy");
+  if (!job) return fail("anm_policy_ppo_grad: null anm_ppo");
+  if (pi->D < 1 || pi->D > policy::MAX_D) return fail("anm_policy_ppo_grad: D is outside [1, 256]");
+  if (pi->A < 1 || pi->A > policy::MAX_A) return fail("anm_policy_ppo_grad: A is outside [1, 64]");
+  if (pi->n_hidden < 1 || pi->n_hidden > policy::MAX_HIDDEN) return fail("anm_policy_ppo_grad: n_hidden is outside [1, 3]");
+  int H = 0;
+  for (int i = 0; i < pi->n_hidden; ++i) {
+    const int32_t h = pi->hidden[i];
+    if (h < policy::MIN_WIDTH || h > policy::MAX_WIDTH || h % 32 != 0)
+      return fail("anm_policy_ppo_grad: a hidden width is not a multiple of 32 in [32, 256]");
+    H = h > H ? h : H;
+  }
+  if (pi->activation != policy::ACT_TANH && pi->activation != policy::ACT_RELU) return fail("anm_policy_ppo_grad: activation must be ANM_POLICY_TANH or ANM_POLICY_RELU");
+  for (int32_t code : {job->io_dtype, job->value_dtype})
+    if (code != ANM_IO_F64 && code != ANM_IO_F32) return fail("anm_policy_ppo_grad: io_dtype and value_dtype must be ANM_IO_F64 or ANM_IO_F32");
+  if (job->B < 1 || job->B > (int64_t(1) << 24)) return fail("anm_policy_ppo_grad: B is outside [1, 2^24]");
+  if (job->rows_per_partial < policy::ROWS || job->rows_per_partial % policy::ROWS != 0)
+    return fail("anm_policy_ppo_grad: rows_per_partial is not a positive multiple of 32");
+  if (!(job->clip > 0.0f) || !std::isfinite(job->clip)) return fail("anm_policy_ppo_grad: clip is not a positive finite number");
+  if (!std::isfinite(job->vf_coef) || !std::isfinite(job->ent_coef) || !std::isfinite(job->vf_clip))
+    return fail("anm_policy_ppo_grad: vf_coef, ent_coef and vf_clip must be finite (vf_clip < 0: off)");
+  ppo::Args a{};
+  int32_t at = 0;
+  policy_net(a.p.actor, pi, pi->A, at);
+  policy_net(a.p.critic, pi, 1, at);
+  a.p.log_std = at;
+  at += pi->A;
+  if (pi->n_params != at) return fail("anm_policy_ppo_grad: n_params is not the size of the layout (actor, critic, log_std)");
+  if (!pi->params || !job->obs || !job->actions || !job->logp_old || !job->returns || !job->adv || !job->weight)
+    return fail("anm_policy_ppo_grad: params and the minibatch's obs, actions, logp_old, returns, adv and weight must be set");
+  if (job->vf_clip >= 0.0f && !job->values_old) return fail("anm_policy_ppo_grad: values_old must be set when vf_clip is on");
+  if (!job->grad || !job->partials || !job->ratio || !job->logp || !job->values || !job->inv_std || !job->stats)
+    return fail("anm_policy_ppo_grad: grad, partials, ratio, logp, values, inv_std and stats must be set");
+  const int wide = H > pi->A ? H : pi->A;
+  a.p.S = ((pi->D > wide ? pi->D : wide) + 1) | 1;       // (one column more than the widest layer: the 1.0 of the bias)
+  a.SE = (pi->A + ppo::STATS) | 1;
+  a.n_tiles = pi->n_hidden + 2;
+  for (int net = 0; net < 2; ++net) {
+    const policy::Net& nn = net ? a.p.critic : a.p.actor;
+    int32_t* off = net ? a.wt_critic : a.wt_actor;
+    for (int i = 1; i < nn.n_layers; ++i) {
+      off[i] = a.wt_floats;
+      a.wt_floats += ((nn.N[i] + 1) & ~1) * nn.K[i];
+    }
+  }
+  int waves = ppo::MAX_WAVES;
+  while (waves >= 1 && ppo::lds_floats(at, a.wt_floats, a.n_tiles, a.p.S, a.SE, waves) * 4 > policy::LDS_BYTES) waves >>= 1;
+  if (waves < 1) return fail("anm_policy_ppo_grad: the network does not fit the backward LDS plan (policy_grad.grad_lds_floats above 40 960)");
+  a.p.params = pi->params;
+  a.p.n_params = at;
+  a.p.D = pi->D;
+  a.p.A = pi->A;
+  a.p.activation = pi->activation;
+  a.p.logp0 = float(-0.5 * double(pi->A) * std::log(2.0 * 3.141592653589793));
+  a.p.obs = job->obs;
+  a.p.vec4 = reinterpret_cast<uintptr_t>(pi->params) % 16 == 0 ? 1 : 0;
+  a.actions = job->actions;
+  a.logp_old = job->logp_old;
+  a.v_old = job->values_old;
+  a.returns = job->returns;
+  a.adv = job->adv;
+  a.weight = job->weight;
+  a.partials = job->partials;
+  a.ratio = job->ratio;
+  a.logp = job->logp;
+  a.values = job->values;
+  a.inv_std = job->inv_std;
+  a.B = job->B;
+  a.R = job->rows_per_partial;
+  a.clip_lo = 1.0f - job->clip;
+  a.clip_hi = 1.0f + job->clip;
+  a.vf_coef = job->vf_coef;
+  a.vf_clip = job->vf_clip < 0.0f ? -1.0f : job->vf_clip;
+  const size_t lds = size_t(ppo::lds_floats(at, a.wt_floats, a.n_tiles, a.p.S, a.SE, waves)) * 4;
+  static int n_cu = 0;
+  if (n_cu == 0) {
+    int dev = 0, n = 0;
+    n_cu = hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && n > 0 ? n : -1;
+  }
+  // a wavefront takes whole groups of rows_per_partial rows, a workgroup `waves` of them at a time; the grid decides only
+  // which wavefront computes a group, never what it computes
+  const int64_t G = (job->B + a.R - 1) / a.R;
+  const int64_t n_wg = (G + waves - 1) / waves;
+  const int64_t resident = n_cu > 0 ? int64_t(n_cu) * int64_t(policy::LDS_BYTES / lds) : n_wg;
+  const unsigned grid = unsigned(n_wg < resident ? n_wg : resident);
+  ppo::ReduceArgs r{};
+  r.partials = job->partials;
+  r.params = pi->params;
+  r.grad = job->grad;
+  r.stats = job->stats;
+  r.P = at;
+  r.A = pi->A;
+  r.log_std = a.p.log_std;
+  r.G = G;
+  r.vf_coef = job->vf_coef;
+  r.ent_coef = job->ent_coef;
+  r.ent_const = float(0.5 + 0.5 * std::log(2.0 * 3.141592653589793));
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const bool i32 = job->io_dtype == ANM_IO_F32, v32 = job->value_dtype == ANM_IO_F32;
+  static bool raised[4] = {false, false, false, false};
+  auto go = [&](auto kernel, int which) {
+    if (!raised[which]) {
+      hipError_t e = hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, policy::LDS_BYTES);
+      if (e != hipSuccess) return fail_hip(e, "anm_policy_ppo_grad: hipFuncSetAttribute");
+      raised[which] = true;
+    }
+    return launch("launch k_ppo_grad", kernel, grid, unsigned(waves * 64), lds, s, a);
+  };
+  const int rc = i32 ? (v32 ? go(ppo::k_ppo_grad<true, true>, 0) : go(ppo::k_ppo_grad<true, false>, 1))
+                     : (v32 ? go(ppo::k_ppo_grad<false, true>, 2) : go(ppo::k_ppo_grad<false, false>, 3));
+  if (rc != 0) return rc;
+  const unsigned rgrid = unsigned((at + ppo::REDUCE_THREADS - 1) / ppo::REDUCE_THREADS) + 1;
+  return launch("launch k_ppo_reduce", ppo::k_ppo_reduce, rgrid, ppo::REDUCE_THREADS, 0, s, r);
 }
 
 int anm_model_bind_view(anm_model* m, const anm_batch_view* v) {

@@ -51,8 +51,8 @@ layers in order, each ``W [K, N]`` row-major (so a layer is ``x @ W + b``) then 
    (38 797 parameters) is refused.
    (:func:`lds_floats`)
    Not served: float64 or bf16 parameters, a shared trunk, state-dependent ``std``, tanh-squashed actions, recurrent policies,
-   ``MixedBatchedANMEnv``, a backend other than the GPU library; the backward pass and the optimiser stay torch's
-   (``evaluate``).  The policy emits the unbounded Gaussian: clamping stays in the step kernel (``action_map="unit"``).  Acting twice
+   ``MixedBatchedANMEnv``, a backend other than the GPU library; the optimiser and gradient-norm clipping stay torch's (the
+   gradient of the PPO loss is ``ppo_gradient``, policy_grad.py; ``evaluate`` remains for other losses).  The policy emits the unbounded Gaussian: clamping stays in the step kernel (``action_map="unit"``).  Acting twice
    on an unchanged environment row repeats the draw, by construction.
 """
 
@@ -437,6 +437,13 @@ class GaussianMLPPolicy(_module_base()):
     def value(self, obs, values):
         """The critic alone, one launch: ``values [E]`` as ``act`` would write it, bit for bit; nothing else is touched."""
         self._launch(obs, None, values, None, True)
+
+    def ppo_gradient(self, batch_size, clip=0.2, vf_coef=0.5, ent_coef=0.0, vf_clip=None):
+        """A ``policy_grad.PPOGradient``: ``g(mb)`` overwrites ``flat.grad`` with the gradient of the clipped PPO loss of a gathered
+        minibatch, in two launches (policy_grad.py)."""
+        from .policy_grad import PPOGradient
+
+        return PPOGradient(self, batch_size, clip, vf_coef, ent_coef, vf_clip)
 
     def evaluate(self, obs, actions):
         """``(logp [B], entropy [B], values [B])`` of ``actions`` under the current parameters: plain differentiable float32 torch on

@@ -488,6 +488,34 @@ typedef struct anm_policy {
 } anm_policy;
 int anm_policy_act(const anm_policy* pi, const void* obs, void* actions, void* values, void* logp, void* stream);
 
+/* The gradient of the clipped PPO loss of one gathered minibatch with respect to the flat parameter vector of an anm_policy
+ * (gym_anm_amd/policy_grad.py has the semantics and fixes every rounding and every order of summation): the forward pass of
+ * anm_policy_act, the loss coefficients and the backward pass on the f32 matrix cores in one launch, which leaves one partial
+ * gradient per group of rows_per_partial rows, and a second launch that adds the partials in ascending order and OVERWRITES
+ * grad (no memset, no zero_grad).  No atomics: the result is a pure function of the inputs, B and rows_per_partial.  Every
+ * pointer is a caller-owned DEVICE pointer; of the anm_policy the parameters, the shape and the activation are used.
+ *   obs [B, D], actions [B, A] in io_dtype; logp_old, values_old, returns, adv, weight [B] in value_dtype: the fields of a
+ *                 minibatch of anm_minibatch_gather.  A row with weight == 0 is not read beyond its weight
+ *   grad          float32 [n_params];  stats  float32 [8]: loss, pg_loss, v_loss, entropy, approx_kl, clip_frac, n, 0
+ *   partials      float32 [ceil(B / rows_per_partial) * (n_params + 8)]: scratch between the two launches
+ *   ratio, logp, values  float32 [B]: the probability ratio, the new log-probability and the value of every row (+0 where
+ *                 weight == 0);  inv_std  float32 [A]: exp(-log_std)
+ *   clip > 0; vf_coef, ent_coef finite; vf_clip < 0 switches the value clipping off (values_old is not read then)
+ * Nothing allocates or synchronises with the host; it can be captured into a graph.
+ * Refused: what anm_policy_act refuses of the shape; a null struct or array; B outside [1, 2^24]; rows_per_partial that is not
+ * a positive multiple of 32; a dtype code other than the two; clip that is not a positive finite number; vf_coef, ent_coef or
+ * vf_clip that is not finite; a network that does not fit the backward LDS plan (policy_grad.grad_lds_floats above 40 960). */
+typedef struct anm_ppo {
+  const void *obs, *actions;
+  const void *logp_old, *values_old, *returns, *adv, *weight;
+  float *grad, *partials, *ratio, *logp, *values, *inv_std, *stats;
+  int64_t B;
+  int32_t rows_per_partial;
+  int32_t io_dtype, value_dtype;
+  float clip, vf_coef, ent_coef, vf_clip;
+} anm_ppo;
+int anm_policy_ppo_grad(const anm_policy* pi, const anm_ppo* job, void* stream);
+
 /* The reference's solver returns the final mismatch next to the iteration count (`diff` of
  * _newton_raphson_sparse, solve_load_flow.py:176-226: ||F(x)||inf of the iterate it stopped at).  With an array bound here
  * (DEVICE double [num_envs], caller-owned, alive while bound; NULL unbinds) anm_transition_f64 and anm_reset_f64 write it per
